@@ -14,14 +14,21 @@ Workloads (BASELINE.json `configs`), `--config`:
     c2wide  the same with the wide quality profile (per-read centre Q3..Q44, q <= 50 instead of Q8..Q25 +-8)
     c3      10 M reads drawn from a 5 Mbp reference, -a assembly (k-mer mode), --target_bases 50 %
     c4      the same reads, -1/-2 short-read reference (1e6 error-free 100 bp pairs), --trim --split 500
-The default run times c2 and then — outside the timed region, N = 1 only, `--no-extras` skips it — measures c2wide, c3
-and c4 (one or two steps each) and both implementations of the cut (radix select / radix sort), reported under
-`extras` on the same JSON line.
+A plain run sets up, warms up, times `--steps` steps, writes the outputs of the last step if `--dump-outputs DIR` is
+given, and prints the result line.  Everything else runs only with `--full`: the CPU baseline, the self-check of the
+N > 1 path, and — c2, N = 1 only, outside the timed region, `--no-extras` skips it — c2wide, c3 and c4 (one or two
+steps each), both implementations of the cut (radix select / radix sort) and the end-to-end runs of the command line,
+reported under `extras` on the same JSON line.
 
 Prints ONE JSON line (rank 0).  `value` = total bases over all ranks / max-over-ranks wall time of the timed steps.
-`roofline` is for the dominant kernel, timed with HIP events on the stream it runs on; `cpu_baseline` is the reference's
-own compiled code (oracle/_ref/ref_bench, kind "reference") on a bounded sample on this box's host cores (1 thread: the
-reference is single-threaded).
+`roofline` is for the dominant kernel, timed with HIP events on the stream it runs on; `cpu_baseline` (--full) is the
+reference's own compiled code (oracle/_ref/ref_bench, kind "reference") on a bounded sample on the host's cores
+(1 thread: the reference is single-threaded).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last step computed as DIR/<name>.npy (float32 / float64):
+the per-read results and the cut's report; above 2^20 entries a fixed, seeded sample (whose indices are written
+beside it), so that DIR stays under 64 MB.  The inputs are synthetic and seeded: the same arguments give the same
+inputs in every run, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -54,6 +61,25 @@ def source_sha16(*names):
 
 
 KMER_SOURCES = ("cover_queue.hip", "cover_common.h", "score_kmer.hip", "kmerset.hip", "kmerset.h", "pathtext.hip")  # what the cover kernel's requests depend on (kernel + the set's tables and text)
+DUMP_SAMPLE = 1 << 20        # --dump-outputs: entries per array beyond which a fixed, seeded sample is written
+
+
+def dump_index(n):
+    """Indices of the entries --dump-outputs writes: all n, or a fixed sample of DUMP_SAMPLE (sorted; seeded, so the same in
+    every run with the same arguments)."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    from filtlong_amd import synth
+    return np.sort(np.random.default_rng(synth.SEED).choice(n, DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(directory, arrays, suffix=""):
+    """arrays: name -> torch tensor or numpy array; each written as <directory>/<name><suffix>.npy in float64 (float32 as given)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        np.save(os.path.join(directory, name + suffix + ".npy"), a)
 
 
 def _run_ref_bench(argv):
@@ -310,9 +336,10 @@ class Batch:
         self.d_ids = torch.arange(first, first + n, dtype=torch.int64, device=dev)
 
 
-def run_kmer(ctx, torch, dev, cfg, n, steps, warmup, target_frac, fixed_len=0, profile=0):
+def run_kmer(ctx, torch, dev, cfg, n, steps, warmup, target_frac, fixed_len=0, profile=0, dump_dir=""):
     """C3 / C4 on one GPU: k-mer scoring + reads2 gather + global stage; returns the result dictionary.  profile: the reads (filtlong_amd/synth.py:
-    seq_read) — 0 = SURVEY §8(d), 1 = a third of the errors insertions and a third deletions, 2 = 30 % of the reads unrelated to the reference."""
+    seq_read) — 0 = SURVEY §8(d), 1 = a third of the errors insertions and a third deletions, 2 = 30 % of the reads unrelated to the reference.
+    dump_dir: write the last step's outputs there (--dump-outputs)."""
     from filtlong_amd import api, synth, _lib
     ref = synth.bases_read(synth.STREAM_REF, 0, 0, REF_LEN)
     t0 = time.time()
@@ -375,6 +402,18 @@ def run_kmer(ctx, torch, dev, cfg, n, steps, warmup, target_frac, fixed_len=0, p
     gather_ms, _ = ctx.timing_get("flx_reads2")
     csort_ms, _ = ctx.timing_get("flx_sort")  # k-mer mode: the children ordered by length for the one-lane-per-child fold
     ctx.timing_enable(False)
+    if dump_dir:
+        # the last step's outputs: the reads2 entries the global stage ranked (every read, or its children in its place) with
+        # their final pass flags, each read's first / last covered base, and the cut
+        i2 = dump_index(n2)
+        g2 = torch.from_numpy(i2).to(dev)
+        i1 = dump_index(n)
+        g1 = torch.from_numpy(i1).to(dev)
+        dump_outputs(dump_dir, {
+            "reads2_index": i2, "reads2_mean_q": r2["mean"][g2], "reads2_window_q": r2["win"][g2],
+            "reads2_length": r2["len"][g2].float(), "reads2_passed": r2["pass"][g2].float(),
+            "read_index": i1, "first_covered": t["first"][g1].float(), "last_covered": t["last"][g1].float(),
+            "cut": [rep.target_bases, rep.kept_bases, rep.outcome, nc, n2]})
     cover = cover_ms / max(cn, 1)
     lookups = b.bases - 15 * n
     # requests of one cover launch by class: PMC passes of this same command (tools/prof_kmer.sh), recorded in profiles/ (since
@@ -498,11 +537,11 @@ def main():
     ap.add_argument("--target-frac", type=float, default=0.5, help="--target_bases as a fraction of all bases")
     ap.add_argument("--cpu-sample-reads", type=int, default=100_000)
     ap.add_argument("--cpu-sample-reads-kmer", type=int, default=2000)
-    ap.add_argument("--full-cpu-baseline", action="store_true", help="c4: let the CPU reference hash the short reads itself (~80 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full-cpu-baseline", action="store_true", help="--full, c4: let the CPU reference hash the short reads itself (~80 s)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--e2e-kmer-pairs", type=int, default=250_000, help="short-read pairs of extras.end_to_end_cli_kmer_short (C4 has "
                     "10^6; the reference hashes ~12 000 pairs a second, so the default run takes a quarter)")
-    ap.add_argument("--no-extras", action="store_true", help="default config only: skip the c2wide / c3 / c4 / cut-path extras")
+    ap.add_argument("--no-extras", action="store_true", help="--full, default config only: skip the c2wide / c3 / c4 / cut-path extras")
     ap.add_argument("--window-size", type=int, default=250)
     ap.add_argument("--global-stage", choices=("rccl", "sharded", "replicated"), default="rccl",
                     help="N > 1: rccl = the library's own communicator (flx_rank_and_cut_comm_dev: one all-gather of the mean "
@@ -514,20 +553,26 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="take the N > 1 code path (process group, collectives) even "
                                                               "with one rank: exercises the RCCL calls on a 1-GPU box")
     ap.add_argument("--dump-flags", default="", help="write this rank's final pass flags to <path>.rank<r>.npy (tests)")
-    ap.add_argument("--verify", action="store_true", help="N = 1: run the self-check of the N > 1 path anyway (needs --force-dist)")
-    ap.add_argument("--no-verify", action="store_true", help="N > 1: skip the self-check behind the timed steps")
+    ap.add_argument("--verify", action="store_true", help="run the self-check of the N > 1 path without --full (N = 1: needs --force-dist)")
+    ap.add_argument("--no-verify", action="store_true", help="N > 1, --full: skip the self-check behind the timed steps")
     ap.add_argument("--verify-reads", type=int, default=200_000, help="reads per rank of the self-check")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: the CPU "
+                    "baseline, the self-check of the N > 1 path, and (c2, N = 1) the extras; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last step computed "
+                    "as DIR/<name>.npy (float32 / float64; a fixed, seeded sample of 2^20 entries per array beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python3 bench.py --gpus N` as the driver types it: start the N ranks ourselves — one process per GPU under
-        # torch.distributed.run on a free local port; rank 0 of that job prints the JSON line on our stdout
+        # torch.distributed.run on a free local port, in a child process; rank 0 of that job prints the JSON line on our stdout
         import socket
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
+                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
 
     import torch
     import torch.distributed as dist
@@ -565,7 +610,8 @@ def main():
     if args.config in ("c3", "c4"):
         if multi:
             sys.exit("bench.py --config %s is a single-GPU configuration" % args.config)
-        r = run_kmer(ctx, torch, dev, args.config, n, args.steps, args.warmup, args.target_frac, args.fixed_len, profile=args.read_profile)
+        r = run_kmer(ctx, torch, dev, args.config, n, args.steps, args.warmup, args.target_frac, args.fixed_len, profile=args.read_profile,
+                     dump_dir=args.dump_outputs)
         info = ctx.device_info()
         out = {"metric": "Mbases/s scored+sorted", "value": r["value"], "unit": "Mbases/s", "n_gpus": 1, "steps": args.steps,
                "warmup": args.warmup, "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak",
@@ -574,7 +620,7 @@ def main():
                           "device": info["name"]},
                "roofline": r["roofline"], "stage_ms_per_step": r["stage_ms_per_step"], "lookups_per_s_G": r["lookups_per_s_G"],
                "children": r["children"], "set_size": r["set_size"], "cut": r["cut"]}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_kmer(args.config, args.cpu_sample_reads_kmer, args.full_cpu_baseline)
         print(json.dumps(out), flush=True)
         ctx.close()
@@ -681,8 +727,16 @@ def main():
     if args.dump_flags:
         torch.cuda.synchronize()
         np.save("%s.rank%d.npy" % (args.dump_flags, rank), t_pass.cpu().numpy())
+    if args.dump_outputs:
+        # the last step's outputs for this rank's reads: mean and window quality, final pass flags, and the cut (rank r > 0: suffix .rank<r>)
+        idx = dump_index(n)
+        g = torch.from_numpy(idx).to(dev)
+        dump_outputs(args.dump_outputs, {
+            "read_index": idx + first, "mean_q": t_mean[g], "window_q": t_win[g], "passed": t_pass[g].float(),
+            "cut": [rep.target_bases, rep.kept_bases, rep.outcome, rep.audited, rep.exact_fallback, int(t_pass.sum().item())]},
+            suffix=".rank%d" % rank if rank else "")
     verify = None
-    if multi and not args.no_verify and (world > 1 or args.verify):
+    if multi and not args.no_verify and ((args.full and world > 1) or args.verify):
         try:
             verify = verify_ranks(ctx, torch, dist, dev, rank, world, args, args.backend == "nccl")
         except Exception as e:  # (the check must not cost the line; a failure is reported in it)
@@ -755,10 +809,10 @@ def main():
         }
         if verify is not None:
             out["verify"] = verify
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_phred(args.cpu_sample_reads)
 
-        if world == 1 and not multi and args.config == "c2" and not args.no_extras:
+        if args.full and world == 1 and not multi and args.config == "c2" and not args.no_extras:
             extras = {}
             # (1) both implementations of the cut on this batch's records: weighted radix SELECT (what the steps above ran)
             #     and radix SORT + scan (north_star's "device radix sort over final_score"); wall time of the whole stage

@@ -176,7 +176,7 @@ def test_bench_two_processes_one_gpu(tmp_path, stage):
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", "29731", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--reads", "20000", "--backend", "gloo", "--global-stage", stage, "--dump-flags", two],
+                        "--warmup", "1", "--reads", "20000", "--backend", "gloo", "--global-stage", stage, "--full", "--dump-flags", two],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     import json
@@ -237,7 +237,7 @@ def test_bench_starts_its_own_ranks(tmp_path, shim):
                        stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads",
-                        "20000", "--dump-flags", two], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "20000", "--full", "--dump-flags", two], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -264,7 +264,7 @@ def test_bench_eight_ranks_exactly_as_the_driver_types_it(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "FLX_RANK_SORT")}
     env["FLX_RCCL_LIB"] = os.path.join(shim_dir, "libloopback_rccl.so")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--reads", "100000",
-                        "--verify-reads", "20000"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
+                        "--verify-reads", "20000", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1
