@@ -68,7 +68,7 @@ static void build_phred_lut(double *lut257) {
 static const char *const kKnownEnv[] = {
     "FLX_API_TIMING", "FLX_KMER_COVER", "FLX_KMER_FOLD", "FLX_KMER_FOLD_EVENTS", "FLX_KMER_FOLD_GRID", "FLX_KMER_FOLD_STREAMS", "FLX_KMER_LOCUS",
     "FLX_KMER_LOCUS_BUILD", "FLX_KMER_PAIRTABLE", "FLX_KMER_PREFILTER", "FLX_KMER_SAFE1", "FLX_KMER_TEXT_ORDER", "FLX_PHRED_KERNEL",
-    "FLX_PHRED_TABLES", "FLX_RANK_EXACT", "FLX_RANK_SORT", "FLX_RCCL_LIB",
+    "FLX_PHRED_LONG_MIN", "FLX_PHRED_TABLES", "FLX_RANK_EXACT", "FLX_RANK_SORT", "FLX_RCCL_LIB",
 };
 static const char *const kOwnPrefixes[] = {"FLX_KMER_", "FLX_PHRED_", "FLX_RANK_", "FLX_RCCL_", "FLX_API_"};
 extern char **environ;
@@ -257,7 +257,7 @@ int flx_scratch(flx_ctx *ctx, size_t bytes, void **out) {
 }
 
 int flx_workspace(flx_ctx *ctx, int slot, size_t bytes, void **out) {
-    if (slot < 0 || slot >= 3) return flx_fail(ctx, FLX_ERR_INVALID, "workspace slot %d", slot);
+    if (slot < 0 || slot >= 4) return flx_fail(ctx, FLX_ERR_INVALID, "workspace slot %d", slot);
     if (bytes > ctx->ws_bytes[slot]) {
         FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->ws[slot]) (void)hipFree(ctx->ws[slot]);

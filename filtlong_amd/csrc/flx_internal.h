@@ -54,8 +54,8 @@ struct flx_ctx {
     size_t scratch_bytes = 0;
     // grow-only workspaces of the k-mer scoring path (kept between calls: a 12 GB hipMalloc + hipFree per batch costs
     // more than the fold kernels)
-    void *ws[3] = {nullptr, nullptr, nullptr};
-    size_t ws_bytes[3] = {0, 0, 0};
+    void *ws[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t ws_bytes[4] = {0, 0, 0, 0};
 };
 
 int flx_fail(flx_ctx *ctx, int code, const char *fmt, ...);
@@ -93,7 +93,8 @@ struct flx_time_scope {
 
 // grow-only scratch on the device
 int flx_scratch(flx_ctx *ctx, size_t bytes, void **out);
-// grow-only workspace `slot` (0: per-read arrays of the k-mer path, 1: its coverage bit plane); valid until the next call
+// grow-only workspace `slot` (0: per-read arrays of the k-mer path, 1: its coverage bit plane, 2: its child arrays, 3: the Phred
+// path of long reads); valid until the next call
 // with the same slot
 int flx_workspace(flx_ctx *ctx, int slot, size_t bytes, void **out);
 

@@ -376,7 +376,6 @@ static constexpr size_t kLutBytes = 2 * LUT_PAD * sizeof(double);
 int flx_launch_score_phred(flx_ctx *ctx, const uint8_t *d_plane, uint64_t plane_bytes, const uint64_t *d_offsets,
                            const int32_t *d_lengths, const uint32_t *d_order, uint64_t n_reads,
                            const flx_params *p, flx_score_out_dev out) {
-    (void)plane_bytes;
     if (n_reads == 0) return FLX_OK;
     if (p->window_size <= 0) return flx_fail(ctx, FLX_ERR_INVALID, "window_size must be positive");
     FLX_CHECK(flx_ensure_lut_d(ctx, p->window_size));
@@ -409,23 +408,34 @@ int flx_launch_score_phred(flx_ctx *ctx, const uint8_t *d_plane, uint64_t plane_
     if ((slots16 & 1) == 0) slots16 += 1;       // odd number of 16-byte slots per row: b128 rows never collide
     const size_t ring_bytes = (size_t)64 * slots16 * 16;
 
-    const uint64_t n_waves = (n_reads + 63) / 64;
     int waves = (int)((kLdsBudget - kLutBytes) / ring_bytes);
     const char *env = getenv("FLX_PHRED_KERNEL");  // test hook: "direct" / "ring" force the older kernels
     const bool force_direct = env && strcmp(env, "direct") == 0;
     const bool force_ring = env && strcmp(env, "ring") == 0;
     const bool force_stream = env && strcmp(env, "stream") == 0;
     const bool force_dual = env && strcmp(env, "dual") == 0;
-    if (force_stream) return flx_launch_score_phred_stream(ctx, a);
-    if (force_dual) return flx_launch_score_phred_dual(ctx, a);
+    // Reads from a length threshold on are scored by the cooperative kernels of score_phred_long.hip; whichever kernel is chosen
+    // below gets the rest of the batch.  The register-history kernel makes the split after the synchronisation it takes anyway.
+    PhredLong lp;
+    FLX_CHECK(flx_phred_long_detect(ctx, a, plane_bytes, &lp));
+    if (force_stream || force_dual) {
+        FLX_CHECK(flx_phred_long_split(ctx, a, &lp));
+        if (a.n_reads == 0) return FLX_OK;
+        return force_stream ? flx_launch_score_phred_stream(ctx, a) : flx_launch_score_phred_dual(ctx, a);
+    }
     if (!force_direct && !force_ring) {  // default: the register-history kernel, where the window size has an instantiation ...
         bool launched = false;
         a.n_slots = 0;
         a.stride = 0;
-        FLX_CHECK(flx_launch_score_phred_regs(ctx, a, &launched));
+        FLX_CHECK(flx_launch_score_phred_regs(ctx, a, &launched, &lp));
         if (launched) return FLX_OK;
+        FLX_CHECK(flx_phred_long_split(ctx, a, &lp));
+        if (a.n_reads == 0) return FLX_OK;
         return flx_launch_score_phred_dual(ctx, a);  // ... and the dual-slot kernel beyond (window sizes from 624 on, any size)
     }
+    FLX_CHECK(flx_phred_long_split(ctx, a, &lp));
+    if (a.n_reads == 0) return FLX_OK;
+    const uint64_t n_waves = (a.n_reads + 63) / 64;
 
     if (waves >= 1 && !force_direct) {
         if (waves > 7) waves = 7;
@@ -469,7 +479,7 @@ int flx_launch_score_phred(flx_ctx *ctx, const uint8_t *d_plane, uint64_t plane_
         a.stride = 0;
         a.ticket = nullptr;
         a.n_groups = 0;
-        const unsigned grid = (unsigned)((n_reads + 255) / 256);
+        const unsigned grid = (unsigned)((a.n_reads + 255) / 256);
         ctx->last_phred_kernel = "flx_score_phred_direct";
         flx_time_begin(ctx, "flx_score_phred_direct");
         hipLaunchKernelGGL(flx_score_phred_direct, dim3(grid), dim3(256), 0, ctx->stream, a);

@@ -88,12 +88,34 @@ __device__ __forceinline__ void finish_read(const PhredArgs &a, uint32_t rid, in
     a.passed[rid] = hard_cutoffs(a.p, L, mean, window);
 }
 
+// score_phred_long.hip: reads from a length threshold on are scored cooperatively, many lanes per read.
+constexpr int PHRED_LONG_NB = 13;                // length buckets of the detection: 2^18 .. 2^30 bases and beyond
+constexpr long long PHRED_LONG_FLOOR = 1 << 18;  // the threshold's floor
+struct PhredLong {
+    bool on = false;       // the detection kernel ran
+    bool fetched = false;  // its counts are copied to the host (valid after the next synchronisation of the stream)
+    bool done = false;     // the split has been made
+    bool forced = false;   // FLX_PHRED_LONG_MIN gave the threshold
+    int t0 = 0;            // the smallest threshold counted
+    uint64_t plane_bytes = 0;  // stands for the batch's bases in the threshold
+    unsigned long long *d_counts = nullptr;
+    unsigned long long h_counts[3 * PHRED_LONG_NB] = {};
+};
 
 }  // namespace flx_phred
 
+// Before the Phred kernel: counts the batch's long reads (nothing when FLX_PHRED_LONG_MIN=0) ...
+int flx_phred_long_detect(flx_ctx *ctx, const flx_phred::PhredArgs &a, uint64_t plane_bytes, flx_phred::PhredLong *lp);
+// ... enqueues the copy of the counts (the caller synchronises the stream: one synchronisation serves both) ...
+int flx_phred_long_fetch(flx_ctx *ctx, flx_phred::PhredLong *lp);
+// ... and, when there are long reads, scores them on the context's stream and leaves in `a` the rest of the batch: a stably compacted
+// order of the other reads and their count (0: nothing is left for the Phred kernel).  Synchronises only if the counts are not
+// fetched yet; a no-op after the first call.
+int flx_phred_long_split(flx_ctx *ctx, flx_phred::PhredArgs &a, flx_phred::PhredLong *lp);
+
 // score_phred_regs.hip: the register-history kernel.  *launched = false when the window size has no instantiation
-// (the caller then uses the LDS-ring kernel).
-int flx_launch_score_phred_regs(flx_ctx *ctx, flx_phred::PhredArgs a, bool *launched);
+// (the caller then uses the LDS-ring kernel).  It makes the long-read split (lp) after the synchronisation its table sample takes.
+int flx_launch_score_phred_regs(flx_ctx *ctx, flx_phred::PhredArgs a, bool *launched, flx_phred::PhredLong *lp);
 // score_phred_regs.hip: any window size, both window edges streamed from global memory (used where the LDS ring does not fit)
 int flx_launch_score_phred_stream(flx_ctx *ctx, flx_phred::PhredArgs a);
 // score_phred_regs.hip: any window size, the trailing edge as a second LDS-DMA stream (nothing of the window stays on chip)

@@ -870,7 +870,7 @@ int flx_launch_score_phred_dual(flx_ctx *ctx, PhredArgs a) {
     return FLX_OK;
 }
 
-int flx_launch_score_phred_regs(flx_ctx *ctx, PhredArgs a, bool *launched) {
+int flx_launch_score_phred_regs(flx_ctx *ctx, PhredArgs a, bool *launched, PhredLong *lp) {
     *launched = false;
     const int A = a.ws / 16;
     if (A > 38) return FLX_OK;  // the register-history kernel serves window sizes 1 .. 623 (A = ws / 16 = 0 .. 38); beyond: the dual-slot kernel
@@ -882,13 +882,13 @@ int flx_launch_score_phred_regs(flx_ctx *ctx, PhredArgs a, bool *launched) {
     a.ticket = (unsigned int *)scr;
     a.redo_count = (unsigned int *)scr + 1;
     a.redo_list = (uint32_t *)((char *)scr + 2048);
-    a.n_groups = (unsigned int)((a.n_reads + 63) / 64);
     FLX_HIP(ctx, hipMemsetAsync(scr, 0, 2048, ctx->stream));
     if (!env || (strcmp(env, "private") != 0 && strcmp(env, "plain") != 0)) {
         unsigned int h[256];
         unsigned int *d_hist = (unsigned int *)((char *)scr + 64);
         hipLaunchKernelGGL(flx_phred_sample, dim3(64), dim3(256), 0, ctx->stream, a, d_hist);
         FLX_HIP(ctx, hipMemcpyAsync(h, d_hist, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+        FLX_CHECK(flx_phred_long_fetch(ctx, lp));  // the long-read counts come back with the same synchronisation
         FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         double tot = 0.0, conflicts = 0.0;
         for (int i = 0; i < 256; ++i) tot += h[i];
@@ -907,6 +907,12 @@ int flx_launch_score_phred_regs(flx_ctx *ctx, PhredArgs a, bool *launched) {
         }
         priv = !high && 496.0 * conflicts > 3.0;  // bytes >= 128 would all go through the redo path: stay plain
     }
+    FLX_CHECK(flx_phred_long_split(ctx, a, lp));
+    if (a.n_reads == 0) {  // every read was long
+        *launched = true;
+        return FLX_OK;
+    }
+    a.n_groups = (unsigned int)((a.n_reads + 63) / 64);
     if (A <= 7) FLX_CHECK(flx_launch_score_phred_regs_part0(ctx, a, priv, launched));
     else if (A <= 12) FLX_CHECK(flx_launch_score_phred_regs_part1(ctx, a, priv, launched));
     else if (A <= 17) FLX_CHECK(flx_launch_score_phred_regs_part2(ctx, a, priv, launched));

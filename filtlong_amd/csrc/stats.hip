@@ -29,6 +29,9 @@
 
 #include "flx_internal.h"
 #include "rank_internal.h"
+#include "fold_map.h"
+
+using namespace flx_fold;
 
 namespace {
 
@@ -52,11 +55,6 @@ struct ChunkMeta {
     int e;             // guessed unbiased binade exponent of the running sum, or INT_MIN: no map
     int pad;
 };
-constexpr int NO_MAP = -2147483647 - 1;
-
-__device__ __forceinline__ int exponent_of(double v) {  // unbiased exponent of a positive normal double
-    return (int)((__double_as_longlong(v) >> 52) & 0x7ff) - 1023;
-}
 
 template <typename F>
 __global__ void __launch_bounds__(256) k_chunk_sums(uint64_t n, const double *x, F f, double *chunk_sum,
@@ -118,44 +116,6 @@ __global__ void __launch_bounds__(256) k_minmax(uint64_t n_chunks, const double 
         out[0] = lo;
         out[1] = hi;
     }
-}
-
-struct Map2 {
-    long long a0, a1;
-};
-__device__ __forceinline__ Map2 compose(const Map2 &a, const Map2 &b) {  // a first, then b
-    Map2 c;
-    c.a0 = a.a0 + ((a.a0 & 1) ? b.a1 : b.a0);
-    c.a1 = a.a1 + (((1 + a.a1) & 1) ? b.a1 : b.a0);
-    return c;
-}
-
-// integer map of one addend v >= 0 (finite) for a running sum in binade e; ok = false if v cannot be added
-// without leaving the binade
-__device__ __forceinline__ Map2 elem_map(double v, int e, bool &ok) {
-    Map2 m;
-    m.a0 = m.a1 = 0;
-    const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
-    if ((bits << 1) == 0) return m;  // +-0
-    const int eb = (int)((bits >> 52) & 0x7ff);
-    unsigned long long mx = bits & 0x000fffffffffffffull;
-    int ex;
-    if (eb == 0) ex = -1022;  // subnormal
-    else { mx |= 1ull << 52; ex = eb - 1023; }
-    const int sh = e - ex;  // v / u = mx >> sh
-    if (sh < 0) { ok = false; return m; }
-    if (sh == 0) { m.a0 = m.a1 = (long long)mx; return m; }
-    if (sh >= 55) return m;
-    const unsigned long long f = mx >> sh;
-    const unsigned long long rem = mx & ((1ull << sh) - 1ull);
-    const unsigned long long half = 1ull << (sh - 1);
-    if (rem > half) m.a0 = m.a1 = (long long)(f + 1);
-    else if (rem < half) m.a0 = m.a1 = (long long)f;
-    else {  // tie: the sum rounds to even
-        m.a0 = (long long)(f + (f & 1));
-        m.a1 = (long long)(f + ((f + 1) & 1));
-    }
-    return m;
 }
 
 template <typename F>
@@ -236,13 +196,6 @@ __global__ void __launch_bounds__(256) k_batch_maps(const ChunkMeta *meta, uint6
     }
 }
 
-__device__ __forceinline__ double readlane_f64(double v, int src) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), src);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 // exact application of an integer map to the running sum: returns true and updates S iff S is in binade e and stays there
 __device__ __forceinline__ bool apply_map(double &S, int e, long long a0, long long a1) {
     const unsigned long long sb = (unsigned long long)__double_as_longlong(S);
@@ -266,12 +219,6 @@ __device__ __forceinline__ Map2 wave_scan_maps(Map2 m, int lane) {
         if (lane >= o) m = compose(prev, m);
     }
     return m;
-}
-
-__device__ __forceinline__ bool normal_positive(double S) {
-    const unsigned long long sb = (unsigned long long)__double_as_longlong(S);
-    const int eb = (int)((sb >> 52) & 0x7ff);
-    return (sb >> 63) == 0 && eb >= 1 && eb <= 2046;
 }
 
 // Advances S (positive, normal, in binade e) through the maps of lanes start, start + 1, ... for as long as they are usable
