@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "flx_comm_init", "flx_comm_destroy", "flx_comm_rank", "flx_comm_world", "flx_comm_sum_u64", "flx_kmerset_create", "flx_kmerset_destroy", "flx_kmerset_add_assembly",
     "flx_kmerset_add_short_reads", "flx_kmerset_finalize", "flx_kmerset_size", "flx_kmerset_contains",
     "flx_last_phred_kernel", "flx_last_kmer_locus", "flx_last_kmer_fold_grid", "flx_last_kmer_cover", "flx_last_kmer_handed_over", "flx_synth_qual_dev", "flx_synth_qual_profile_dev", "flx_synth_seq_dev", "flx_synth_seq_profile_dev",
+    "flx_bgzf_bound", "flx_bgzf_compress_dev", "flx_bgzf_create", "flx_bgzf_compress", "flx_bgzf_destroy",
 ]
 
 
@@ -166,5 +167,11 @@ def load():
     L.flx_synth_qual_profile_dev.argtypes = [vp, u64, C.c_int, vp, u64, vp, vp, vp, u64]
     L.flx_synth_seq_dev.argtypes = [vp, u64, vp, u64, vp, vp, vp, u64, vp, u64]
     L.flx_synth_seq_profile_dev.argtypes = [vp, u64, C.c_int, vp, u64, vp, vp, vp, u64, vp, u64]
+    L.flx_bgzf_bound.argtypes = [u64, i32, C.POINTER(u64)]
+    L.flx_bgzf_compress_dev.argtypes = [vp, vp, u64, i32, vp, u64, C.POINTER(u64)]
+    L.flx_bgzf_create.argtypes = [vp, u64, C.c_uint, C.POINTER(vp)]
+    L.flx_bgzf_compress.argtypes = [vp, vp, u64, i32, vp, u64, C.POINTER(u64)]
+    L.flx_bgzf_destroy.argtypes = [vp]
+    L.flx_bgzf_destroy.restype = None
     _lib = L
     return L

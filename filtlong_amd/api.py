@@ -385,6 +385,60 @@ class Context:
         return rc
 
 
+    def bgzf_compress_dev(self, d_in, n, d_out, out_cap, eof=True):
+        """flx_bgzf_compress_dev: BGZF of the n device bytes at d_in into d_out (device, out_cap bytes) -> bytes written."""
+        got = C.c_uint64()
+        self._check(self.L.flx_bgzf_compress_dev(self.h, d_in, int(n), BGZF_EOF if eof else 0, d_out, int(out_cap), C.byref(got)))
+        return got.value
+
+
+BGZF_EOF = 1  # FLX_BGZF_EOF
+
+
+def bgzf_bound(n, eof=True):
+    """The most bytes a BGZF compression of n bytes writes (flx_bgzf_bound)."""
+    b = C.c_uint64()
+    rc = _lib.load().flx_bgzf_bound(int(n), BGZF_EOF if eof else 0, C.byref(b))
+    if rc:
+        raise FlxError(rc, "flx_bgzf_bound")
+    return b.value
+
+
+class Bgzf:
+    """Host-to-host BGZF compressor (flx_bgzf) with `slots` pinned slots of `slot_bytes`; compress() may be called from
+    several threads at once (ctypes releases the GIL for the call)."""
+
+    def __init__(self, ctx, slot_bytes=16 << 20, slots=4):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx._check(ctx.L.flx_bgzf_create(ctx.h, int(slot_bytes), int(slots), C.byref(h)))
+        self.h = h
+        ctx._sets.append(weakref.ref(self))
+
+    def compress(self, data, eof=True, out_cap=None):
+        src = np.frombuffer(bytes(data), dtype=np.uint8)
+        cap = bgzf_bound(len(src), eof) if out_cap is None else int(out_cap)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        got = C.c_uint64()
+        rc = self.ctx.L.flx_bgzf_compress(self.h, src.ctypes.data if len(src) else None, len(src), BGZF_EOF if eof else 0,
+                                          out.ctypes.data, cap, C.byref(got))
+        if rc:
+            raise FlxError(rc, "flx_bgzf_compress")
+        return out[:got.value].tobytes()
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:  # destroyed before its context (Context.close() closes it first)
+                self.ctx.L.flx_bgzf_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Kmers:
     """Reference 16-mer set on the device — mirrors the reference's Kmers (src/kmers.h:28-56)."""
 

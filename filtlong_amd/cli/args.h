@@ -31,6 +31,7 @@ struct Args {
     long long window_size = 250;
     bool verbose = false;
     int gpus = 1;  // not a reference flag: --gpus N scores on N GPUs of this node (one process per GPU)
+    bool gzip = false;  // not a reference flag: --gzip writes stdout as BGZF, compressed on the GPU
 };
 enum ParsingResult { GOOD, BAD, HELP, VERSION };
 
@@ -102,7 +103,7 @@ static long long read_ll(const std::string &name, const std::string &value, long
 // terminal on STDOUT (TIOCGWINSZ; indent 1 / 2 / 3 / 4 for widths up to 60 / 80 / 120 / beyond).  When stdout is no terminal the
 // reference reads the width out of an untouched `struct winsize` — 0 in practice: the description comes out one word per line and,
 // the other widths being unsigned differences that wrap around, nothing else is wrapped at all.  Both cases are restated here.
-// (--gpus, this binary's one flag of its own, is documented in README.md: the menu is the reference's.)
+// (--gpus and --gzip, this binary's flags of its own, are documented in README.md: the menu is the reference's.)
 static std::vector<std::string> help_wrap(const std::string &in, size_t width, size_t first = 0) {  // src/args.h:94-149
     std::vector<std::string> out;
     size_t cur = first ? first : width, linesize = 0;
@@ -264,6 +265,7 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
             else if (flag == "split") { a.split = read_int_suffix("split", need("split")); a.split_set = true; }
             else if (flag == "window_size") a.window_size = read_ll("int", need("window_size"), a.window_size);
             else if (flag == "gpus") a.gpus = (int)read_ll("int", need("gpus"), a.gpus);
+            else if (flag == "gzip") a.gzip = true;
             else throw ParseError("Error: flag could not be matched: " + flag);
         }
     } catch (const ParseError &e) {

@@ -883,6 +883,23 @@ int main(int argc, char **argv) {
             out += '\n';
         }
     };
+    // --gzip: every piece is compressed into BGZF members by the worker that produced it (flx_bgzf may be called from all of them at
+    // once: ~16 MiB pieces are ~257 members each, so the concurrent workers are what keeps the device full); the pieces then go out
+    // in order like plain ones, and the end-of-file block follows once the output pass is complete.
+    flx_bgzf *gz = nullptr;
+    if (args.gzip && flx_bgzf_create(ctx, 16u << 20, (unsigned)std::min<size_t>(host_threads(), 16), &gz) != FLX_OK)
+        return fail_flx(ctx, "gzip");
+    auto gz_piece = [&](std::string &buf) -> bool {
+        if (!gz || buf.empty()) return true;
+        uint64_t bound = 0, got = 0;
+        if (flx_bgzf_bound(buf.size(), 0, &bound) != FLX_OK) return false;
+        std::string z(bound, '\0');
+        if (flx_bgzf_compress(gz, buf.data(), buf.size(), 0, &z[0], bound, &got) != FLX_OK) return false;
+        z.resize(got);
+        buf.swap(z);
+        return true;
+    };
+    static const char kBgzfEof[28] = {0x1f, (char)0x8b, 8, 4, 0, 0, 0, 0, 0, (char)0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     bool pieces_ok = true;
     if (!streamed) {
         // The passed records are cut out of the mapped input by several threads, ~16 MiB of output per piece.  Every piece's
@@ -951,7 +968,7 @@ int main(int argc, char **argv) {
             // of it, one exchange — with the same pwrite / pwritev pieces a single rank uses, and nothing is written twice.  A pipe, a
             // terminal, or ranks under a launcher (no common stdout): part files that rank 0 streams out in order, as before.
             std::vector<uint64_t> v(2 + 2 * (size_t)world, 0);
-            if (rank == 0 && g_shared_out >= 0 && !getenv("FLX_CLI_ORDERED_OUTPUT")) {
+            if (rank == 0 && g_shared_out >= 0 && !getenv("FLX_CLI_ORDERED_OUTPUT") && !gz) {  // (--gzip: part files, sizes are not known ahead)
                 fflush(stdout);
                 struct stat st;
                 const int fl = fcntl(g_shared_out, F_GETFL);
@@ -985,7 +1002,7 @@ int main(int argc, char **argv) {
             if (fail_writes) return false;
             if (!g_direct_pieces) {  // a pipe / terminal / append-mode file: the caller writes the formatted piece in order
                 for (uint64_t i = piece_first[j]; i < piece_first[j + 1]; ++i) emit(buf, i, kept.recs[reads2[i].rec]);
-                return true;
+                return gz_piece(buf);
             }
             // regular file: this thread writes the piece itself, ranges of the mapping and formatted records interleaved
             std::vector<struct iovec> iov;
@@ -1032,7 +1049,7 @@ int main(int argc, char **argv) {
             if (!flush()) return false;
             buf.clear();
             return at == g_direct_base + (off_t)piece_at[j + 1];
-        }, sink, &piece_at, shared_file ? shared_base : (off_t)-1);
+        }, sink, gz ? nullptr : &piece_at, shared_file ? shared_base : (off_t)-1);  // (--gzip: formatted and compressed, in order)
         // (several ranks: a rank that could not write — a full disk under its pwrite — still goes to the exchange below, where
         // every rank learns of it and rank 0 says why; leaving here would strand the others in that exchange)
         if (!ok && world == 1) { std::cerr << "Error: could not write the output\n"; return 1; }
@@ -1071,13 +1088,15 @@ int main(int argc, char **argv) {
                 if (r.name.sv() != names[rec - lo_rec] || (int32_t)r.seq.size() != lengths[rec - lo_rec]) return false;
                 for (; cur < r2_at[j + 1] && reads2[cur].rec == rec; ++cur) emit(buf, cur, r);
             }
-            return true;
+            return gz_piece(buf);
         }, sink, nullptr);
         if (!ok && world == 1) { std::cerr << "Error: " << args.input_reads << " could not be read a second time (did it change?)\n"; return 1; }
         pieces_ok = ok;  // (several ranks: to the exchange below, like a failed write)
     }
     // a sink that did not take everything (disk full, the reader of a pipe gone while SIGPIPE is ignored) ends the job with status 1
-    const bool sink_ok = pieces_ok && fflush(sink) == 0 && !ferror(sink);
+    const bool sink_ok = pieces_ok && (!gz || world > 1 || fwrite(kBgzfEof, 1, 28, sink) == 28) && fflush(sink) == 0 && !ferror(sink);
+    flx_bgzf_destroy(gz);
+    gz = nullptr;
     if (world == 1 && !sink_ok) { std::cerr << "Error: could not write the output\n"; return 1; }
     if (world > 1) {
         fclose(sink);
@@ -1115,7 +1134,7 @@ int main(int argc, char **argv) {
                     return 1;
                 }
             }
-            if (fflush(stdout) != 0) { std::cerr << "Error: could not write the output\n"; return 1; }
+            if ((args.gzip && fwrite(kBgzfEof, 1, 28, stdout) != 28) || fflush(stdout) != 0) { std::cerr << "Error: could not write the output\n"; return 1; }
         }
     }
     stage("output");

@@ -1,0 +1,311 @@
+// bgzf.hip — BGZF compression on the GPU: gzip members of at most 65280 input bytes, each with the BC extra field
+// (SAM/BAM specification §4.1), optionally followed by the 28-byte end-of-file block.
+//
+// k_bgzf_members   one workgroup per member (the phases of bgzf_member.h): the compressed member in a 65664-byte slot;
+// k_bgzf_scan      exclusive scan of the members' sizes of one batch onto the running total (and the capacity check);
+// k_bgzf_gather    one workgroup per member: its bytes into the contiguous output;
+// k_bgzf_eof       the end-of-file block.
+// A call runs the members in batches of at most kBatch (the match table of a batch lives in device scratch); everything stays
+// in stream order, the host reads back 16 bytes at the end.  The output is a pure function of (bytes, flags).
+#include <condition_variable>
+#include <mutex>
+
+#include "flx_internal.h"
+#include "bgzf_member.h"
+
+using namespace bgzf;
+
+namespace {
+
+constexpr uint32_t kBatch = 1024;   // members per launch (k_bgzf_scan scans one batch with one workgroup)
+constexpr int kScanThreads = 1024;
+
+const uint8_t kEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+struct Work {  // device scratch of one call
+    uint64_t *state;  // [0] bytes so far (needed size), [1] capacity exceeded
+    uint32_t *sizes;  // [kBatch]
+    uint64_t *offs;   // [kBatch]
+    uint8_t *slots;   // [batch * BG_SLOT]
+    uint32_t *mt;     // [batch * BG_MEMBER]
+};
+
+size_t work_bytes(uint64_t n) {
+    const uint64_t members = (n + BG_MEMBER - 1) / BG_MEMBER;
+    const uint64_t b = members < kBatch ? members : kBatch;
+    return 256 + 4 * kBatch + 8 * kBatch + b * BG_SLOT + b * BG_MEMBER * 4;
+}
+
+Work carve(void *p, uint64_t n) {
+    const uint64_t members = (n + BG_MEMBER - 1) / BG_MEMBER;
+    const uint64_t b = members < kBatch ? members : kBatch;
+    uint8_t *c = (uint8_t *)p;
+    Work w;
+    w.state = (uint64_t *)c;
+    w.sizes = (uint32_t *)(c + 256);
+    w.offs = (uint64_t *)(c + 256 + 4 * kBatch);
+    w.slots = c + 256 + 12 * kBatch;
+    w.mt = (uint32_t *)(w.slots + b * BG_SLOT);
+    return w;
+}
+
+__global__ void __launch_bounds__(BG_NT) k_bgzf_members(const uint8_t *in, uint64_t n_total, uint64_t first_member,
+                                                        uint32_t *mt, uint8_t *slots, uint32_t *sizes) {
+    __shared__ Shared S;
+    const int t = threadIdx.x;
+    const uint64_t off = (first_member + blockIdx.x) * (uint64_t)BG_MEMBER;
+    const uint32_t n = n_total - off < BG_MEMBER ? (uint32_t)(n_total - off) : BG_MEMBER;
+    const uint8_t *src = in + off;
+    uint32_t *m = mt + (size_t)blockIdx.x * BG_MEMBER;
+    uint8_t *slot = slots + (size_t)blockIdx.x * BG_SLOT;
+
+    ph_load(t, S, src, n, ((uintptr_t)src & 15) == 0);
+    __syncthreads();
+    ph_crc(t, S, n);
+    __syncthreads();
+    ph_crc_final(t, S, n);
+    for (uint32_t base = 0; base < n; base += BG_NT) {
+        ph_lookup(t, S, n, base, m);
+        __syncthreads();
+        ph_insert(t, S, n, base);
+        __syncthreads();
+    }
+    ph_hist(t, S, n, m);
+    __syncthreads();
+    ph_rank(t, S);
+    __syncthreads();
+    ph_codes(t, S);
+    __syncthreads();
+    ph_header(t, S, n);
+    __syncthreads();
+    ph_count(t, S, n, m);
+    __syncthreads();
+    ph_scan(t, S);
+    __syncthreads();
+    ph_zero(t, S, slot);
+    __syncthreads();
+    ph_pack(t, S, n, m, slot);
+    __syncthreads();
+    ph_frame(t, S, n, slot, sizes + blockIdx.x);
+}
+
+// offs[k] = running total + sizes of the members before k; the running total moves on; past `cap` the flag is set for good
+__global__ void __launch_bounds__(kScanThreads) k_bgzf_scan(const uint32_t *sizes, uint32_t m, uint64_t *offs, uint64_t *state,
+                                                            uint64_t cap) {
+    __shared__ uint32_t s[kScanThreads];
+    __shared__ uint64_t base;
+    const int t = threadIdx.x;
+    const uint32_t v = (uint32_t)t < m ? sizes[t] : 0;
+    s[t] = v;
+    if (t == 0) base = state[0];
+    __syncthreads();
+    for (int d = 1; d < kScanThreads; d <<= 1) {
+        const uint32_t a = t >= d ? s[t - d] : 0;
+        __syncthreads();
+        s[t] += a;
+        __syncthreads();
+    }
+    if ((uint32_t)t < m) offs[t] = base + s[t] - v;
+    if (t == 0) {
+        const uint64_t total = base + s[kScanThreads - 1];
+        if (total > cap) state[1] = 1;
+        state[0] = total;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_bgzf_gather(const uint8_t *slots, const uint32_t *sizes, const uint64_t *offs,
+                                                     const uint64_t *state, uint8_t *out) {
+    if (state[1]) return;  // capacity exceeded: nothing is written
+    const uint8_t *slot = slots + (size_t)blockIdx.x * BG_SLOT;
+    const uint32_t sz = sizes[blockIdx.x];
+    uint8_t *dst = out + offs[blockIdx.x];
+    for (uint32_t j = threadIdx.x; j < sz; j += 256) dst[j] = j < 18 ? slot[j] : slot[BG_DEFL_OFF + j - 18];
+}
+
+struct EofBlock {
+    uint8_t b[28];
+};
+
+__global__ void k_bgzf_eof(uint64_t *state, uint8_t *out, uint64_t cap, EofBlock e) {
+    const uint64_t at = state[0];
+    if (threadIdx.x == 0) {
+        if (at + 28 > cap) state[1] = 1;
+        if (!state[1])
+            for (int k = 0; k < 28; ++k) out[at + k] = e.b[k];
+        state[0] = at + 28;
+    }
+}
+
+// every launch of one call, on `st`; *h_state (host) gets the needed size and the capacity flag
+hipError_t bgzf_run(hipStream_t st, const uint8_t *d_in, uint64_t n, int flags, uint8_t *d_out, uint64_t cap, void *work,
+                    uint64_t *h_state) {
+    Work w = carve(work, n);
+    hipError_t e = hipMemsetAsync(w.state, 0, 16, st);
+    if (e != hipSuccess) return e;
+    const uint64_t members = (n + BG_MEMBER - 1) / BG_MEMBER;
+    for (uint64_t first = 0; first < members; first += kBatch) {
+        const uint32_t b = (uint32_t)(members - first < kBatch ? members - first : kBatch);
+        hipLaunchKernelGGL(k_bgzf_members, dim3(b), dim3(BG_NT), 0, st, d_in, n, first, w.mt, w.slots, w.sizes);
+        hipLaunchKernelGGL(k_bgzf_scan, dim3(1), dim3(kScanThreads), 0, st, w.sizes, b, w.offs, w.state, cap);
+        hipLaunchKernelGGL(k_bgzf_gather, dim3(b), dim3(256), 0, st, w.slots, w.sizes, w.offs, w.state, d_out);
+    }
+    if (flags & FLX_BGZF_EOF) {
+        EofBlock eb;
+        memcpy(eb.b, kEof, 28);
+        hipLaunchKernelGGL(k_bgzf_eof, dim3(1), dim3(64), 0, st, w.state, d_out, cap, eb);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(h_state, w.state, 16, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    return hipStreamSynchronize(st);
+}
+
+uint64_t bound_of(uint64_t n, int flags) {
+    return n + 31 * ((n + BG_MEMBER - 1) / BG_MEMBER) + ((flags & FLX_BGZF_EOF) ? 28 : 0);
+}
+
+}  // namespace
+
+extern "C" int flx_bgzf_bound(uint64_t n, int flags, uint64_t *bound) {
+    if (!bound || (flags & ~FLX_BGZF_EOF)) return FLX_ERR_INVALID;
+    *bound = bound_of(n, flags);
+    return FLX_OK;
+}
+
+extern "C" int flx_bgzf_compress_dev(flx_ctx *ctx, const void *d_in, uint64_t n, int flags, void *d_out, uint64_t out_cap,
+                                     uint64_t *out_len) {
+    if (!ctx) return FLX_ERR_INVALID;
+    if ((!d_in && n) || !out_len || (flags & ~FLX_BGZF_EOF) || (!d_out && out_cap))
+        return flx_fail(ctx, FLX_ERR_INVALID, "flx_bgzf_compress_dev: bad argument");
+    *out_len = 0;
+    void *work = nullptr;
+    FLX_CHECK(flx_scratch(ctx, work_bytes(n), &work));
+    uint64_t st[2] = {0, 0};
+    flx_time_scope ts(ctx, "flx_bgzf");
+    hipError_t e = bgzf_run(ctx->stream, (const uint8_t *)d_in, n, flags, (uint8_t *)d_out, out_cap, work, st);
+    ts.end();
+    if (e != hipSuccess) return flx_fail(ctx, FLX_ERR_HIP, "flx_bgzf_compress_dev: %s", hipGetErrorString(e));
+    if (st[1]) return flx_fail(ctx, FLX_ERR_CAPACITY, "flx_bgzf_compress_dev: %llu bytes needed, capacity %llu",
+                               (unsigned long long)st[0], (unsigned long long)out_cap);
+    *out_len = st[0];
+    return FLX_OK;
+}
+
+// ---- host-to-host compressor with its own streams and pinned slots ---------------------------------------------------
+struct flx_bgzf_slot {
+    hipStream_t stream = nullptr;
+    uint8_t *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
+    void *work = nullptr;
+    uint64_t *h_state = nullptr;
+    bool busy = false;
+};
+
+struct flx_bgzf {
+    flx_ctx *ctx = nullptr;
+    int device = 0;
+    uint64_t slot_bytes = 0;  // a multiple of 65280: chunks of one call keep the member grid of the whole input
+    std::vector<flx_bgzf_slot> slots;
+    std::mutex mu;
+    std::condition_variable cv;
+};
+
+static void free_slot(flx_bgzf_slot &s) {
+    if (s.stream) (void)hipStreamDestroy(s.stream);
+    if (s.d_in) (void)hipFree(s.d_in);
+    if (s.d_out) (void)hipFree(s.d_out);
+    if (s.work) (void)hipFree(s.work);
+    if (s.h_in) (void)hipHostFree(s.h_in);
+    if (s.h_out) (void)hipHostFree(s.h_out);
+    if (s.h_state) (void)hipHostFree(s.h_state);
+    s = flx_bgzf_slot();
+}
+
+extern "C" void flx_bgzf_destroy(flx_bgzf *z) {
+    if (!z) return;
+    (void)hipSetDevice(z->device);
+    for (auto &s : z->slots) {
+        if (s.stream) (void)hipStreamSynchronize(s.stream);
+        free_slot(s);
+    }
+    delete z;
+}
+
+extern "C" int flx_bgzf_create(flx_ctx *ctx, uint64_t slot_bytes, unsigned slots, flx_bgzf **out) {
+    if (!ctx) return FLX_ERR_INVALID;
+    if (!out || slots == 0 || slots > 256) return flx_fail(ctx, FLX_ERR_INVALID, "flx_bgzf_create: bad argument");
+    *out = nullptr;
+    uint64_t sb = slot_bytes / BG_MEMBER * BG_MEMBER;
+    if (sb == 0) sb = BG_MEMBER;
+    flx_bgzf *z = new flx_bgzf();
+    z->ctx = ctx;
+    z->device = ctx->device;
+    z->slot_bytes = sb;
+    z->slots.resize(slots);
+    FLX_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t ob = bound_of(sb, FLX_BGZF_EOF);
+    for (auto &s : z->slots) {
+        hipError_t e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipMalloc(&s.d_in, sb);
+        if (e == hipSuccess) e = hipMalloc(&s.d_out, ob);
+        if (e == hipSuccess) e = hipMalloc(&s.work, work_bytes(sb));
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_in, sb, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_out, ob, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_state, 16, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            flx_bgzf_destroy(z);
+            return flx_fail(ctx, FLX_ERR_NOMEM, "flx_bgzf_create: %s", hipGetErrorString(e));
+        }
+    }
+    *out = z;
+    return FLX_OK;
+}
+
+// Thread-safe: a call takes a free slot (or waits for one) and runs its chunks on that slot's stream.
+extern "C" int flx_bgzf_compress(flx_bgzf *z, const void *in, uint64_t n, int flags, void *out, uint64_t out_cap,
+                                 uint64_t *out_len) {
+    if (!z || (!in && n) || !out_len || (flags & ~FLX_BGZF_EOF) || (!out && out_cap)) return FLX_ERR_INVALID;
+    *out_len = 0;
+    flx_bgzf_slot *s = nullptr;
+    {
+        std::unique_lock<std::mutex> lk(z->mu);
+        for (;;) {
+            for (auto &c : z->slots)
+                if (!c.busy) { s = &c; break; }
+            if (s) break;
+            z->cv.wait(lk);
+        }
+        s->busy = true;
+    }
+    int rc = FLX_OK;
+    hipError_t e = hipSetDevice(z->device);
+    uint64_t done = 0, len = 0;
+    do {
+        const uint64_t c = n - done < z->slot_bytes ? n - done : z->slot_bytes;
+        const int f = (done + c == n) ? flags : 0;
+        if (e == hipSuccess && c) {
+            memcpy(s->h_in, (const uint8_t *)in + done, c);
+            e = hipMemcpyAsync(s->d_in, s->h_in, c, hipMemcpyHostToDevice, s->stream);
+        }
+        const uint64_t cap = bound_of(c, f);
+        if (e == hipSuccess) e = bgzf_run(s->stream, s->d_in, c, f, s->d_out, cap, s->work, s->h_state);
+        if (e != hipSuccess) break;
+        const uint64_t got = s->h_state[0];
+        if (got > out_cap - len) {
+            rc = FLX_ERR_CAPACITY;
+            break;
+        }
+        if ((e = hipMemcpyAsync(s->h_out, s->d_out, got, hipMemcpyDeviceToHost, s->stream)) == hipSuccess)
+            e = hipStreamSynchronize(s->stream);
+        if (e != hipSuccess) break;
+        memcpy((uint8_t *)out + len, s->h_out, got);
+        len += got;
+        done += c;
+    } while (done < n);
+    if (e != hipSuccess) rc = FLX_ERR_HIP;
+    {
+        std::lock_guard<std::mutex> lk(z->mu);
+        s->busy = false;
+    }
+    z->cv.notify_one();
+    if (rc == FLX_OK) *out_len = len;
+    return rc;
+}

@@ -39,7 +39,8 @@ extern "C" {
  * set built from an assembly also keeps the assembly as a text + seed table (0.5 B per base + 10 B per distinct 16-mer of device
  * memory beside the 512 MiB bitmap, 1 GiB pair table and 2 + 2 MiB prefilters); when that memory cannot be had the set works without */
 /* 3 (round 5): + flx_last_kmer_fold_grid */
-/* 4 (round 6): + flx_last_kmer_cover, flx_last_kmer_handed_over, flx_synth_seq_profile_dev */
+/* 4 (round 6): + flx_last_kmer_cover, flx_last_kmer_handed_over, flx_synth_seq_profile_dev; added under version 4: the BGZF
+ * compressor (flx_bgzf_bound, flx_bgzf_compress_dev, flx_bgzf_create / _compress / _destroy) */
 #define FLX_ABI_VERSION 4
 
 enum flx_status {
@@ -316,6 +317,29 @@ int flx_kmerset_add_short_reads(flx_kmerset *set, const uint8_t *bases, const ui
 int flx_kmerset_finalize(flx_kmerset *set);
 uint64_t flx_kmerset_size(const flx_kmerset *set);
 int flx_kmerset_contains(const flx_kmerset *set, const uint32_t *kmers, uint64_t n, uint8_t *present);
+
+/* ------------------------------------------------------------------------------------------
+ * BGZF compression (added under version 4): gzip members of at most 65280 input bytes (member k holds bytes
+ * [k*65280, (k+1)*65280) of the input), each with the BC extra field of the SAM/BAM specification §4.1, each compressed
+ * on its own by one workgroup (one dynamic-Huffman deflate block, or one stored block when that is not larger).
+ * Plain gzip to any gzip reader; FLX_BGZF_EOF appends the 28-byte end-of-file block.  The output is a pure function of
+ * (bytes, flags); an input of 0 bytes gives 0 bytes, or just the end-of-file block.
+ *   flx_bgzf_bound          the most bytes a call can write: n + 31 per member (+ 28)
+ *   flx_bgzf_compress_dev   device to device, on the context's stream (timed as "flx_bgzf"); FLX_ERR_CAPACITY when out_cap
+ *                           is below the compressed size (*out_len 0; what was written is no result)
+ *   flx_bgzf                host to host with its own streams and pinned slots of slot_bytes (rounded down to a multiple
+ *                           of 65280) each: the ONE object of the ABI that may be called from several threads at once;
+ *                           concurrent calls take different slots and overlap their copies and kernels.  A call of more
+ *                           than slot_bytes runs in slot-sized pieces on one slot (the same bytes as one piece).
+ * ---------------------------------------------------------------------------------------- */
+#define FLX_BGZF_EOF 1 /* append the 28-byte BGZF end-of-file block */
+int flx_bgzf_bound(uint64_t n, int flags, uint64_t *bound);
+int flx_bgzf_compress_dev(flx_ctx *ctx, const void *d_in, uint64_t n, int flags, void *d_out, uint64_t out_cap,
+                          uint64_t *out_len);
+typedef struct flx_bgzf flx_bgzf;
+int flx_bgzf_create(flx_ctx *ctx, uint64_t slot_bytes, unsigned slots, flx_bgzf **out);
+int flx_bgzf_compress(flx_bgzf *z, const void *in, uint64_t n, int flags, void *out, uint64_t out_cap, uint64_t *out_len);
+void flx_bgzf_destroy(flx_bgzf *z);
 
 /* ------------------------------------------------------------------------------------------
  * bench / test support: deterministic synthetic Phred planes generated directly in HBM
