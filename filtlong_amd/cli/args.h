@@ -1,9 +1,11 @@
 // args.h — the command line of the drop-in binary: flags, unit suffixes, validation order and messages of the reference
-// (src/arguments.cpp:28-393, src/args.h for the generic readers).  Included by main.cpp only.
+// (src/arguments.cpp:28-393, src/args.h for the generic readers).
 #pragma once
 #include <sys/ioctl.h>
+#include <unistd.h>
 #include <climits>
 #include <cmath>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <limits>

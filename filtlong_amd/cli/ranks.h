@@ -1,15 +1,21 @@
 // ranks.h — one process per GPU under `--gpus N`: the forked ranks, their pipes, the private directory of the output parts, the
-// watchdog that ends the job when a rank dies early.  Included by main.cpp only.
+// watchdog that ends the job when a rank dies early.
 #pragma once
 #include <atomic>
+#include <ctime>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include <fcntl.h>
+#include <poll.h>
 #include <signal.h>
+#include <sys/stat.h>
 #include <sys/wait.h>
 #include <unistd.h>
+
+#include "run.h"
 
 // ---- rank 0 of `--gpus N`: the forked ranks, their pipes, the private directory of the output parts -------------------------
 // A watchdog thread reaps the children while rank 0 works: a child that dies early (no such device, RCCL missing, ...) would
@@ -97,8 +103,9 @@ struct JobGuard {
 };
 
 // Either a launcher set RANK / WORLD_SIZE (/ LOCAL_RANK) + FLX_COMM_ID_FILE, or --gpus N forks N-1 copies of this process here, before
-// any GPU state exists.  Returns -1 to go on (g_rank / g_world / g_job are set), or the process's exit code.
-static int start_ranks(const Args &args, std::string &id_file, int &id_pipe) {
+// any GPU state exists.  Returns kGoOn (run.rank / run.world / run.part_prefix / g_job are set), or the process's exit code.
+static int start_ranks(Run &run, std::string &id_file, int &id_pipe) {
+    const Args &args = run.args;
     // ---- ranks: one process per GPU (north_star / SURVEY §8e) ---------------------------------------------------
     // Either a launcher set RANK / WORLD_SIZE (/ LOCAL_RANK), or --gpus N forks N-1 copies of this process here, before
     // any GPU state exists.  Reads are sharded by count in contiguous blocks of file order; every rank parses the (mapped)
@@ -107,10 +114,10 @@ static int start_ranks(const Args &args, std::string &id_file, int &id_pipe) {
     // Launcher mode is an explicit opt-in — RANK + WORLD_SIZE + FLX_COMM_ID_FILE (a path unique to the job) all set: a bare
     // WORLD_SIZE inherited from a SLURM / torchrun shell must not turn a plain run into a rank that waits for peers.
     if (getenv("WORLD_SIZE") && getenv("RANK") && getenv("FLX_COMM_ID_FILE")) {
-        g_world = std::max(1, atoi(getenv("WORLD_SIZE")));
-        g_rank = atoi(getenv("RANK"));
+        run.world = std::max(1, atoi(getenv("WORLD_SIZE")));
+        run.rank = atoi(getenv("RANK"));
         id_file = getenv("FLX_COMM_ID_FILE");
-        g_part_prefix = id_file + ".out";
+        run.part_prefix = id_file + ".out";
     } else if (args.gpus > 1) {
         if (!getenv("FLX_DEVICE")) {  // (FLX_DEVICE pins every rank to one device: the one-GPU tests of this path)
             // the HIP runtime does not survive a fork, so the device count comes from a probe child
@@ -123,22 +130,22 @@ static int start_ranks(const Args &args, std::string &id_file, int &id_pipe) {
                 return 1;
             }
         }
-        g_world = args.gpus;
+        run.world = args.gpus;
         // a private directory for the ranks' output parts (mkdtemp: mode 0700, unpredictable name)
         const char *td = getenv("TMPDIR");
         std::string tmpl = std::string(td && *td ? td : "/tmp") + "/flx_XXXXXX";
         if (!mkdtemp(&tmpl[0])) { std::cerr << "Error: cannot create a temporary directory under " << (td && *td ? td : "/tmp") << "\n"; return 1; }
         g_job.dir = tmpl;
-        g_part_prefix = tmpl + "/out";
+        run.part_prefix = tmpl + "/out";
         // the communicator id reaches every rank through a pipe made before the fork
         std::vector<int> wr;
-        for (int r = 1; r < g_world; ++r) {
+        for (int r = 1; r < run.world; ++r) {
             int fds[2];
             if (pipe(fds) != 0) { std::cerr << "Error: pipe failed\n"; return 1; }
             const pid_t pid = fork();
             if (pid < 0) { std::cerr << "Error: fork failed\n"; return 1; }
             if (pid == 0) {
-                g_rank = r;
+                run.rank = r;
                 g_job = Job();  // a child owns neither children nor the directory
                 for (int w : wr) close(w);
                 close(fds[1]);
@@ -149,24 +156,25 @@ static int start_ranks(const Args &args, std::string &id_file, int &id_pipe) {
             wr.push_back(fds[1]);
             g_job.children.push_back(pid);
         }
-        if (g_rank == 0) {
+        if (run.rank == 0) {
             g_job.id_pipes = wr;
             g_job.start_watchdog();
         }
     }
-    return -1;
+    return kGoOn;
 }
 
 // The communicator's 128-byte id reaches every rank (pipes made before the fork, or FLX_COMM_ID_FILE under a launcher), then the
-// library's communicator is initialised.  Returns -1 to go on, or the process's exit code.
-static int exchange_communicator_id(flx_ctx *ctx, const std::string &id_file, int id_pipe) {
+// library's communicator is initialised.  Returns kGoOn, or the process's exit code.
+static int exchange_communicator_id(Run &run, const std::string &id_file, int id_pipe) {
+    flx_ctx *ctx = run.ctx;
     {
         // the communicator's 128-byte id: --gpus hands it to every child through its pipe; under a launcher it travels through
         // FLX_COMM_ID_FILE (rank 0: exclusive create of a temp name, never through a symlink, then rename; the others accept
         // only a file written after they started — a stale one from a crashed earlier job is older)
         unsigned char id[FLX_COMM_ID_BYTES];
-        if (g_rank == 0) {
-            if (flx_comm_unique_id(ctx, id) != FLX_OK) return fail_flx(ctx, "communicator");
+        if (run.rank == 0) {
+            if (flx_comm_unique_id(ctx, id) != FLX_OK) return run.fail("communicator");
             if (!g_job.children.empty()) {
                 for (int w : g_job.id_pipes) {
                     if (write(w, id, sizeof id) != (ssize_t)sizeof id) { std::cerr << "Error: cannot hand the communicator id to a rank\n"; return 1; }
@@ -205,11 +213,11 @@ static int exchange_communicator_id(flx_ctx *ctx, const std::string &id_file, in
             }
             if (!ok) return 1;
         }
-        if (flx_comm_init(ctx, id, g_rank, g_world) != FLX_OK) return fail_flx(ctx, "communicator");
+        if (flx_comm_init(ctx, id, run.rank, run.world) != FLX_OK) return run.fail("communicator");
         uint64_t ready = 1;  // everybody has read the id
-        if (flx_comm_sum_u64(ctx, &ready, 1) != FLX_OK) return fail_flx(ctx, "communicator");
-        if (g_rank == 0 && !id_file.empty()) unlink(id_file.c_str());
+        if (flx_comm_sum_u64(ctx, &ready, 1) != FLX_OK) return run.fail("communicator");
+        if (run.rank == 0 && !id_file.empty()) unlink(id_file.c_str());
     }
 
-    return -1;
+    return kGoOn;
 }

@@ -1,5 +1,4 @@
 // reference.h — the reference files of -a / -1 / -2 as a STREAM into the device-side 16-mer set (src/kmers.cpp:75-134).
-// Included by main.cpp only.
 //
 // The reference reads a record at a time through kseq and hashes it on the spot: constant memory, and a progress line
 // "\r  file (N bp)" whenever 483 611 more bases have been hashed (src/kmers.cpp:123-126), once more at the end, then "\n".
@@ -10,8 +9,8 @@
 // size of the file (round 4 held three copies of every sequence).  The progress lines are printed record by record with the
 // reference's rule, so stderr is the reference's byte for byte.  Pipes and empty files keep the in-memory reader (fastx.h: Input).
 #pragma once
-#include "fastx.h"
-#include "gzblocks.h"
+#include "format.h"
+#include "run.h"
 
 static void print_hash_progress(const std::string &filename, long long base_count) {  // src/kmers.cpp (print_hash_progress)
     std::cerr << "\r  " << filename << " (" << int_to_string(base_count) << " bp)";
@@ -75,4 +74,41 @@ static int hash_reference(const std::string &filename, flx_kmerset *const *sets,
     print_hash_progress(filename, bases);
     std::cerr << "\n";
     return n;
+}
+
+// ---- reference 16-mers (src/main.cpp:51-59, src/kmers.cpp:50-72) --------------------------------------
+static int build_reference_set(Run &run) {
+    const Args &args = run.args;
+    if (!args.assembly_set && args.short_reads.empty()) return kGoOn;
+    if (flx_kmerset_create(run.ctx, &run.kmers) != FLX_OK) return run.fail("k-mer set");
+    if (args.assembly_set) {
+        std::cerr << "Hashing 16-mers from assembly\n";
+        std::cerr << "  " << args.assembly << "\n";
+        // the reference prints the set's size after the assembly alone (src/kmers.cpp:60-72); with short reads to follow that
+        // takes a second set, which is fed the same batches and dropped once it has been counted
+        flx_kmerset *alone = nullptr;
+        if (!args.short_reads.empty() && flx_kmerset_create(run.ctx, &alone) != FLX_OK) return run.fail("k-mer set");
+        flx_kmerset *both[2] = {run.kmers, alone};
+        bool ok = true;
+        const int count = hash_reference(args.assembly, both, alone ? 2 : 1, false, ok);
+        if (!ok) return run.fail("assembly");
+        flx_kmerset *counted = alone ? alone : run.kmers;
+        if (flx_kmerset_finalize(counted) != FLX_OK) return run.fail(alone ? "assembly" : "k-mer set");
+        std::cerr << "  " << int_to_string(count) << " " << (count == 1 ? "contig" : "contigs") << ", "
+                  << int_to_string((long long)flx_kmerset_size(counted)) << " 16-mers\n\n";
+        if (alone) flx_kmerset_destroy(alone);
+    }
+    if (!args.short_reads.empty()) {
+        std::cerr << "Hashing 16-mers from short reads\n";
+        int count = 0;
+        for (auto &f : args.short_reads) {
+            bool ok = true;
+            count += hash_reference(f, &run.kmers, 1, true, ok);
+            if (!ok) return run.fail("short reads");
+        }
+        if (flx_kmerset_finalize(run.kmers) != FLX_OK) return run.fail("k-mer set");
+        std::cerr << "  " << int_to_string(count) << " reads, " << int_to_string((long long)flx_kmerset_size(run.kmers)) << " 16-mers\n\n";
+    }
+    run.kmers_empty = flx_kmerset_size(run.kmers) == 0;
+    return kGoOn;
 }
