@@ -133,6 +133,7 @@ extern "C" void flx_ctx_destroy(flx_ctx *ctx) {
     if (ctx->d_lut_q) (void)hipFree(ctx->d_lut_q);
     if (ctx->d_lut_d) (void)hipFree(ctx->d_lut_d);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
+    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     for (void *w : ctx->ws)
         if (w) (void)hipFree(w);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -253,6 +254,20 @@ int flx_scratch(flx_ctx *ctx, size_t bytes, void **out) {
         ctx->scratch_bytes = want;
     }
     *out = ctx->scratch;
+    return FLX_OK;
+}
+
+int flx_pinned(flx_ctx *ctx, size_t bytes, void **out) {
+    if (bytes > ctx->pinned_bytes) {
+        FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+        ctx->pinned = nullptr;
+        ctx->pinned_bytes = 0;
+        hipError_t e = hipHostMalloc(&ctx->pinned, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) return flx_fail(ctx, FLX_ERR_NOMEM, "pinned host buffer of %zu bytes: %s", bytes, hipGetErrorString(e));
+        ctx->pinned_bytes = bytes;
+    }
+    *out = ctx->pinned;
     return FLX_OK;
 }
 

@@ -31,6 +31,7 @@ struct flx_ctx {
     uint64_t last_kmer_redo_n = 0;            // ... and how many there are
     const char *last_kmer_cover = "";    // which coverage kernel the last k-mer scoring call ran: "q" (cover_queue.hip), "w", "v2"
     bool last_kmer_locus = false;        // the last k-mer scoring call ran with the assembly text (kmerset.h: flx_locus)
+    void *phred_pending = nullptr;       // score_phred_regs.hip: what flx_phred_finish has to look at after the call's synchronisation
     const char *last_phred_kernel = "";  // which Phred kernel the last scoring call launched (flx_last_phred_kernel)
 
     // Phred LUTs: lut_q[c] = 1 - 10^(-(c-33)/10) for the signed-char value of byte c, built on the
@@ -52,6 +53,10 @@ struct flx_ctx {
     // reusable device scratch (grown on demand)
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
+    // reusable pinned host buffer (grown on demand): small results come back into it and small uploads leave from it without
+    // a pageable-memory staging copy, and it outlives the asynchronous copy that uses it
+    void *pinned = nullptr;
+    size_t pinned_bytes = 0;
     // grow-only workspaces of the k-mer scoring path (kept between calls: a 12 GB hipMalloc + hipFree per batch costs
     // more than the fold kernels)
     void *ws[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -93,6 +98,8 @@ struct flx_time_scope {
 
 // grow-only scratch on the device
 int flx_scratch(flx_ctx *ctx, size_t bytes, void **out);
+// grow-only pinned host buffer; valid until the next call that asks for more
+int flx_pinned(flx_ctx *ctx, size_t bytes, void **out);
 // grow-only workspace `slot` (0: per-read arrays of the k-mer path, 1: its coverage bit plane, 2: its child arrays, 3: the Phred
 // path of long reads); valid until the next call
 // with the same slot
@@ -121,6 +128,9 @@ struct flx_score_out_dev {  // device pointers
 };
 
 int flx_ensure_lut_d(flx_ctx *ctx, int window_size);
+// After the synchronisation that ends a Phred scoring call: names the table variant the device chose, and scores the batch's long
+// reads (then synchronises once more) if the detection found any.  A no-op when nothing is pending.
+int flx_phred_finish(flx_ctx *ctx);
 
 int flx_launch_score_phred(flx_ctx *ctx, const uint8_t *d_plane, uint64_t plane_bytes, const uint64_t *d_offsets,
                            const int32_t *d_lengths, const uint32_t *d_order, uint64_t n_reads,

@@ -90,11 +90,9 @@ struct DevPow {
     }
 };
 
-__global__ void k_final_score(uint64_t n, const double *mean_q, const double *window_q, const int32_t *length,
-                              NormArgs s, double *final_score, uint64_t *keys, uint32_t *vals,
-                              unsigned int *any_nan) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+__device__ __forceinline__ void final_score_store(uint64_t i, const double *mean_q, const double *window_q, const int32_t *length,
+                                                  const NormArgs &s, double *final_score, uint64_t *keys, uint32_t *vals,
+                                                  unsigned int *any_nan) {
     const double f = final_score_with(DevPow(), length[i], mean_q[i], window_q[i], s);
     if (any_nan && f != f) atomicOr(any_nan, 1u);
     if (final_score) final_score[i] = f;
@@ -102,6 +100,14 @@ __global__ void k_final_score(uint64_t n, const double *mean_q, const double *wi
         keys[i] = ~key_ascending(f);  // descending score == ascending key
         if (vals) vals[i] = (uint32_t)i;
     }
+}
+
+__global__ void k_final_score(uint64_t n, const double *mean_q, const double *window_q, const int32_t *length,
+                              NormArgs s, double *final_score, uint64_t *keys, uint32_t *vals,
+                              unsigned int *any_nan) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    final_score_store(i, mean_q, window_q, length, s, final_score, keys, vals, any_nan);
 }
 
 // one atomic per workgroup (256 threads): thousands of same-address atomics cost more than the pass over the data
@@ -301,6 +307,203 @@ __global__ void __launch_bounds__(256) k_select_mark(uint64_t n, const uint64_t 
     if (i < n && keys[i] >= k_lo) passed[i] = 0;
 }
 
+// passed[idx[i]] = 1
+__global__ void __launch_bounds__(256) k_set_flags(unsigned int m, const uint32_t *idx, uint8_t *passed) {
+    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < m) passed[idx[i]] = 1;
+}
+
+// ---- SELECT path with the decisions on the device -----------------------------------------------------------------
+// Everything the host used to fetch between the kernels of the stage — the statistics, the normalisation arguments, the
+// passed bases, the selection's state, the band's bounds and size — lives in one record on the device.  The kernels read it
+// and write it, and the host sees it once, together with the band's records, when it has to re-score the band with its libm.
+constexpr unsigned kBandCap = 1u << 16;   // band members the select path audits (beyond: the sort path)
+constexpr unsigned kBandInline = 1024;    // ... of which this many come back with the record itself
+struct RankDev {
+    flx_stats_dev stats;
+    NormArgs s;
+    SelState st[9];  // st[q]: q key bytes decided
+    unsigned long long passed_bases;  // = the total of the first histogram
+    unsigned long long k_lo, k_hi;    // the band's keys
+    unsigned long long weight_before;
+    unsigned int band_n;
+    unsigned int need_sort;  // target < passed_bases: there is a cut to find
+};
+static_assert(sizeof(RankDev) <= 1024, "the band's records follow at byte 1024");
+
+__device__ __host__ inline void norm_args(const flx_stats_dev &st, double lw, double mw, double ww, NormArgs &s, double *max_z) {
+    s.qmean = st.mean;
+    s.qstd = st.stdev;
+    if (st.stdev > 0.0) {  // main.cpp:188-195
+        s.zmin = (st.min - st.mean) / st.stdev;
+        const double zmax = (st.max - st.mean) / st.stdev;
+        s.zspan = zmax - s.zmin;
+        *max_z = zmax;
+    } else {
+        s.zmin = 1.0;
+        s.zspan = 1.0 - 1.0;
+        *max_z = 1.0;
+    }
+    s.lw = lw; s.mw = mw; s.ww = ww;
+}
+
+__device__ __host__ inline double key_to_score(uint64_t k) {
+    uint64_t a = ~k;  // ascending key
+    uint64_t b = (a >> 63) ? (a & 0x7fffffffffffffffull) : ~a;
+    double v;
+    memcpy(&v, &b, 8);
+    return v;
+}
+
+// band around the crossing score: everything the reference might order differently (descending keys: lo = best score)
+__device__ __host__ inline void band_keys(uint64_t key_star, uint64_t *k_lo, uint64_t *k_hi) {
+    const double kBand = 1e-11;  // relative; the device pow is good to a few ulp (1e-16), so this is generous
+    const double sp = key_to_score(key_star);
+    const double band = fabs(sp) * kBand + 1e-300;
+    *k_lo = ~key_ascending(sp + band);
+    *k_hi = ~key_ascending(sp - band);
+}
+
+__global__ void k_rank_prepare(RankDev *h, double lw, double mw, double ww, long long target) {
+    double max_z;
+    norm_args(h->stats, lw, mw, ww, h->s, &max_z);
+    SelState init = {0ull, target, 0u, 0u};
+    h->st[0] = init;
+}
+
+__global__ void k_final_score_dev(uint64_t n, const double *mean_q, const double *window_q, const int32_t *length,
+                                  const RankDev *h, double *final_score, uint64_t *keys, unsigned int *any_nan) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const NormArgs s = h->s;
+    final_score_store(i, mean_q, window_q, length, s, final_score, keys, (uint32_t *)nullptr, any_nan);
+}
+
+// k_select_decide by a whole workgroup of 256 threads: st[pass + 1] from st[pass] and the complete histogram of pass `pass`.
+// Every workgroup of the NEXT kernel computes it for itself (2 KiB from the L2 and one scan) instead of waiting for a
+// one-workgroup launch in between; workgroup 0 also stores it.  The bins are >= 0, so the running sum does not decrease and
+// "the first bin at which it reaches `remaining`" is the one bin whose exclusive sum is below and inclusive sum is not.
+__device__ SelState select_decide(const unsigned long long *bins, const SelState in, int pass, long long *total) {
+    __shared__ long long wsum[4], s_cum;
+    __shared__ int s_d;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const long long v = (long long)bins[t];
+    long long inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+    }
+    if (lane == 63) wsum[w] = inc;
+    if (t == 0) s_d = 256;
+    __syncthreads();
+    for (int k = 0; k < w; ++k) inc += wsum[k];
+    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const long long remaining = in.remaining;
+    if (inc >= remaining && (t == 0 || inc - v < remaining)) {
+        s_d = t;
+        s_cum = inc - v;
+    }
+    __syncthreads();
+    SelState out = in;
+    int d = s_d;
+    long long cum = s_cum;
+    if (d == 256) {
+        out.fail = 1;
+        d = 255;
+        cum = *total;
+    }
+    if (pass == 0 && bins[256]) out.nan = 1;
+    out.remaining = remaining - cum;
+    out.prefix = (in.prefix << 8) | (unsigned long long)d;
+    __syncthreads();  // (the caller reuses shared memory)
+    return out;
+}
+
+// k_select_hist with the previous pass's decision in front
+__global__ void __launch_bounds__(256) k_select_hist_dev(uint64_t n, const uint64_t *keys, const int32_t *length,
+                                                         const uint8_t *passed, RankDev *hd, int pass,
+                                                         unsigned long long *bins_all) {
+    __shared__ unsigned long long h[256];
+    SelState st = hd->st[0];
+    if (pass > 0) {
+        long long total;
+        st = select_decide(bins_all + 264 * (pass - 1), hd->st[pass - 1], pass - 1, &total);
+        // the first histogram holds every passed base: target >= passed bases means there is nothing to cut (main.cpp:238-246).
+        // (Lengths are >= 0 by contract — flx_score_batch refuses negative ones —, so leaving out len <= 0 changes no sum.)
+        const bool need = pass == 1 ? hd->st[0].remaining < total : hd->need_sort != 0;
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            hd->st[pass] = st;
+            if (pass == 1) {
+                hd->passed_bases = (unsigned long long)total;
+                hd->need_sort = need ? 1u : 0u;
+            }
+        }
+        if (!need) return;
+    }
+    unsigned long long *bins = bins_all + 264 * pass;
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t prefix = st.prefix;
+    const int shift = 56 - 8 * pass;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t k = keys[i];
+        const bool match = pass == 0 || (k >> (shift + 8)) == prefix;
+        if (match && passed[i]) {
+            const int len = length[i];
+            if (len > 0) atomicAdd(&h[(k >> shift) & 0xff], (unsigned long long)len);
+        }
+    }
+    __syncthreads();
+    if (h[threadIdx.x]) atomicAdd(&bins[threadIdx.x], h[threadIdx.x]);
+}
+
+// the last decision, the band's bounds from it, then k_select_band
+__global__ void __launch_bounds__(256) k_select_band_dev(uint64_t n, const uint64_t *keys, const int32_t *length,
+                                                         const uint8_t *passed, RankDev *hd, const unsigned long long *bins_all,
+                                                         uint32_t *band_idx, unsigned int cap) {
+    long long total;
+    const SelState st = select_decide(bins_all + 264 * 7, hd->st[7], 7, &total);
+    uint64_t k_lo, k_hi;
+    band_keys(st.prefix, &k_lo, &k_hi);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        hd->st[8] = st;
+        hd->k_lo = k_lo;
+        hd->k_hi = k_hi;
+    }
+    if (!hd->need_sort || st.nan || st.fail) return;  // the host takes another path
+    unsigned long long acc = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t k = keys[i];
+        if (k < k_lo) {
+            if (passed[i]) acc += (unsigned long long)length[i];
+        } else if (k <= k_hi) {
+            const unsigned int at = atomicAdd(&hd->band_n, 1u);
+            if (at < cap) band_idx[at] = (uint32_t)i;
+        }
+    }
+    block_add(acc, &hd->weight_before);
+}
+
+// k_band_gather for as many members as the band turned out to have (none when it exceeds the capacity)
+__global__ void __launch_bounds__(256) k_band_gather_dev(const RankDev *hd, unsigned int cap, const uint32_t *band_idx,
+                                                         const uint64_t *keys, const double *mean, const double *window,
+                                                         const int32_t *length, const uint8_t *passed, BandRec *out) {
+    const unsigned int m = hd->band_n;
+    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+    if (m > cap || i >= m) return;
+    const uint32_t r = band_idx[i];
+    BandRec b;
+    b.key = keys[r];
+    b.mean = mean[r];
+    b.window = window[r];
+    b.idx = r;
+    b.len = length[r];
+    b.was_passed = passed[r];
+    b.pad = 0;
+    out[i] = b;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -426,14 +629,6 @@ struct Shard {
     }
 };
 
-static double key_to_score(uint64_t k) {
-    uint64_t a = ~k;  // ascending key
-    uint64_t b = (a >> 63) ? (a & 0x7fffffffffffffffull) : ~a;
-    double v;
-    memcpy(&v, &b, 8);
-    return v;
-}
-
 using TimeScope = flx_time_scope;  // (flx_internal.h)
 
 // ---- the boundary audit, shared by both cut implementations ---------------------------------------------------------
@@ -492,7 +687,7 @@ static int cut_by_select(flx_ctx *ctx, uint64_t n, const double *mean, const dou
                          const Shard &sh = Shard()) {
     hipStream_t st = ctx->stream;
     const unsigned nb = (unsigned)((n + 255) / 256);
-    const unsigned cap = 1u << 16;
+    const unsigned cap = kBandCap;
     const size_t bins_bytes = 8 * 264 * 8;  // 8 passes x (256 bins + flag slot + padding)
     const size_t bytes = n * 8 + bins_bytes + 256 + (size_t)cap * (4 + sizeof(BandRec) + 4 + 1) + 1024;
     void *scr;
@@ -541,12 +736,10 @@ static int cut_by_select(flx_ctx *ctx, uint64_t n, const double *mean, const dou
     if (h_state.fail)  // cannot happen when 0 < target < passed_bases
         return flx_fail(ctx, FLX_ERR_STATE, "radix select ran out of weight (target %lld)", (long long)target);
     const uint64_t key_star = h_state.prefix;  // key of the read at which the walk reaches the target
-    const double sp = key_to_score(key_star);
 
     // ---- band around the crossing score: everything the reference might order differently -------------------
-    const double kBand = 1e-11;  // relative; the device pow is good to a few ulp (1e-16), so this is generous
-    const double band = std::fabs(sp) * kBand + 1e-300;
-    const uint64_t k_lo = ~key_ascending(sp + band), k_hi = ~key_ascending(sp - band);  // descending keys: lo = best score
+    uint64_t k_lo, k_hi;
+    band_keys(key_star, &k_lo, &k_hi);
     hipLaunchKernelGGL(k_select_band, dim3(grid), dim3(256), 0, st, n, keys, length, passed, k_lo, k_hi, band_idx,
                        (unsigned int *)d_acc, cap, d_acc + 1);
     unsigned long long h_acc[2] = {0, 0};
@@ -640,6 +833,143 @@ static int cut_by_select(flx_ctx *ctx, uint64_t n, const double *mean, const dou
             hipLaunchKernelGGL(k_scatter_flags, dim3((m + 255) / 256), dim3(256), 0, st, m, d_set_idx, d_set_val, passed);
             FLX_HIP(ctx, hipStreamSynchronize(st));  // the host vectors go out of scope
         }
+    }
+    FLX_HIP(ctx, hipStreamSynchronize(st));
+    rep->kept_bases = so_far;  // "keeping N bp", main.cpp:258
+    rep->audited = band_n;
+    FLX_HIP(ctx, hipGetLastError());
+    return FLX_OK;
+}
+
+// =================================================================================================
+// SELECT path, decisions on the device (one rank, a cut is asked for): statistics, normalisation, final scores, the eight
+// selection passes, the band and its records are enqueued back to back; the host waits ONCE, for the record and the band, checks
+// what the device derived against its own arithmetic, audits the band with its libm, and enqueues the mark.
+// FLX_RANK_REDO_HOST: the device's derived values are not the host's (never seen) — nothing has touched the pass flags yet and the
+// caller goes through the host-driven sequence below.
+// =================================================================================================
+static const int FLX_RANK_REDO_HOST = -1001;
+
+static int rank_and_cut_device(flx_ctx *ctx, uint64_t n, const double *mean, const double *window, const int32_t *length,
+                               uint8_t *passed, double lw, double mw, double ww, int64_t target, void *d_final_score,
+                               flx_cut_report *rep, NormArgs *s_out) {
+    hipStream_t st = ctx->stream;
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    const unsigned cap = kBandCap;
+    const size_t bins_bytes = 8 * 264 * 8;  // 8 passes x (256 bins + flag slot + padding)
+    const size_t recs_bytes = (size_t)cap * sizeof(BandRec);
+    // device: record (1 KiB) | band records | bins | band / set indices | keys, with the statistics' workspace in the keys' place
+    const size_t body = std::max<size_t>(n * 8, flx_exact_stats_workspace(n));
+    void *scr;
+    FLX_CHECK(flx_scratch(ctx, 1024 + recs_bytes + bins_bytes + (size_t)cap * 8 + body + 256, &scr));
+    char *p = (char *)scr;
+    RankDev *hd = (RankDev *)p; p += 1024;
+    BandRec *d_recs = (BandRec *)p; p += recs_bytes;
+    unsigned long long *bins = (unsigned long long *)p; p += bins_bytes;  // pass q at bins + 264 q
+    uint32_t *band_idx = (uint32_t *)p; p += (size_t)cap * 4;
+    uint32_t *d_set_idx = (uint32_t *)p; p += (size_t)cap * 4;
+    uint64_t *keys = (uint64_t *)p;
+    // host (pinned): what comes back | the indices that go up
+    const size_t back_bytes = 1024 + (size_t)kBandInline * sizeof(BandRec);
+    void *pin;
+    FLX_CHECK(flx_pinned(ctx, back_bytes + (size_t)cap * 4, &pin));
+    const RankDev *h = (const RankDev *)pin;
+    const BandRec *h_recs = (const BandRec *)((char *)pin + 1024);
+    uint32_t *h_set_idx = (uint32_t *)((char *)pin + back_bytes);
+
+    FLX_HIP(ctx, hipMemsetAsync(hd, 0, 1024, st));
+    FLX_HIP(ctx, hipMemsetAsync(bins, 0, bins_bytes, st));
+    FLX_CHECK(flx_exact_stats_async(ctx, n, mean, keys, &hd->stats));
+    hipLaunchKernelGGL(k_rank_prepare, dim3(1), dim3(1), 0, st, hd, lw, mw, ww, (long long)target);
+    {
+        TimeScope t(ctx, "flx_rank_final_score");  // the NaN flag is OR-ed into the flag slot of the first histogram
+        hipLaunchKernelGGL(k_final_score_dev, dim3(nb), dim3(256), 0, st, n, mean, window, length, hd, (double *)d_final_score, keys,
+                           (unsigned int *)(bins + 256));
+    }
+    TimeScope tsel(ctx, "flx_rank_select");
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 2048));
+    for (int pass = 0; pass < 8; ++pass)
+        hipLaunchKernelGGL(k_select_hist_dev, dim3(grid), dim3(256), 0, st, n, keys, length, passed, hd, pass, bins);
+    hipLaunchKernelGGL(k_select_band_dev, dim3(grid), dim3(256), 0, st, n, keys, length, passed, hd, bins, band_idx, cap);
+    hipLaunchKernelGGL(k_band_gather_dev, dim3(kBandInline / 256), dim3(256), 0, st, hd, kBandInline, band_idx, keys, mean, window,
+                       length, passed, d_recs);
+    FLX_HIP(ctx, hipMemcpyAsync(pin, hd, back_bytes, hipMemcpyDeviceToHost, st));
+    FLX_HIP(ctx, hipStreamSynchronize(st));
+    FLX_HIP(ctx, hipGetLastError());
+
+    // ---- the host's own arithmetic on the folds' sums; everything the device derived must agree with it ---------------
+    flx_stats stats;
+    bool same = flx_stats_finish(h->stats, n, &stats);
+    flx_stats_dev hs = h->stats;
+    hs.mean = stats.mean;
+    hs.stdev = stats.stdev;
+    NormArgs s;
+    {
+        volatile double a = lw, b = mw, c = ww;  // (no constant folding across the call: the same divisions as ever)
+        norm_args(hs, a, b, c, s, &rep->max_z);
+    }
+    same = same && memcmp(&s, &h->s, sizeof s) == 0;
+    const SelState fin = h->st[8];
+    uint64_t k_lo, k_hi;
+    band_keys(fin.prefix, &k_lo, &k_hi);
+    if (!same || (h->need_sort && !fin.nan && !fin.fail && (k_lo != h->k_lo || k_hi != h->k_hi))) return FLX_RANK_REDO_HOST;
+    *s_out = s;
+    rep->mean_quality = stats.mean;
+    rep->stdev_quality = stats.stdev;
+    rep->min_z = s.zmin;
+    rep->target_bases = target;
+    if (!h->need_sort) {  // target >= passed bases: the final scores are written, the flags stay
+        rep->outcome = FLX_CUT_ALREADY_BELOW;
+        return FLX_OK;
+    }
+    rep->outcome = FLX_CUT_SORTED;
+    if (fin.nan) {
+        // NaN scores (stdev == 0 -> 0/0, main.cpp:192-206, or 0/0 window ratios): the reference's comparator is
+        // inconsistent and its outcome is whatever libstdc++'s introsort does on reads2 order -> host path.
+        tsel.end();
+        return exact_host_cut(ctx, n, mean, window, length, passed, nullptr, nullptr, s, target, rep);
+    }
+    if (fin.fail)  // cannot happen when 0 < target < passed_bases
+        return flx_fail(ctx, FLX_ERR_STATE, "radix select ran out of weight (target %lld)", (long long)target);
+    const unsigned band_n = h->band_n;
+    if (band_n > cap) {  // huge tie group (e.g. millions of duplicate reads): let the sort path handle it
+        tsel.end();
+        return FLX_SELECT_BAND_TOO_LARGE;
+    }
+    std::vector<BandRec> recs(h_recs, h_recs + std::min(band_n, kBandInline));
+    if (band_n > kBandInline) {  // a band beyond what came back with the record: all of it, in a second round trip (rare: a plain
+                                 // pageable copy followed by a wait, rather than 2.6 MB of pinned memory held for it)
+        recs.resize(band_n);
+        hipLaunchKernelGGL(k_band_gather_dev, dim3((band_n + 255) / 256), dim3(256), 0, st, hd, cap, band_idx, keys, mean, window, length,
+                           passed, d_recs);
+        FLX_HIP(ctx, hipMemcpyAsync(recs.data(), d_recs, (size_t)band_n * sizeof(BandRec), hipMemcpyDeviceToHost, st));
+        FLX_HIP(ctx, hipStreamSynchronize(st));
+    }
+    std::sort(recs.begin(), recs.end(), [](const BandRec &x, const BandRec &y) { return x.idx < y.idx; });
+    std::vector<Cand> cand(band_n);
+    for (unsigned i = 0; i < band_n; ++i) {
+        const BandRec &b = recs[i];
+        Cand &c = cand[i];
+        c.idx = b.idx;
+        c.key = b.key;
+        c.score = host_final_score(b.len, b.mean, b.window, s);
+        c.len = b.len;
+        c.was_passed = (uint8_t)b.was_passed;
+    }
+    std::vector<uint8_t> keep;
+    long long so_far = 0;
+    const bool order_dependent = audit_walk(cand, (long long)h->weight_before, target, keep, &so_far);
+    tsel.end();
+    if (order_dependent) return exact_host_cut(ctx, n, mean, window, length, passed, nullptr, nullptr, s, target, rep);
+
+    // ---- mark: better than the band -> unchanged; band and worse -> fail; kept band members -> back on ----------
+    hipLaunchKernelGGL(k_select_mark, dim3(nb), dim3(256), 0, st, n, keys, k_lo, passed);
+    unsigned m = 0;
+    for (unsigned i = 0; i < band_n; ++i)
+        if (keep[i]) h_set_idx[m++] = (uint32_t)cand[i].idx;
+    if (m) {  // one upload from the context's pinned buffer (it outlives the copy), one kernel
+        FLX_HIP(ctx, hipMemcpyAsync(d_set_idx, h_set_idx, (size_t)m * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_set_flags, dim3((m + 255) / 256), dim3(256), 0, st, m, d_set_idx, passed);
     }
     FLX_HIP(ctx, hipStreamSynchronize(st));
     rep->kept_bases = so_far;  // "keeping N bp", main.cpp:258
@@ -824,6 +1154,19 @@ static int rank_and_cut_impl(flx_ctx *ctx, uint64_t n_total, const double *mean_
     const double *mean = mean_all + sh.first;
     hipStream_t st = ctx->stream;
     const bool cutting = target_bases_set || keep_percent_set;
+
+    // ---- one rank, a cut that the total does not rule out: the whole stage with a single wait in the middle ----------------
+    if (cutting && n_total && !sh.sharded()) {
+        const int64_t t = compute_target(target_bases_set, target_bases, keep_percent_set, keep_percent, total_bases);
+        const char *x = getenv("FLX_RANK_EXACT"), *e = getenv("FLX_RANK_SORT");  // (test hooks: host-driven sequence below)
+        if (t < total_bases && !(x && x[0] == '1') && !(e && e[0] == '1')) {
+            NormArgs sd;
+            int rc = rank_and_cut_device(ctx, n, mean, window, length, passed, lw, mw, ww, t, d_final_score, rep, &sd);
+            if (rc == FLX_SELECT_BAND_TOO_LARGE) rc = cut_by_sort(ctx, n, mean, window, length, passed, sd, t, d_final_score, rep);
+            if (rc != FLX_RANK_REDO_HOST) return rc;
+            memset(rep, 0, sizeof *rep);
+        }
+    }
 
     // ---- a20: statistics (exact serial folds) -------------------------------------------------
     flx_stats stats;

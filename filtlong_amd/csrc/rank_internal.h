@@ -9,6 +9,17 @@ struct flx_stats {
     unsigned long long serial_chunks;  // diagnostic: 512-element chunks folded serially (binade crossings etc.)
 };
 int flx_exact_stats(flx_ctx *ctx, uint64_t n, const double *d_mean_q, flx_stats *out);
+// The same without the host: both folds run back to back on ctx->stream (the second reads the mean the first left on the
+// device) and leave their results in *d_out; ws = flx_exact_stats_workspace(n) bytes of device memory, n > 0.
+struct flx_stats_dev {
+    double sum, min, max, mean, sq_sum, stdev;
+    unsigned long long serial_chunks[2];
+};
+size_t flx_exact_stats_workspace(uint64_t n);
+int flx_exact_stats_async(flx_ctx *ctx, uint64_t n, const double *d_mean_q, void *ws, flx_stats_dev *d_out);
+// host side, once *d_out has been copied back: mean and stdev recomputed with the host's own division and square root;
+// false when the device had derived other bits (then nothing computed from them on the device may be used)
+bool flx_stats_finish(const flx_stats_dev &h, uint64_t n, flx_stats *out);
 
 // Stable LSD radix sort of (u64 key, u32 value) pairs, ascending by key.  keys0/vals0 hold the input;
 // keys1/vals1 are the ping-pong buffers; *sorted_keys / *sorted_vals point at whichever buffer holds

@@ -51,7 +51,7 @@ extern "C" int flx_score_batch_dev(flx_ctx *ctx, const flx_kmerset *set, const v
             FLX_HIP(ctx, hipMemsetAsync(out->child_offsets, 0, (n_reads + 1) * sizeof(uint64_t), ctx->stream));
         out->n_children = 0;
         FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return FLX_OK;
+        return flx_phred_finish(ctx);
     }
     return flx_score_kmer_dev(ctx, set, (const uint8_t *)d_plane, plane_bytes, (const uint64_t *)d_offsets,
                               (const int32_t *)d_lengths, (const uint32_t *)d_order, n_reads, params, out);

@@ -402,6 +402,8 @@ int flx_launch_score_phred(flx_ctx *ctx, const uint8_t *d_plane, uint64_t plane_
     a.n_groups = 0;
     a.redo_count = nullptr;
     a.redo_list = nullptr;
+    a.use_private = nullptr;
+    a.long_thr = 0x7fffffff;
 
     const long long n_slots = ((long long)p->window_size + CH - 1) / CH + 1;
     long long slots16 = n_slots * CH / 16 + 1;  // + the 16-byte mirror behind the last slot

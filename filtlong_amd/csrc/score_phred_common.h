@@ -29,6 +29,10 @@ struct PhredArgs {
     unsigned int n_groups; // ceil(n_reads / 64)
     unsigned int *redo_count;  // register kernel, bank-private tables: reads holding a byte >= 128 ...
     uint32_t *redo_list;       // ... are re-scored by the direct kernel (their ids are appended here)
+    // register kernel, chosen on the device: both table variants are launched and the one *use_private does not name returns at
+    // once (NULL: this launch is the choice) ...
+    const unsigned int *use_private;
+    int long_thr;  // ... and reads of at least this many bases are left to the cooperative path (INT_MAX: none)
 };
 
 __device__ __forceinline__ int wave_max(int v) {
@@ -106,6 +110,8 @@ struct PhredLong {
 
 // Before the Phred kernel: counts the batch's long reads (nothing when FLX_PHRED_LONG_MIN=0) ...
 int flx_phred_long_detect(flx_ctx *ctx, const flx_phred::PhredArgs &a, uint64_t plane_bytes, flx_phred::PhredLong *lp);
+// ... the length from which reads take that path (INT_MAX: the detection is off): known before any count is (*b0: its bucket) ...
+long long flx_phred_long_threshold(const flx_ctx *ctx, const flx_phred::PhredLong *lp, int *b0);
 // ... enqueues the copy of the counts (the caller synchronises the stream: one synchronisation serves both) ...
 int flx_phred_long_fetch(flx_ctx *ctx, flx_phred::PhredLong *lp);
 // ... and, when there are long reads, scores them on the context's stream and leaves in `a` the rest of the batch: a stably compacted
@@ -114,7 +120,9 @@ int flx_phred_long_fetch(flx_ctx *ctx, flx_phred::PhredLong *lp);
 int flx_phred_long_split(flx_ctx *ctx, flx_phred::PhredArgs &a, flx_phred::PhredLong *lp);
 
 // score_phred_regs.hip: the register-history kernel.  *launched = false when the window size has no instantiation
-// (the caller then uses the LDS-ring kernel).  It makes the long-read split (lp) after the synchronisation its table sample takes.
+// (the caller then uses the LDS-ring kernel).  Nothing waits in front of the kernel: the table variant is chosen on the device, the
+// kernel skips the long reads itself, and what the host has to know (which variant ran, whether there are long reads to score)
+// comes back in the context's pinned buffer — flx_phred_finish, after the scoring call's synchronisation, acts on it.
 int flx_launch_score_phred_regs(flx_ctx *ctx, flx_phred::PhredArgs a, bool *launched, flx_phred::PhredLong *lp);
 // score_phred_regs.hip: any window size, both window edges streamed from global memory (used where the LDS ring does not fit)
 int flx_launch_score_phred_stream(flx_ctx *ctx, flx_phred::PhredArgs a);

@@ -750,6 +750,23 @@ int flx_phred_long_fetch(flx_ctx *ctx, PhredLong *lp) {
 // batch's bases per lane of the default kernels (one lane per read, 16 waves of 64 lanes per CU) are at least twice as many: a
 // read no longer than a lane's share of the batch finishes inside the batch's time anyway.  The plane's size stands for the bases
 // (16-byte padding per read included: an upper bound, so at worst a read stays in the batch that could have left it).
+long long flx_phred_long_threshold(const flx_ctx *ctx, const PhredLong *lp, int *b0_out) {
+    int b0 = 0;
+    long long thr = 0x7fffffff;
+    if (lp && lp->on) {
+        thr = lp->t0;
+        if (!lp->forced) {
+            const double per_lane = (double)lp->plane_bytes / ((double)ctx->prop.multiProcessorCount * 1024.0);
+            while (b0 + 1 < PHRED_LONG_NB && (double)(thr * 2) <= per_lane) {
+                thr *= 2;
+                ++b0;
+            }
+        }
+    }
+    if (b0_out) *b0_out = b0;
+    return thr;
+}
+
 int flx_phred_long_split(flx_ctx *ctx, PhredArgs &a, PhredLong *lp) {
     if (!lp || !lp->on || lp->done) return FLX_OK;
     lp->done = true;
@@ -759,14 +776,7 @@ int flx_phred_long_split(flx_ctx *ctx, PhredArgs &a, PhredLong *lp) {
     }
     const unsigned long long *h = lp->h_counts;
     int b0 = 0;
-    long long thr = lp->t0;
-    if (!lp->forced) {
-        const double per_lane = (double)lp->plane_bytes / ((double)ctx->prop.multiProcessorCount * 1024.0);
-        while (b0 + 1 < PHRED_LONG_NB && (double)(thr * 2) <= per_lane) {
-            thr *= 2;
-            ++b0;
-        }
-    }
+    const long long thr = flx_phred_long_threshold(ctx, lp, &b0);
     unsigned long long k = 0, n_mean = 0, n_win = 0;
     for (int b = b0; b < PHRED_LONG_NB; ++b) {
         k += h[b];

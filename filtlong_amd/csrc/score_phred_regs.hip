@@ -140,6 +140,7 @@ __device__ __forceinline__ void funnel(const uint32_t (&p0)[4], const uint32_t (
 template <int A, bool PRIV, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) flx_score_phred_regs(const PhredArgs a) {
     using T = Tab<PRIV>;
+    if (a.use_private && (*a.use_private != 0u) != PRIV) return;  // the other table variant was chosen: no ticket is drawn
     constexpr int R = ((A + 5 + 3) / 4) * 4;  // ring pieces (16 bytes each): a multiple of the 4 pieces per round, >= A + 5
     constexpr int RR = R / 4;                 // ring rounds = unroll factor of the main loop
     constexpr int H = (A + 1 + 3) / 4;        // prologue rounds: they cover pieces 0..A (everything up to position ws)
@@ -193,15 +194,17 @@ __global__ void __launch_bounds__(WAVES * 64) flx_score_phred_regs(const PhredAr
     group = (unsigned int)__builtin_amdgcn_readfirstlane((int)group);
     if (group >= a.n_groups) break;
     const uint64_t gslot = (uint64_t)group * 64 + lane;
-    const bool live = gslot < a.n_reads;
+    const bool slot_used = gslot < a.n_reads;
     uint32_t rid = 0;
     int L = 0;
     uint64_t base = 0;
-    if (live) {
+    if (slot_used) {
         rid = a.order ? a.order[gslot] : (uint32_t)gslot;
         L = a.lengths[rid];
         base = a.offsets[rid];
     }
+    const bool live = slot_used && L < a.long_thr;  // a long read's outputs are the cooperative path's
+    if (!live) L = 0;
     const int Lmax = wave_max(L);
     const int Lmin = wave_min(L);
     if (Lmax == 0) {
@@ -721,10 +724,12 @@ int launch_one(flx_ctx *ctx, PhredArgs &a) {
     const uint64_t per_block = (uint64_t)WAVES;
     const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)a.n_groups + per_block - 1) / per_block,
                                                        (uint64_t)ctx->prop.multiProcessorCount);
-    ctx->last_phred_kernel = PRIV ? "flx_score_phred_regs_private" : "flx_score_phred_regs";
-    flx_time_begin(ctx, ctx->last_phred_kernel);
+    if (!a.use_private) {  // (chosen on the device: the caller brackets both launches and names the kernel afterwards)
+        ctx->last_phred_kernel = PRIV ? "flx_score_phred_regs_private" : "flx_score_phred_regs";
+        flx_time_begin(ctx, ctx->last_phred_kernel);
+    }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, ctx->stream, a);
-    flx_time_end(ctx);
+    if (!a.use_private) flx_time_end(ctx);
     FLX_HIP(ctx, hipGetLastError());
     return FLX_OK;
 }
@@ -815,7 +820,7 @@ namespace {
 // entries; bank-private tables cost the same whatever the data is and win (by up to ~11 %) on a wide quality range, where
 // plain entries e and e + 32 collide.  16 K sampled bytes give the byte distribution p; C(32,2) * sum over bank pairs of
 // p_e * p_e' (e != e', e = e' mod 32) is the expected number of conflicting lane pairs per 32-lane gather group.
-__global__ void __launch_bounds__(256) flx_phred_sample(const PhredArgs a, unsigned int *hist) {
+__global__ void __launch_bounds__(256) flx_phred_sample(const PhredArgs a, unsigned int *hist, unsigned int *done, unsigned int *use_private) {
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     uint64_t z = (t + 1) * 0x9E3779B97F4A7C15ULL;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
@@ -823,10 +828,45 @@ __global__ void __launch_bounds__(256) flx_phred_sample(const PhredArgs a, unsig
     z ^= z >> 31;
     const uint64_t r = z % a.n_reads;
     const int L = a.lengths[r];
-    if (L <= 0) return;
-    const uint32_t pos = (uint32_t)((z >> 32) % (uint64_t)L);
-    atomicAdd(&hist[a.plane[a.offsets[r] + pos]], 1u);
+    if (L > 0) {
+        const uint32_t pos = (uint32_t)((z >> 32) % (uint64_t)L);
+        atomicAdd(&hist[a.plane[a.offsets[r] + pos]], 1u);
+    }
+    // the workgroup that finishes last turns the histogram into the choice (one thread, the arithmetic in a fixed order)
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x != 0 || atomicAdd(done, 1u) != gridDim.x - 1) return;
+    __threadfence();
+    double tot = 0.0, conflicts = 0.0;
+    bool high = false;
+    for (int i = 0; i < 256; ++i) {
+        const unsigned int h = __hip_atomic_load(&hist[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        tot += h;
+        high = high || (i >= 128 && h != 0);
+    }
+    if (tot > 0) {
+        for (int b = 0; b < 32; ++b) {
+            double pb = 0.0, sq = 0.0;
+            for (int e = b; e < 256; e += 32) {
+                const double pe = __hip_atomic_load(&hist[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / tot;
+                pb += pe;
+                sq += pe * pe;
+            }
+            conflicts += pb * pb - sq;
+        }
+    }
+    *use_private = (!high && 496.0 * conflicts > 3.0) ? 1u : 0u;  // bytes >= 128 would all go through the redo path: stay plain
 }
+
+// what flx_phred_finish needs once the scoring call's synchronisation has passed
+struct PhredPending {
+    PhredArgs a;       // the whole batch, as the kernel got it
+    PhredLong lp;
+    bool chosen_on_device;
+    long timed_index;  // the bracket around both launches (-1: timing is off)
+    const unsigned int *h_flag;
+    const unsigned long long *h_counts;
+};
 }  // namespace
 
 int flx_launch_score_phred_stream(flx_ctx *ctx, PhredArgs a) {
@@ -874,63 +914,96 @@ int flx_launch_score_phred_regs(flx_ctx *ctx, PhredArgs a, bool *launched, Phred
     *launched = false;
     const int A = a.ws / 16;
     if (A > 38) return FLX_OK;  // the register-history kernel serves window sizes 1 .. 623 (A = ws / 16 = 0 .. 38); beyond: the dual-slot kernel
-    const char *env = getenv("FLX_PHRED_TABLES");  // "plain" | "private" | unset = decide from a sample of the data
+    const char *env = getenv("FLX_PHRED_TABLES");  // "plain" | "private" | unset = decided on the device from a sample of the data
     bool priv = env && strcmp(env, "private") == 0;
-    // scratch: [0,4) ticket, [4,8) redo count, [64, 1088) sample histogram, [2048, 2048 + 4 n) redo list
+    bool forced = env && (strcmp(env, "private") == 0 || strcmp(env, "plain") == 0);
+    if (A >= 32) {  // big rings come with plain tables only
+        forced = true;
+        priv = false;
+    }
+    delete (PhredPending *)ctx->phred_pending;  // (a call that failed half way)
+    ctx->phred_pending = nullptr;
+    // scratch: [0,4) ticket, [4,8) redo count, [8,12) sample workgroups done, [12,16) the choice, [64, 1088) sample histogram,
+    // [2048, 2048 + 4 n) redo list
     void *scr;
     FLX_CHECK(flx_scratch(ctx, 2048 + a.n_reads * 4, &scr));
+    void *pin;
+    FLX_CHECK(flx_pinned(ctx, 1024, &pin));
     a.ticket = (unsigned int *)scr;
     a.redo_count = (unsigned int *)scr + 1;
     a.redo_list = (uint32_t *)((char *)scr + 2048);
+    unsigned int *d_flag = (unsigned int *)scr + 3;
     FLX_HIP(ctx, hipMemsetAsync(scr, 0, 2048, ctx->stream));
-    if (!env || (strcmp(env, "private") != 0 && strcmp(env, "plain") != 0)) {
-        unsigned int h[256];
-        unsigned int *d_hist = (unsigned int *)((char *)scr + 64);
-        hipLaunchKernelGGL(flx_phred_sample, dim3(64), dim3(256), 0, ctx->stream, a, d_hist);
-        FLX_HIP(ctx, hipMemcpyAsync(h, d_hist, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-        FLX_CHECK(flx_phred_long_fetch(ctx, lp));  // the long-read counts come back with the same synchronisation
-        FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        double tot = 0.0, conflicts = 0.0;
-        for (int i = 0; i < 256; ++i) tot += h[i];
-        bool high = false;
-        for (int i = 128; i < 256; ++i) high = high || h[i] != 0;
-        if (tot > 0) {
-            for (int b = 0; b < 32; ++b) {
-                double pb = 0.0, sq = 0.0;
-                for (int e = b; e < 256; e += 32) {
-                    const double pe = h[e] / tot;
-                    pb += pe;
-                    sq += pe * pe;
-                }
-                conflicts += pb * pb - sq;
-            }
-        }
-        priv = !high && 496.0 * conflicts > 3.0;  // bytes >= 128 would all go through the redo path: stay plain
+    if (!forced) {
+        hipLaunchKernelGGL(flx_phred_sample, dim3(64), dim3(256), 0, ctx->stream, a, (unsigned int *)((char *)scr + 64),
+                           (unsigned int *)scr + 2, d_flag);
+        a.use_private = d_flag;
     }
-    FLX_CHECK(flx_phred_long_split(ctx, a, lp));
-    if (a.n_reads == 0) {  // every read was long
-        *launched = true;
-        return FLX_OK;
-    }
+    // long reads: the kernel leaves them out by their length; whether there are any is looked at after the call's synchronisation
+    a.long_thr = (int)std::min<long long>(flx_phred_long_threshold(ctx, lp, nullptr), 0x7fffffff);
     a.n_groups = (unsigned int)((a.n_reads + 63) / 64);
-    if (A <= 7) FLX_CHECK(flx_launch_score_phred_regs_part0(ctx, a, priv, launched));
-    else if (A <= 12) FLX_CHECK(flx_launch_score_phred_regs_part1(ctx, a, priv, launched));
-    else if (A <= 17) FLX_CHECK(flx_launch_score_phred_regs_part2(ctx, a, priv, launched));
-    else if (A <= 22) FLX_CHECK(flx_launch_score_phred_regs_part3(ctx, a, priv, launched));
-    else if (A <= 27) FLX_CHECK(flx_launch_score_phred_regs_part4(ctx, a, priv, launched));
-    else if (A <= 31) FLX_CHECK(flx_launch_score_phred_regs_part5(ctx, a, priv, launched));
-    else {
+    auto part = [&](bool pv) -> int {
+        if (A <= 7) return flx_launch_score_phred_regs_part0(ctx, a, pv, launched);
+        if (A <= 12) return flx_launch_score_phred_regs_part1(ctx, a, pv, launched);
+        if (A <= 17) return flx_launch_score_phred_regs_part2(ctx, a, pv, launched);
+        if (A <= 22) return flx_launch_score_phred_regs_part3(ctx, a, pv, launched);
+        if (A <= 27) return flx_launch_score_phred_regs_part4(ctx, a, pv, launched);
+        if (A <= 31) return flx_launch_score_phred_regs_part5(ctx, a, pv, launched);
         typedef int (*part_fn)(flx_ctx *, PhredArgs &, bool, bool *);
         static const part_fn wide[2] = {flx_launch_score_phred_regs_part6, flx_launch_score_phred_regs_part7};
-        priv = false;  // big rings come with plain tables only
-        FLX_CHECK(wide[(A - 32) / 4](ctx, a, priv, launched));
+        return wide[(A - 32) / 4](ctx, a, false, launched);
+    };
+    long timed_index = -1;
+    if (forced) {
+        FLX_CHECK(part(priv));
+    } else {  // both variants back to back; the one the flag does not name returns at once
+        ctx->last_phred_kernel = "flx_score_phred_regs";
+        flx_time_scope t(ctx, ctx->last_phred_kernel);
+        if (ctx->timing) timed_index = (long)ctx->timed.size() - 1;
+        FLX_CHECK(part(false));
+        FLX_CHECK(part(true));
     }
-    if (*launched && priv) {
+    if (!*launched) return FLX_OK;
+    if (priv || !forced) {
         flx_time_begin(ctx, "flx_score_phred_redo");
         hipLaunchKernelGGL(flx_score_phred_redo, dim3(256), dim3(256), 0, ctx->stream, a);
         flx_time_end(ctx);
         FLX_HIP(ctx, hipGetLastError());
     }
+    PhredPending *pd = new PhredPending();
+    pd->a = a;
+    pd->lp = *lp;
+    pd->chosen_on_device = !forced;
+    pd->timed_index = timed_index;
+    pd->h_flag = (const unsigned int *)pin;
+    pd->h_counts = (const unsigned long long *)((char *)pin + 64);
+    ctx->phred_pending = pd;
+    if (!forced) FLX_HIP(ctx, hipMemcpyAsync(pin, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (lp->on) FLX_HIP(ctx, hipMemcpyAsync((char *)pin + 64, lp->d_counts, sizeof lp->h_counts, hipMemcpyDeviceToHost, ctx->stream));
+    lp->done = true;  // (the caller's own split has nothing left to do)
+    return FLX_OK;
+}
+
+int flx_phred_finish(flx_ctx *ctx) {
+    PhredPending *pd = (PhredPending *)ctx->phred_pending;
+    if (!pd) return FLX_OK;
+    ctx->phred_pending = nullptr;
+    struct Free {
+        PhredPending *p;
+        ~Free() { delete p; }
+    } guard{pd};
+    if (pd->chosen_on_device) {
+        ctx->last_phred_kernel = *pd->h_flag ? "flx_score_phred_regs_private" : "flx_score_phred_regs";
+        if (pd->timed_index >= 0 && (size_t)pd->timed_index < ctx->timed.size()) ctx->timed[pd->timed_index].name = ctx->last_phred_kernel;
+    }
+    if (!pd->lp.on) return FLX_OK;
+    memcpy(pd->lp.h_counts, pd->h_counts, sizeof pd->lp.h_counts);
+    pd->lp.fetched = true;
+    const uint64_t n0 = pd->a.n_reads;
+    PhredArgs a = pd->a;
+    a.use_private = nullptr;
+    FLX_CHECK(flx_phred_long_split(ctx, a, &pd->lp));  // scores the long reads, if there are any, exactly as ever
+    if (a.n_reads != n0) FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return FLX_OK;
 }
 #endif

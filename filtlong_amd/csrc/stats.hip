@@ -43,9 +43,9 @@ struct Identity {
     __device__ __forceinline__ double operator()(double x) const { return x; }
 };
 struct SqDev {  // main.cpp:182-185: d = x - mean; d * d   (separate IEEE sub and mul, no FMA)
-    double mean;
+    const double *mean;  // device memory: the first fold leaves the mean there, the host never sees it in between
     __device__ __forceinline__ double operator()(double x) const {
-        const double d = x - mean;
+        const double d = x - *mean;
         return d * d;
     }
 };
@@ -57,7 +57,7 @@ struct ChunkMeta {
 };
 
 template <typename F>
-__global__ void __launch_bounds__(256) k_chunk_sums(uint64_t n, const double *x, F f, double *chunk_sum,
+__global__ void __launch_bounds__(256) k_chunk_sums(uint64_t n, const double *x, F f, double *chunk_sum, double *chunk_start,
                                                     unsigned char *chunk_clean, double *minmax) {
     // one wave per chunk
     const int lane = threadIdx.x & 63;
@@ -88,6 +88,7 @@ __global__ void __launch_bounds__(256) k_chunk_sums(uint64_t n, const double *x,
     const bool all_clean = __all(clean);
     if (lane == 0) {
         chunk_sum[chunk] = acc;
+        chunk_start[chunk] = acc;  // scanned in place afterwards
         chunk_clean[chunk] = all_clean ? 1 : 0;
         if (minmax) {
             minmax[2 * chunk] = lo;
@@ -104,12 +105,19 @@ __global__ void __launch_bounds__(256) k_minmax(uint64_t n_chunks, const double 
         if (l < lo) lo = l;
         if (h > hi) hi = h;
     }
-    __shared__ double sl[256], sh[256];
-    sl[threadIdx.x] = lo;
-    sh[threadIdx.x] = hi;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double l2 = __shfl_xor(lo, o, 64), h2 = __shfl_xor(hi, o, 64);
+        if (l2 < lo) lo = l2;
+        if (h2 > hi) hi = h2;
+    }
+    __shared__ double sl[4], sh[4];
+    if ((threadIdx.x & 63) == 0) {
+        sl[threadIdx.x >> 6] = lo;
+        sh[threadIdx.x >> 6] = hi;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int i = 1; i < 256; ++i) {
+        for (int i = 1; i < 4; ++i) {
             if (sl[i] < lo) lo = sl[i];
             if (sh[i] > hi) hi = sh[i];
         }
@@ -255,7 +263,7 @@ __device__ __forceinline__ int wave_apply_prefix(double &S, int e, Map2 m, bool 
 // ~25 descents, each two dependent loads and a handful of scans long.
 template <typename F>
 __global__ void __launch_bounds__(64) k_walk(uint64_t n, const double *x, F f, const ChunkMeta *meta, const ChunkMeta *batch,
-                                             uint64_t n_chunks, double *result, unsigned long long *serial_chunks) {
+                                             uint64_t n_chunks, flx_stats_dev *out, int second) {
     const int lane = threadIdx.x;
     double S = 0.0;
     unsigned long long n_serial = 0;
@@ -340,15 +348,24 @@ __global__ void __launch_bounds__(64) k_walk(uint64_t n, const double *x, F f, c
             bs = fb + 1;
         }
     }
+    // the fold's result and what the reference derives from it right away (IEEE division and square root, both correctly
+    // rounded on the device; the host checks them against its own at the stage's one synchronisation)
     if (lane == 0) {
-        result[0] = S;
-        serial_chunks[0] = n_serial;
+        const double nn = (double)n;
+        if (!second) {
+            out->sum = S;
+            out->mean = S / nn;  // main.cpp:181
+        } else {
+            out->sq_sum = S;
+            out->stdev = sqrt(S / nn);  // main.cpp:186
+        }
+        out->serial_chunks[second] = n_serial;
     }
 }
 
 template <typename F>
-int exact_fold(flx_ctx *ctx, uint64_t n, const double *x, F f, char *ws, double *d_result, unsigned long long *d_serial,
-               double *d_minmax_out) {
+int exact_fold(flx_ctx *ctx, uint64_t n, const double *x, F f, char *ws, flx_stats_dev *d_out, int second) {
+    double *d_minmax_out = second ? nullptr : &d_out->min;  // (min, max are adjacent)
     const uint64_t n_chunks = (n + CHUNK - 1) / CHUNK;
     double *chunk_sum = (double *)ws;
     double *chunk_start = chunk_sum + n_chunks;
@@ -360,19 +377,48 @@ int exact_fold(flx_ctx *ctx, uint64_t n, const double *x, F f, char *ws, double 
     char *scan_ws = (char *)(((uintptr_t)(clean + n_chunks) + 255) & ~(uintptr_t)255);
     hipStream_t st = ctx->stream;
     const unsigned nb = (unsigned)((n_chunks + 3) / 4);
-    hipLaunchKernelGGL(k_chunk_sums<F>, dim3(nb), dim3(256), 0, st, n, x, f, chunk_sum, clean,
+    hipLaunchKernelGGL(k_chunk_sums<F>, dim3(nb), dim3(256), 0, st, n, x, f, chunk_sum, chunk_start, clean,
                        d_minmax_out ? minmax : (double *)nullptr);
     if (d_minmax_out) hipLaunchKernelGGL(k_minmax, dim3(1), dim3(256), 0, st, n_chunks, minmax, d_minmax_out);
-    FLX_HIP(ctx, hipMemcpyAsync(chunk_start, chunk_sum, n_chunks * 8, hipMemcpyDeviceToDevice, st));
     FLX_CHECK(flx_exclusive_scan_f64_approx(ctx, n_chunks, chunk_start, scan_ws));
     hipLaunchKernelGGL(k_chunk_maps<F>, dim3(nb), dim3(256), 0, st, n, x, f, chunk_start, chunk_sum, clean, meta);
     hipLaunchKernelGGL(k_batch_maps, dim3((unsigned)((n_batches + 3) / 4)), dim3(256), 0, st, meta, n_chunks, batch);
-    hipLaunchKernelGGL(k_walk<F>, dim3(1), dim3(64), 0, st, n, x, f, meta, batch, n_chunks, d_result, d_serial);
+    hipLaunchKernelGGL(k_walk<F>, dim3(1), dim3(64), 0, st, n, x, f, meta, batch, n_chunks, d_out, second);
     FLX_HIP(ctx, hipGetLastError());
     return FLX_OK;
 }
 
 }  // namespace
+
+size_t flx_exact_stats_workspace(uint64_t n) {
+    const uint64_t n_chunks = (n + CHUNK - 1) / CHUNK;
+    return n_chunks * (8 + 8 + 16 + sizeof(ChunkMeta) + 1) + (n_chunks / 64 + 2) * sizeof(ChunkMeta) + 512 + (n_chunks / 2048 + 4096) * 8 * 2 + 4096;
+}
+
+int flx_exact_stats_async(flx_ctx *ctx, uint64_t n, const double *d_mean_q, void *ws, flx_stats_dev *d_out) {
+    flx_time_scope t(ctx, "flx_rank_stats");
+    FLX_CHECK(exact_fold(ctx, n, d_mean_q, Identity{0.0}, (char *)ws, d_out, 0));
+    FLX_CHECK(exact_fold(ctx, n, d_mean_q, SqDev{&d_out->mean}, (char *)ws, d_out, 1));
+    return FLX_OK;
+}
+
+bool flx_stats_finish(const flx_stats_dev &h, uint64_t n, flx_stats *out) {
+    memset(out, 0, sizeof *out);
+    out->sum = h.sum;
+    out->min = h.min;
+    out->max = h.max;
+    out->sq_sum = h.sq_sum;
+    {
+        volatile double s = out->sum, nn = (double)n;
+        out->mean = s / nn;  // main.cpp:181
+    }
+    {
+        volatile double ss = out->sq_sum, nn = (double)n;
+        out->stdev = sqrt(ss / nn);  // main.cpp:186 (sqrt is correctly rounded)
+    }
+    out->serial_chunks = h.serial_chunks[0] + h.serial_chunks[1];
+    return memcmp(&out->mean, &h.mean, 8) == 0 && memcmp(&out->stdev, &h.stdev, 8) == 0;
+}
 
 int flx_exact_stats(flx_ctx *ctx, uint64_t n, const double *d_mean_q, flx_stats *out) {
     memset(out, 0, sizeof *out);
@@ -381,39 +427,22 @@ int flx_exact_stats(flx_ctx *ctx, uint64_t n, const double *d_mean_q, flx_stats 
         out->min = 100.0; out->max = 0.0; out->sum = 0.0; out->mean = z / z; out->sq_sum = 0.0; out->stdev = sqrt(z / z);
         return FLX_OK;
     }
-    const uint64_t n_chunks = (n + CHUNK - 1) / CHUNK;
-    const size_t bytes = n_chunks * (8 + 8 + 16 + sizeof(ChunkMeta) + 1) + (n_chunks / 64 + 2) * sizeof(ChunkMeta) + 512 + (n_chunks / 2048 + 4096) * 8 * 2 + 4096;
     void *scr;
-    FLX_CHECK(flx_scratch(ctx, bytes, &scr));
-    char *ws = (char *)scr;
-    double *d_res = (double *)ws;             // [0]=sum/sq_sum, [2..3] = min,max
-    unsigned long long *d_serial = (unsigned long long *)(ws + 64);
-    ws += 256;
-
-    flx_time_begin(ctx, "flx_rank_stats");
-    FLX_CHECK(exact_fold(ctx, n, d_mean_q, Identity{0.0}, ws, d_res, d_serial, d_res + 2));
-    double h[4];
-    unsigned long long h_serial[2] = {0, 0};
-    FLX_HIP(ctx, hipMemcpyAsync(h, d_res, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    FLX_HIP(ctx, hipMemcpyAsync(&h_serial[0], d_serial, 8, hipMemcpyDeviceToHost, ctx->stream));
+    FLX_CHECK(flx_scratch(ctx, 256 + flx_exact_stats_workspace(n), &scr));
+    flx_stats_dev *d_out = (flx_stats_dev *)scr;
+    char *ws = (char *)scr + 256;
+    FLX_CHECK(flx_exact_stats_async(ctx, n, d_mean_q, ws, d_out));
+    flx_stats_dev h;
+    FLX_HIP(ctx, hipMemcpyAsync(&h, d_out, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    out->sum = h[0];
-    out->min = h[2];
-    out->max = h[3];
-    {
-        volatile double s = out->sum, nn = (double)n;
-        out->mean = s / nn;  // main.cpp:181
+    flx_stats_finish(h, n, out);
+    if (memcmp(&out->mean, &h.mean, 8) != 0) {  // the second fold ran on another mean than the host's: once more on the host's
+        FLX_HIP(ctx, hipMemcpyAsync(&d_out->mean, &out->mean, 8, hipMemcpyHostToDevice, ctx->stream));
+        FLX_CHECK(exact_fold(ctx, n, d_mean_q, SqDev{&d_out->mean}, ws, d_out, 1));
+        FLX_HIP(ctx, hipMemcpyAsync(&h, d_out, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+        FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        h.mean = out->mean;
+        flx_stats_finish(h, n, out);
     }
-    FLX_CHECK(exact_fold(ctx, n, d_mean_q, SqDev{out->mean}, ws, d_res, d_serial, (double *)nullptr));
-    FLX_HIP(ctx, hipMemcpyAsync(h, d_res, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FLX_HIP(ctx, hipMemcpyAsync(&h_serial[1], d_serial, 8, hipMemcpyDeviceToHost, ctx->stream));
-    flx_time_end(ctx);
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    out->sq_sum = h[0];
-    {
-        volatile double ss = out->sq_sum, nn = (double)n;
-        out->stdev = sqrt(ss / nn);  // main.cpp:186 (sqrt is correctly rounded)
-    }
-    out->serial_chunks = h_serial[0] + h_serial[1];
     return FLX_OK;
 }
