@@ -21,6 +21,10 @@
 //   * SELECT (default): MSD radix selection with weights — 8 histogram passes over the order-preserving 64-bit
 //     keys (one byte per pass, bins hold summed read lengths) locate the crossing key without moving any data;
 //     streaming reads only, which matters when the stage is replicated over 8x the reads after the all-gather.
+//     ONE enqueued sequence with one wait (cut_by_select) serves one rank and the sharded stage: its decisions are taken
+//     on the device, in a record (RankDev) that either the sequence itself fills (statistics folds + k_rank_prepare, one
+//     rank) or the host uploads (statistics from flx_exact_stats: the sharded stage, and the redo when the device's derived
+//     values are not the host's); sharded, the histograms are summed over the ranks between the passes.
 //   * SORT (FLX_RANK_SORT=1, and the fallback when the audit band is huge): stable LSD radix sort of
 //     (key, index) + exclusive scan of the lengths in sorted order + binary search (sort.hip).
 #include <algorithm>
@@ -40,6 +44,43 @@ struct NormArgs {
     double lw, mw, ww;
 };
 
+// ---- the SELECT path's record ---------------------------------------------------------------------------------------
+// state of the radix selection, kept on the device so that the 8 passes need no host round trip
+struct SelState {
+    unsigned long long prefix;  // key bytes decided so far (most significant first)
+    long long remaining;        // bases still to be collected inside the current prefix
+    unsigned int nan;           // some final score is NaN
+    unsigned int fail;          // ran out of weight (cannot happen when 0 < target < passed_bases)
+};
+
+// boundary-audit record of one read: everything the host needs to re-score it with the host libm
+struct BandRec {
+    uint64_t key;
+    double mean, window;
+    uint32_t idx;  // local reads2 index
+    int32_t len;
+    uint32_t was_passed;
+    uint32_t pad;
+};
+
+// Everything the host would otherwise fetch between the kernels of the stage — the statistics, the normalisation arguments,
+// the passed bases, the selection's state, the band's bounds and size — lives in one record on the device.  The kernels read it
+// and write it, and the host sees it once, together with the band's records, when it has to re-score the band with its libm.
+constexpr unsigned kBandCap = 1u << 16;   // band members the select path audits (beyond: the sort path)
+constexpr unsigned kBandInline = 1024;    // ... of which this many come back with the record itself
+struct RankDev {
+    flx_stats_dev stats;
+    NormArgs s;
+    SelState st[9];  // st[q]: q key bytes decided
+    unsigned long long passed_bases;  // = the total of the first histogram
+    unsigned long long k_lo, k_hi;    // the band's keys
+    unsigned long long weight_before;
+    unsigned int band_n;
+    unsigned int need_sort;   // target < passed_bases: there is a cut to find
+    unsigned int keys_given;  // k_lo / k_hi and st[8] are the host's: the band kernel takes them as they are
+};
+static_assert(sizeof(RankDev) <= 1024, "the band's records follow at byte 1024");
+
 // a8, src/read.cpp:241-244
 __device__ __host__ inline double length_score(int length) {
     const double half = 5000.0;
@@ -51,6 +92,46 @@ __device__ __host__ inline uint64_t key_ascending(double v) {
     uint64_t b;
     memcpy(&b, &v, 8);
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// the score behind a (descending) key
+__device__ __host__ inline double key_to_score(uint64_t k) {
+    uint64_t a = ~k;  // ascending key
+    uint64_t b = (a >> 63) ? (a & 0x7fffffffffffffffull) : ~a;
+    double v;
+    memcpy(&v, &b, 8);
+    return v;
+}
+
+// half width of the band around the crossing score sp: everything the reference might order differently
+__device__ __host__ inline double band_width(double sp) {
+    const double kBand = 1e-11;  // relative; the device pow is good to a few ulp (1e-16), so this is generous
+    return fabs(sp) * kBand + 1e-300;
+}
+// ... as keys (descending: lo = best score)
+__device__ __host__ inline void band_keys(uint64_t key_star, uint64_t *k_lo, uint64_t *k_hi) {
+    const double sp = key_to_score(key_star);
+    const double band = band_width(sp);
+    *k_lo = ~key_ascending(sp + band);
+    *k_hi = ~key_ascending(sp - band);
+}
+
+// main.cpp:188-195
+__device__ __host__ inline void norm_args(double mn, double mx, double mean, double stdev, double lw, double mw, double ww,
+                                          NormArgs &s, double *max_z) {
+    s.qmean = mean;
+    s.qstd = stdev;
+    if (stdev > 0.0) {
+        s.zmin = (mn - mean) / stdev;
+        const double zmax = (mx - mean) / stdev;
+        s.zspan = zmax - s.zmin;
+        *max_z = zmax;
+    } else {
+        s.zmin = 1.0;
+        s.zspan = 1.0 - 1.0;
+        *max_z = 1.0;
+    }
+    s.lw = lw; s.mw = mw; s.ww = ww;
 }
 
 template <typename PowFn>
@@ -90,9 +171,13 @@ struct DevPow {
     }
 };
 
-__device__ __forceinline__ void final_score_store(uint64_t i, const double *mean_q, const double *window_q, const int32_t *length,
-                                                  const NormArgs &s, double *final_score, uint64_t *keys, uint32_t *vals,
-                                                  unsigned int *any_nan) {
+// normalisation arguments: the record's when there is one (SELECT path), else the ones passed by value
+__global__ void k_final_score(uint64_t n, const double *mean_q, const double *window_q, const int32_t *length,
+                              NormArgs s_val, const RankDev *hd, double *final_score, uint64_t *keys, uint32_t *vals,
+                              unsigned int *any_nan) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const NormArgs s = hd ? hd->s : s_val;
     const double f = final_score_with(DevPow(), length[i], mean_q[i], window_q[i], s);
     if (any_nan && f != f) atomicOr(any_nan, 1u);
     if (final_score) final_score[i] = f;
@@ -100,14 +185,6 @@ __device__ __forceinline__ void final_score_store(uint64_t i, const double *mean
         keys[i] = ~key_ascending(f);  // descending score == ascending key
         if (vals) vals[i] = (uint32_t)i;
     }
-}
-
-__global__ void k_final_score(uint64_t n, const double *mean_q, const double *window_q, const int32_t *length,
-                              NormArgs s, double *final_score, uint64_t *keys, uint32_t *vals,
-                              unsigned int *any_nan) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    final_score_store(i, mean_q, window_q, length, s, final_score, keys, vals, any_nan);
 }
 
 // one atomic per workgroup (256 threads): thousands of same-address atomics cost more than the pass over the data
@@ -179,210 +256,48 @@ __global__ void k_cut_mark(uint64_t n, const uint64_t *keys_orig, uint64_t key_s
     if (!before) passed[i] = 0;
 }
 
-
-// ---- SELECT path ---------------------------------------------------------------------------------
-// state of the radix selection, kept on the device so that the 8 passes need no host round trip
-struct SelState {
-    unsigned long long prefix;  // key bytes decided so far (most significant first)
-    long long remaining;        // bases still to be collected inside the current prefix
-    unsigned int nan;           // some final score is NaN
-    unsigned int fail;          // ran out of weight (cannot happen when 0 < target < passed_bases)
-};
-
-// weight histogram of one key byte: bins[b] += length of every PASSED read whose key agrees with the state's prefix in its
-// top `prefix_bytes` bytes and whose next byte is b
-__global__ void __launch_bounds__(256) k_select_hist(uint64_t n, const uint64_t *keys, const int32_t *length,
-                                                     const uint8_t *passed, const SelState *st, int prefix_bytes,
-                                                     unsigned long long *bins) {
-    __shared__ unsigned long long h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t prefix = st->prefix;
-    const int shift = 56 - 8 * prefix_bytes;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t k = keys[i];
-        const bool match = prefix_bytes == 0 || (k >> (shift + 8)) == prefix;
-        if (match && passed[i]) {
-            const int len = length[i];
-            if (len > 0) atomicAdd(&h[(k >> shift) & 0xff], (unsigned long long)len);
-        }
-    }
-    __syncthreads();
-    if (h[threadIdx.x]) atomicAdd(&bins[threadIdx.x], h[threadIdx.x]);
-}
-
-// one byte of the crossing key from the (globally summed) histogram of this pass; bins[256] of pass 0 carries the NaN flag
-__global__ void __launch_bounds__(256) k_select_decide(const unsigned long long *bins, SelState *st, int pass) {
-    __shared__ unsigned long long h[256];
-    h[threadIdx.x] = bins[threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    if (pass == 0 && bins[256]) st->nan = 1;
-    long long cum = 0;
-    const long long remaining = st->remaining;
-    int d = 0;
-    for (; d < 256; ++d) {
-        if (cum + (long long)h[d] >= remaining) break;
-        cum += (long long)h[d];
-    }
-    if (d == 256) {
-        st->fail = 1;
-        d = 255;
-    }
-    st->remaining = remaining - cum;
-    st->prefix = (st->prefix << 8) | (unsigned long long)d;
-}
-
-// boundary-audit record of one read: everything the host needs to re-score it with the host libm
-struct BandRec {
-    uint64_t key;
-    double mean, window;
-    uint32_t idx;  // local reads2 index
-    int32_t len;
-    uint32_t was_passed;
-    uint32_t pad;
-};
-__global__ void __launch_bounds__(256) k_band_gather(unsigned int m, const uint32_t *band_idx, const uint64_t *keys,
-                                                     const double *mean, const double *window, const int32_t *length,
-                                                     const uint8_t *passed, BandRec *out) {
-    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    const uint32_t r = band_idx[i];
-    BandRec b;
-    b.key = keys[r];
-    b.mean = mean[r];
-    b.window = window[r];
-    b.idx = r;
-    b.len = length[r];
-    b.was_passed = passed[r];
-    b.pad = 0;
-    out[i] = b;
-}
-// the same for a run of SORTED positions [pos0, pos0 + m): read index from the sorted values, pre-cut flag in sorted order
-__global__ void __launch_bounds__(256) k_band_gather_sorted(unsigned int m, uint64_t pos0, const uint32_t *sorted_idx,
-                                                            const uint64_t *sorted_keys, const double *mean,
-                                                            const double *window, const int32_t *length,
-                                                            const uint8_t *pre_sorted, BandRec *out) {
-    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    const uint32_t r = sorted_idx[pos0 + i];
-    BandRec b;
-    b.key = sorted_keys[pos0 + i];
-    b.mean = mean[r];
-    b.window = window[r];
-    b.idx = r;
-    b.len = length[r];
-    b.was_passed = pre_sorted[pos0 + i];
-    b.pad = 0;
-    out[i] = b;
-}
 // passed[idx[i]] = val[i]
 __global__ void __launch_bounds__(256) k_scatter_flags(unsigned int m, const uint32_t *idx, const uint8_t *val, uint8_t *passed) {
     const unsigned int i = blockIdx.x * 256 + threadIdx.x;
     if (i < m) passed[idx[i]] = val[i];
 }
 
-// every read whose key lies in [k_lo, k_hi] is appended to the band list; the lengths of passed reads with a
-// smaller key (= better score) are summed: that is bases_so_far when the walk enters the band
-__global__ void __launch_bounds__(256) k_select_band(uint64_t n, const uint64_t *keys, const int32_t *length,
-                                                     const uint8_t *passed, uint64_t k_lo, uint64_t k_hi,
-                                                     uint32_t *band_idx, unsigned int *band_n, unsigned int cap,
-                                                     unsigned long long *weight_before) {
-    unsigned long long acc = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t k = keys[i];
-        if (k < k_lo) {
-            if (passed[i]) acc += (unsigned long long)length[i];
-        } else if (k <= k_hi) {
-            const unsigned int at = atomicAdd(band_n, 1u);
-            if (at < cap) band_idx[at] = (uint32_t)i;
-        }
-    }
-    block_add(acc, weight_before);
+// the audit record of read r
+__device__ __forceinline__ void band_rec_store(BandRec *out, uint32_t r, uint64_t key, uint32_t was_passed, const double *mean,
+                                               const double *window, const int32_t *length) {
+    BandRec b;
+    b.key = key;
+    b.mean = mean[r];
+    b.window = window[r];
+    b.idx = r;
+    b.len = length[r];
+    b.was_passed = was_passed;
+    b.pad = 0;
+    *out = b;
 }
-
-// everything at or beyond the band fails; the kept members of the band are switched back on by the host
-__global__ void __launch_bounds__(256) k_select_mark(uint64_t n, const uint64_t *keys, uint64_t k_lo, uint8_t *passed) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && keys[i] >= k_lo) passed[i] = 0;
-}
-
-// passed[idx[i]] = 1
-__global__ void __launch_bounds__(256) k_set_flags(unsigned int m, const uint32_t *idx, uint8_t *passed) {
+// SORT path: a run of SORTED positions [pos0, pos0 + m): read index from the sorted values, pre-cut flag in sorted order
+__global__ void __launch_bounds__(256) k_band_gather_sorted(unsigned int m, uint64_t pos0, const uint32_t *sorted_idx,
+                                                            const uint64_t *sorted_keys, const double *mean,
+                                                            const double *window, const int32_t *length,
+                                                            const uint8_t *pre_sorted, BandRec *out) {
     const unsigned int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < m) passed[idx[i]] = 1;
+    if (i >= m) return;
+    band_rec_store(out + i, sorted_idx[pos0 + i], sorted_keys[pos0 + i], pre_sorted[pos0 + i], mean, window, length);
 }
 
-// ---- SELECT path with the decisions on the device -----------------------------------------------------------------
-// Everything the host used to fetch between the kernels of the stage — the statistics, the normalisation arguments, the
-// passed bases, the selection's state, the band's bounds and size — lives in one record on the device.  The kernels read it
-// and write it, and the host sees it once, together with the band's records, when it has to re-score the band with its libm.
-constexpr unsigned kBandCap = 1u << 16;   // band members the select path audits (beyond: the sort path)
-constexpr unsigned kBandInline = 1024;    // ... of which this many come back with the record itself
-struct RankDev {
-    flx_stats_dev stats;
-    NormArgs s;
-    SelState st[9];  // st[q]: q key bytes decided
-    unsigned long long passed_bases;  // = the total of the first histogram
-    unsigned long long k_lo, k_hi;    // the band's keys
-    unsigned long long weight_before;
-    unsigned int band_n;
-    unsigned int need_sort;  // target < passed_bases: there is a cut to find
-};
-static_assert(sizeof(RankDev) <= 1024, "the band's records follow at byte 1024");
-
-__device__ __host__ inline void norm_args(const flx_stats_dev &st, double lw, double mw, double ww, NormArgs &s, double *max_z) {
-    s.qmean = st.mean;
-    s.qstd = st.stdev;
-    if (st.stdev > 0.0) {  // main.cpp:188-195
-        s.zmin = (st.min - st.mean) / st.stdev;
-        const double zmax = (st.max - st.mean) / st.stdev;
-        s.zspan = zmax - s.zmin;
-        *max_z = zmax;
-    } else {
-        s.zmin = 1.0;
-        s.zspan = 1.0 - 1.0;
-        *max_z = 1.0;
-    }
-    s.lw = lw; s.mw = mw; s.ww = ww;
-}
-
-__device__ __host__ inline double key_to_score(uint64_t k) {
-    uint64_t a = ~k;  // ascending key
-    uint64_t b = (a >> 63) ? (a & 0x7fffffffffffffffull) : ~a;
-    double v;
-    memcpy(&v, &b, 8);
-    return v;
-}
-
-// band around the crossing score: everything the reference might order differently (descending keys: lo = best score)
-__device__ __host__ inline void band_keys(uint64_t key_star, uint64_t *k_lo, uint64_t *k_hi) {
-    const double kBand = 1e-11;  // relative; the device pow is good to a few ulp (1e-16), so this is generous
-    const double sp = key_to_score(key_star);
-    const double band = fabs(sp) * kBand + 1e-300;
-    *k_lo = ~key_ascending(sp + band);
-    *k_hi = ~key_ascending(sp - band);
-}
-
+// ---- SELECT path: every kernel reads what it needs from the record and takes the previous kernel's decision in its prologue ----
 __global__ void k_rank_prepare(RankDev *h, double lw, double mw, double ww, long long target) {
     double max_z;
-    norm_args(h->stats, lw, mw, ww, h->s, &max_z);
+    norm_args(h->stats.min, h->stats.max, h->stats.mean, h->stats.stdev, lw, mw, ww, h->s, &max_z);
     SelState init = {0ull, target, 0u, 0u};
     h->st[0] = init;
 }
 
-__global__ void k_final_score_dev(uint64_t n, const double *mean_q, const double *window_q, const int32_t *length,
-                                  const RankDev *h, double *final_score, uint64_t *keys, unsigned int *any_nan) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const NormArgs s = h->s;
-    final_score_store(i, mean_q, window_q, length, s, final_score, keys, (uint32_t *)nullptr, any_nan);
-}
-
-// k_select_decide by a whole workgroup of 256 threads: st[pass + 1] from st[pass] and the complete histogram of pass `pass`.
-// Every workgroup of the NEXT kernel computes it for itself (2 KiB from the L2 and one scan) instead of waiting for a
-// one-workgroup launch in between; workgroup 0 also stores it.  The bins are >= 0, so the running sum does not decrease and
-// "the first bin at which it reaches `remaining`" is the one bin whose exclusive sum is below and inclusive sum is not.
+// One byte of the crossing key, by a whole workgroup of 256 threads: st[pass + 1] from st[pass] and the complete (globally
+// summed) histogram of pass `pass`; bins[256] of pass 0 carries the NaN flag.  Every workgroup of the NEXT kernel computes it
+// for itself (2 KiB from the L2 and one scan) instead of waiting for a one-workgroup launch in between; workgroup 0 also stores
+// it.  The bins are >= 0, so the running sum does not decrease and "the first bin at which it reaches `remaining`" is the one
+// bin whose exclusive sum is below and inclusive sum is not.
 __device__ SelState select_decide(const unsigned long long *bins, const SelState in, int pass, long long *total) {
     __shared__ long long wsum[4], s_cum;
     __shared__ int s_d;
@@ -420,10 +335,11 @@ __device__ SelState select_decide(const unsigned long long *bins, const SelState
     return out;
 }
 
-// k_select_hist with the previous pass's decision in front
-__global__ void __launch_bounds__(256) k_select_hist_dev(uint64_t n, const uint64_t *keys, const int32_t *length,
-                                                         const uint8_t *passed, RankDev *hd, int pass,
-                                                         unsigned long long *bins_all) {
+// weight histogram of one key byte, with the previous pass's decision in front: bins[b] += length of every PASSED read whose
+// key agrees with the decided prefix in its top `pass` bytes and whose next byte is b
+__global__ void __launch_bounds__(256) k_select_hist(uint64_t n, const uint64_t *keys, const int32_t *length,
+                                                     const uint8_t *passed, RankDev *hd, int pass,
+                                                     unsigned long long *bins_all) {
     __shared__ unsigned long long h[256];
     SelState st = hd->st[0];
     if (pass > 0) {
@@ -458,18 +374,27 @@ __global__ void __launch_bounds__(256) k_select_hist_dev(uint64_t n, const uint6
     if (h[threadIdx.x]) atomicAdd(&bins[threadIdx.x], h[threadIdx.x]);
 }
 
-// the last decision, the band's bounds from it, then k_select_band
-__global__ void __launch_bounds__(256) k_select_band_dev(uint64_t n, const uint64_t *keys, const int32_t *length,
-                                                         const uint8_t *passed, RankDev *hd, const unsigned long long *bins_all,
-                                                         uint32_t *band_idx, unsigned int cap) {
-    long long total;
-    const SelState st = select_decide(bins_all + 264 * 7, hd->st[7], 7, &total);
+// The last decision and the band's keys from it (or the keys the host gave), then: every read whose key lies in [k_lo, k_hi] is
+// appended to the band list; the lengths of passed reads with a smaller key (= better score) are summed: that is bases_so_far
+// when the walk enters the band
+__global__ void __launch_bounds__(256) k_select_band(uint64_t n, const uint64_t *keys, const int32_t *length,
+                                                     const uint8_t *passed, RankDev *hd, const unsigned long long *bins_all,
+                                                     uint32_t *band_idx, unsigned int cap) {
+    SelState st;
     uint64_t k_lo, k_hi;
-    band_keys(st.prefix, &k_lo, &k_hi);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        hd->st[8] = st;
-        hd->k_lo = k_lo;
-        hd->k_hi = k_hi;
+    if (hd->keys_given) {
+        st = hd->st[8];
+        k_lo = hd->k_lo;
+        k_hi = hd->k_hi;
+    } else {
+        long long total;
+        st = select_decide(bins_all + 264 * 7, hd->st[7], 7, &total);
+        band_keys(st.prefix, &k_lo, &k_hi);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            hd->st[8] = st;
+            hd->k_lo = k_lo;
+            hd->k_hi = k_hi;
+        }
     }
     if (!hd->need_sort || st.nan || st.fail) return;  // the host takes another path
     unsigned long long acc = 0;
@@ -485,23 +410,27 @@ __global__ void __launch_bounds__(256) k_select_band_dev(uint64_t n, const uint6
     block_add(acc, &hd->weight_before);
 }
 
-// k_band_gather for as many members as the band turned out to have (none when it exceeds the capacity)
-__global__ void __launch_bounds__(256) k_band_gather_dev(const RankDev *hd, unsigned int cap, const uint32_t *band_idx,
-                                                         const uint64_t *keys, const double *mean, const double *window,
-                                                         const int32_t *length, const uint8_t *passed, BandRec *out) {
+// the records of as many members as the band turned out to have (none when it exceeds `cap`)
+__global__ void __launch_bounds__(256) k_band_gather(const RankDev *hd, unsigned int cap, const uint32_t *band_idx,
+                                                     const uint64_t *keys, const double *mean, const double *window,
+                                                     const int32_t *length, const uint8_t *passed, BandRec *out) {
     const unsigned int m = hd->band_n;
     const unsigned int i = blockIdx.x * 256 + threadIdx.x;
     if (m > cap || i >= m) return;
     const uint32_t r = band_idx[i];
-    BandRec b;
-    b.key = keys[r];
-    b.mean = mean[r];
-    b.window = window[r];
-    b.idx = r;
-    b.len = length[r];
-    b.was_passed = passed[r];
-    b.pad = 0;
-    out[i] = b;
+    band_rec_store(out + i, r, keys[r], passed[r], mean, window, length);
+}
+
+// everything at or beyond the band fails; the kept members of the band are switched back on by k_set_flags
+__global__ void __launch_bounds__(256) k_select_mark(uint64_t n, const uint64_t *keys, uint64_t k_lo, uint8_t *passed) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && keys[i] >= k_lo) passed[i] = 0;
+}
+
+// passed[idx[i]] = 1
+__global__ void __launch_bounds__(256) k_set_flags(unsigned int m, const uint32_t *idx, uint8_t *passed) {
+    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < m) passed[idx[i]] = 1;
 }
 
 }  // namespace
@@ -587,11 +516,6 @@ static int exact_host_cut(flx_ctx *ctx, uint64_t n, const double *d_mean, const 
     rep->audited = n;
     return FLX_OK;
 }
-
-// =================================================================================================
-// SELECT path
-// =================================================================================================
-static const int FLX_SELECT_BAND_TOO_LARGE = -1000;
 
 // One rank's view when the global stage is sharded (flx_rank_and_cut_sharded_dev / flx_rank_and_cut_comm_dev): the
 // statistics are global, the final scores / keys / pass flags are those of the local reads2 entries [first, first + n),
@@ -682,98 +606,186 @@ static bool audit_walk(const std::vector<Cand> &cand, long long weight_before, l
     return order_dependent;
 }
 
+// a band record as a candidate of the audit: global reads2 index, exact score
+static Cand to_cand(const BandRec &b, uint64_t first, const NormArgs &s) {
+    return Cand{first + b.idx, b.key, host_final_score(b.len, b.mean, b.window, s), b.len, (uint8_t)b.was_passed};
+}
+
+// the host's normalisation arguments and what the report shows of them
+static void host_norm_args(const flx_stats &st, double lw, double mw, double ww, NormArgs &s, flx_cut_report *rep) {
+    volatile double a = lw, b = mw, c = ww;  // (no constant folding across the call: the divisions the reference performs)
+    norm_args(st.min, st.max, st.mean, st.stdev, a, b, c, s, &rep->max_z);
+    rep->mean_quality = st.mean;
+    rep->stdev_quality = st.stdev;
+    rep->min_z = s.zmin;
+}
+
+// =================================================================================================
+// SELECT path
+// =================================================================================================
+// It is ONE enqueued sequence — final scores, eight histogram passes that each start with the previous pass's
+// decision, the band kernel (last decision and the band's keys in its prologue), the gather of up to kBandInline band records —
+// and ONE wait, for the record and those band records in the context's pinned buffer.  Then the host audits the band with its
+// libm and enqueues mark + one upload + set.  Two ways of filling the record in front of it:
+//   * host_s == NULL (one rank, a cut asked for, no hook): both statistics folds and k_rank_prepare run inside the sequence.  After
+//     the wait the host recomputes mean, stdev and the normalisation arguments with its own arithmetic and compares bit for bit; on a
+//     difference (never seen; nothing has touched the pass flags yet) the call starts over with the host's values;
+//   * host_s != NULL (the sharded stage, both transports, and that redo): the caller ran flx_exact_stats and the host's norm_args;
+//     they are uploaded with the selection's initial state.
+// The band's keys are checked the same way in both; on a difference the host's keys go into the record and the band kernel and the
+// gather run once more.
+// SHARDED INVARIANT: the number and the order of the collective calls (sh.sum_dev, sh.sum) on a rank depend only on values that are
+// identical on all ranks — the summed bins, the summed counts, the arguments.  Nothing rank-local (a band-key mismatch, the size
+// of the local band, an empty shard) adds or removes one: a rank that took another turn alone would leave the others waiting.
+// That is why the sharded stage comes with host values (no redo of the eight passes), why the band-key repeat lies where no
+// collective is (after the last histogram sum, before the band exchange), and why a rank whose own band exceeds the capacity
+// gathers nothing but still takes part in every exchange.
+// *s_used: the normalisation arguments the scores were computed with (valid whenever the statistics were; the caller's sort
+// fallback needs them).  FLX_NEED_REPLICATED / FLX_SELECT_BAND_TOO_LARGE are returned before anything was modified.
+static const int FLX_SELECT_BAND_TOO_LARGE = -1000;
+
 static int cut_by_select(flx_ctx *ctx, uint64_t n, const double *mean, const double *window, const int32_t *length,
-                         uint8_t *passed, const NormArgs &s, int64_t target, void *d_final_score, flx_cut_report *rep,
-                         const Shard &sh = Shard()) {
+                         uint8_t *passed, double lw, double mw, double ww, int64_t target, void *d_final_score,
+                         flx_cut_report *rep, const Shard &sh, const NormArgs *host_s, NormArgs *s_used) {
     hipStream_t st = ctx->stream;
     const unsigned nb = (unsigned)((n + 255) / 256);
     const unsigned cap = kBandCap;
     const size_t bins_bytes = 8 * 264 * 8;  // 8 passes x (256 bins + flag slot + padding)
-    const size_t bytes = n * 8 + bins_bytes + 256 + (size_t)cap * (4 + sizeof(BandRec) + 4 + 1) + 1024;
+    const size_t recs_bytes = (size_t)cap * sizeof(BandRec);
+    // device: record (1 KiB) | band records | bins | band / set indices | keys, with the statistics' workspace in the keys' place
+    // when the folds run inside the sequence
+    const size_t body = host_s ? n * 8 : std::max<size_t>(n * 8, flx_exact_stats_workspace(n));
     void *scr;
-    FLX_CHECK(flx_scratch(ctx, bytes, &scr));
+    FLX_CHECK(flx_scratch(ctx, 1024 + recs_bytes + bins_bytes + (size_t)cap * 8 + body + 256, &scr));
     char *p = (char *)scr;
-    uint64_t *keys = (uint64_t *)p; p += n * 8;
+    RankDev *hd = (RankDev *)p; p += 1024;
+    BandRec *d_recs = (BandRec *)p; p += recs_bytes;
     unsigned long long *bins = (unsigned long long *)p; p += bins_bytes;  // pass q at bins + 264 q
-    SelState *d_state = (SelState *)p; p += 64;
-    unsigned long long *d_acc = (unsigned long long *)p; p += 192;       // [0] band count, [1] weight before the band
-    BandRec *d_recs = (BandRec *)p; p += (size_t)cap * sizeof(BandRec);
     uint32_t *band_idx = (uint32_t *)p; p += (size_t)cap * 4;
     uint32_t *d_set_idx = (uint32_t *)p; p += (size_t)cap * 4;
-    uint8_t *d_set_val = (uint8_t *)p;
+    uint64_t *keys = (uint64_t *)p;
+    // host (pinned): what comes back | what goes up: a record before the wait, the kept indices after it
+    const size_t back_bytes = 1024 + (size_t)kBandInline * sizeof(BandRec);
+    void *pin;
+    FLX_CHECK(flx_pinned(ctx, back_bytes + (size_t)cap * 4, &pin));
+    const RankDev *h = (const RankDev *)pin;
+    const BandRec *h_recs = (const BandRec *)((char *)pin + 1024);
+    uint32_t *h_set_idx = (uint32_t *)((char *)pin + back_bytes);
+    RankDev *up = (RankDev *)h_set_idx;
 
-    FLX_HIP(ctx, hipMemsetAsync(bins, 0, bins_bytes + 256, st));
-    {
-        SelState init = {0ull, (long long)target, 0u, 0u};
-        FLX_HIP(ctx, hipMemcpyAsync(d_state, &init, sizeof init, hipMemcpyHostToDevice, st));
+    FLX_HIP(ctx, hipMemsetAsync(bins, 0, bins_bytes, st));
+    if (host_s) {
+        memset(up, 0, sizeof *up);
+        up->s = *host_s;
+        up->st[0].remaining = (long long)target;
+        FLX_HIP(ctx, hipMemcpyAsync(hd, up, sizeof *up, hipMemcpyHostToDevice, st));
+    } else {
+        FLX_HIP(ctx, hipMemsetAsync(hd, 0, 1024, st));
+        FLX_CHECK(flx_exact_stats_async(ctx, n, mean, keys, &hd->stats));
+        hipLaunchKernelGGL(k_rank_prepare, dim3(1), dim3(1), 0, st, hd, lw, mw, ww, (long long)target);
     }
     {
         TimeScope t(ctx, "flx_rank_final_score");
         if (n)  // the NaN flag is OR-ed into the flag slot of the first histogram and summed over the ranks with it
-            hipLaunchKernelGGL(k_final_score, dim3(nb), dim3(256), 0, st, n, mean, window, length, s, (double *)d_final_score, keys,
-                               (uint32_t *)nullptr, (unsigned int *)(bins + 256));
+            hipLaunchKernelGGL(k_final_score, dim3(nb), dim3(256), 0, st, n, mean, window, length, NormArgs(), hd,
+                               (double *)d_final_score, keys, (uint32_t *)nullptr, (unsigned int *)(bins + 256));
     }
-
-    // ---- 8 weighted histogram passes, most significant byte first; the crossing byte is picked on the device ----------
     TimeScope tsel(ctx, "flx_rank_select");
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 2048));
-    for (int pass = 0; pass < 8; ++pass) {
-        unsigned long long *b = bins + 264 * pass;
-        hipLaunchKernelGGL(k_select_hist, dim3(grid), dim3(256), 0, st, n, keys, length, passed, d_state, pass, b);
-        FLX_CHECK(sh.sum_dev(ctx, (uint64_t *)b, 257));
-        hipLaunchKernelGGL(k_select_decide, dim3(1), dim3(256), 0, st, b, d_state, pass);
+    for (int pass = 0; pass < 8; ++pass) {  // most significant byte first; the next kernel's prologue decides from the summed bins
+        hipLaunchKernelGGL(k_select_hist, dim3(grid), dim3(256), 0, st, n, keys, length, passed, hd, pass, bins);
+        FLX_CHECK(sh.sum_dev(ctx, (uint64_t *)(bins + 264 * pass), 257));
     }
-    SelState h_state;
-    FLX_HIP(ctx, hipMemcpyAsync(&h_state, d_state, sizeof h_state, hipMemcpyDeviceToHost, st));
-    FLX_HIP(ctx, hipStreamSynchronize(st));
-    if (h_state.nan) {
+    auto band_and_back = [&]() -> int {
+        hipLaunchKernelGGL(k_select_band, dim3(grid), dim3(256), 0, st, n, keys, length, passed, hd, bins, band_idx, cap);
+        hipLaunchKernelGGL(k_band_gather, dim3(kBandInline / 256), dim3(256), 0, st, hd, kBandInline, band_idx, keys, mean, window,
+                           length, passed, d_recs);
+        FLX_HIP(ctx, hipMemcpyAsync(pin, hd, back_bytes, hipMemcpyDeviceToHost, st));
+        FLX_HIP(ctx, hipStreamSynchronize(st));
+        FLX_HIP(ctx, hipGetLastError());
+        return FLX_OK;
+    };
+    FLX_CHECK(band_and_back());
+
+    // ---- the host's own arithmetic; everything the device derived must agree with it ----------------------------------
+    NormArgs s;
+    if (host_s) s = *host_s;
+    else {
+        flx_stats stats;
+        bool same = flx_stats_finish(h->stats, n, &stats);
+        host_norm_args(stats, lw, mw, ww, s, rep);
+        same = same && memcmp(&s, &h->s, sizeof s) == 0;
+        if (!same) {
+            tsel.end();
+            FLX_CHECK(flx_exact_stats(ctx, n, mean, &stats));
+            host_norm_args(stats, lw, mw, ww, s, rep);
+            return cut_by_select(ctx, n, mean, window, length, passed, lw, mw, ww, target, d_final_score, rep, sh, &s, s_used);
+        }
+    }
+    *s_used = s;
+    rep->target_bases = target;
+    if (!h->need_sort) {  // target >= passed bases: the final scores are written, the flags stay
+        rep->outcome = FLX_CUT_ALREADY_BELOW;
+        return FLX_OK;
+    }
+    rep->outcome = FLX_CUT_SORTED;
+    const SelState fin = h->st[8];
+    if (fin.nan) {
         // NaN scores (stdev == 0 -> 0/0, main.cpp:192-206, or 0/0 window ratios): the reference's comparator is
         // inconsistent and its outcome is whatever libstdc++'s introsort does on reads2 order -> host path.
         tsel.end();
         if (sh.sharded()) return FLX_NEED_REPLICATED;
         return exact_host_cut(ctx, n, mean, window, length, passed, nullptr, nullptr, s, target, rep);
     }
-    if (h_state.fail)  // cannot happen when 0 < target < passed_bases
+    if (fin.fail)  // cannot happen when 0 < target < passed_bases
         return flx_fail(ctx, FLX_ERR_STATE, "radix select ran out of weight (target %lld)", (long long)target);
-    const uint64_t key_star = h_state.prefix;  // key of the read at which the walk reaches the target
-
-    // ---- band around the crossing score: everything the reference might order differently -------------------
     uint64_t k_lo, k_hi;
-    band_keys(key_star, &k_lo, &k_hi);
-    hipLaunchKernelGGL(k_select_band, dim3(grid), dim3(256), 0, st, n, keys, length, passed, k_lo, k_hi, band_idx,
-                       (unsigned int *)d_acc, cap, d_acc + 1);
-    unsigned long long h_acc[2] = {0, 0};
-    FLX_HIP(ctx, hipMemcpyAsync(h_acc, d_acc, 16, hipMemcpyDeviceToHost, st));
-    FLX_HIP(ctx, hipStreamSynchronize(st));
-    const unsigned local_n = (unsigned)(h_acc[0] & 0xffffffffull);
-    // the band's records in ONE gather kernel + ONE copy; exact scores with the host libm (what the reference computes)
-    // (a rank whose own band already exceeds the capacity gathers nothing but still takes part in the sum below: every rank
-    // must issue the same exchanges, and the summed sizes then send all of them to the sort path together)
-    std::vector<BandRec> recs(local_n <= cap ? local_n : 0);
-    if (local_n && local_n <= cap) {
-        hipLaunchKernelGGL(k_band_gather, dim3((local_n + 255) / 256), dim3(256), 0, st, local_n, band_idx, keys, mean, window,
-                           length, passed, d_recs);
+    band_keys(fin.prefix, &k_lo, &k_hi);
+    if (k_lo != h->k_lo || k_hi != h->k_hi) {  // (never seen) the band once more, around the host's keys
+        *up = *h;
+        up->k_lo = k_lo;
+        up->k_hi = k_hi;
+        up->keys_given = 1;
+        up->band_n = 0;
+        up->weight_before = 0;
+        FLX_HIP(ctx, hipMemcpyAsync(hd, up, sizeof *up, hipMemcpyHostToDevice, st));
+        FLX_CHECK(band_and_back());
+    }
+
+    // ---- the band's records: with the record, or (a local band beyond kBandInline; rare) all of them in a second gather and a
+    // plain pageable copy followed by a wait, rather than 2.6 MB of pinned memory held for it.  A rank whose own band already
+    // exceeds the capacity gathers nothing but still takes part in the sums below: every rank must issue the same exchanges,
+    // and the summed sizes then send all of them to the sort path together.
+    const unsigned local_n = h->band_n;
+    const unsigned long long local_weight_before = h->weight_before;
+    std::vector<BandRec> recs;
+    if (local_n <= kBandInline) recs.assign(h_recs, h_recs + local_n);
+    else if (local_n <= cap) {
+        recs.resize(local_n);
+        hipLaunchKernelGGL(k_band_gather, dim3((local_n + 255) / 256), dim3(256), 0, st, hd, cap, band_idx, keys, mean, window, length,
+                           passed, d_recs);
         FLX_HIP(ctx, hipMemcpyAsync(recs.data(), d_recs, (size_t)local_n * sizeof(BandRec), hipMemcpyDeviceToHost, st));
         FLX_HIP(ctx, hipStreamSynchronize(st));
-        std::sort(recs.begin(), recs.end(), [](const BandRec &x, const BandRec &y) { return x.idx < y.idx; });
     }
+    std::sort(recs.begin(), recs.end(), [](const BandRec &x, const BandRec &y) { return x.idx < y.idx; });
     // five words per candidate: global reads2 index, key, exact score bits, length, pre-cut flag
     auto put = [&](uint64_t *w, const BandRec &b) {
-        const double sc = host_final_score(b.len, b.mean, b.window, s);
-        w[0] = sh.first + b.idx;
-        w[1] = b.key;
-        memcpy(&w[2], &sc, 8);
-        w[3] = (uint64_t)(uint32_t)b.len;
-        w[4] = b.was_passed;
+        const Cand c = to_cand(b, sh.first, s);
+        w[0] = c.idx;
+        w[1] = c.key;
+        memcpy(&w[2], &c.score, 8);
+        w[3] = (uint64_t)(uint32_t)c.len;
+        w[4] = c.was_passed;
     };
     // ONE sum carries the band sizes of every rank (own slot filled, the rest zero), the weight in front of the band and,
     // in fixed slots of kInline candidates per rank, the candidates themselves — the band is a 1e-11 neighbourhood of the
     // crossing score, normally a handful of reads.  Only a rank with more than kInline members forces a second exchange.
+    // (One rank: both sums are no-ops.)
     const unsigned kInline = 32;
     const size_t head = (size_t)sh.world + 1;
     std::vector<uint64_t> counts(head + (sh.sharded() ? (size_t)sh.world * kInline * 5 : 0), 0);
     counts[sh.rank] = local_n;
-    counts[sh.world] = h_acc[1];
+    counts[sh.world] = local_weight_before;
     if (sh.sharded() && local_n <= kInline)
         for (unsigned i = 0; i < local_n; ++i) put(&counts[head + ((size_t)sh.rank * kInline + i) * 5], recs[i]);
     FLX_CHECK(sh.sum(ctx, counts.data(), counts.size()));
@@ -821,152 +833,9 @@ static int cut_by_select(flx_ctx *ctx, uint64_t n, const double *mean, const dou
 
     // ---- mark: better than the band -> unchanged; band and worse -> fail; kept band members -> back on ----------
     if (n) hipLaunchKernelGGL(k_select_mark, dim3(nb), dim3(256), 0, st, n, keys, k_lo, passed);
-    {   // this rank's members sit at [my_at, my_at + local_n) of the global band: one upload, one scatter kernel
-        std::vector<uint32_t> set_idx;
-        for (unsigned i = 0; i < local_n; ++i)
-            if (keep[my_at + i]) set_idx.push_back((uint32_t)(cand[my_at + i].idx - sh.first));
-        if (!set_idx.empty()) {
-            const unsigned m = (unsigned)set_idx.size();
-            std::vector<uint8_t> ones(m, 1);
-            FLX_HIP(ctx, hipMemcpyAsync(d_set_idx, set_idx.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
-            FLX_HIP(ctx, hipMemcpyAsync(d_set_val, ones.data(), m, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_scatter_flags, dim3((m + 255) / 256), dim3(256), 0, st, m, d_set_idx, d_set_val, passed);
-            FLX_HIP(ctx, hipStreamSynchronize(st));  // the host vectors go out of scope
-        }
-    }
-    FLX_HIP(ctx, hipStreamSynchronize(st));
-    rep->kept_bases = so_far;  // "keeping N bp", main.cpp:258
-    rep->audited = band_n;
-    FLX_HIP(ctx, hipGetLastError());
-    return FLX_OK;
-}
-
-// =================================================================================================
-// SELECT path, decisions on the device (one rank, a cut is asked for): statistics, normalisation, final scores, the eight
-// selection passes, the band and its records are enqueued back to back; the host waits ONCE, for the record and the band, checks
-// what the device derived against its own arithmetic, audits the band with its libm, and enqueues the mark.
-// FLX_RANK_REDO_HOST: the device's derived values are not the host's (never seen) — nothing has touched the pass flags yet and the
-// caller goes through the host-driven sequence below.
-// =================================================================================================
-static const int FLX_RANK_REDO_HOST = -1001;
-
-static int rank_and_cut_device(flx_ctx *ctx, uint64_t n, const double *mean, const double *window, const int32_t *length,
-                               uint8_t *passed, double lw, double mw, double ww, int64_t target, void *d_final_score,
-                               flx_cut_report *rep, NormArgs *s_out) {
-    hipStream_t st = ctx->stream;
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    const unsigned cap = kBandCap;
-    const size_t bins_bytes = 8 * 264 * 8;  // 8 passes x (256 bins + flag slot + padding)
-    const size_t recs_bytes = (size_t)cap * sizeof(BandRec);
-    // device: record (1 KiB) | band records | bins | band / set indices | keys, with the statistics' workspace in the keys' place
-    const size_t body = std::max<size_t>(n * 8, flx_exact_stats_workspace(n));
-    void *scr;
-    FLX_CHECK(flx_scratch(ctx, 1024 + recs_bytes + bins_bytes + (size_t)cap * 8 + body + 256, &scr));
-    char *p = (char *)scr;
-    RankDev *hd = (RankDev *)p; p += 1024;
-    BandRec *d_recs = (BandRec *)p; p += recs_bytes;
-    unsigned long long *bins = (unsigned long long *)p; p += bins_bytes;  // pass q at bins + 264 q
-    uint32_t *band_idx = (uint32_t *)p; p += (size_t)cap * 4;
-    uint32_t *d_set_idx = (uint32_t *)p; p += (size_t)cap * 4;
-    uint64_t *keys = (uint64_t *)p;
-    // host (pinned): what comes back | the indices that go up
-    const size_t back_bytes = 1024 + (size_t)kBandInline * sizeof(BandRec);
-    void *pin;
-    FLX_CHECK(flx_pinned(ctx, back_bytes + (size_t)cap * 4, &pin));
-    const RankDev *h = (const RankDev *)pin;
-    const BandRec *h_recs = (const BandRec *)((char *)pin + 1024);
-    uint32_t *h_set_idx = (uint32_t *)((char *)pin + back_bytes);
-
-    FLX_HIP(ctx, hipMemsetAsync(hd, 0, 1024, st));
-    FLX_HIP(ctx, hipMemsetAsync(bins, 0, bins_bytes, st));
-    FLX_CHECK(flx_exact_stats_async(ctx, n, mean, keys, &hd->stats));
-    hipLaunchKernelGGL(k_rank_prepare, dim3(1), dim3(1), 0, st, hd, lw, mw, ww, (long long)target);
-    {
-        TimeScope t(ctx, "flx_rank_final_score");  // the NaN flag is OR-ed into the flag slot of the first histogram
-        hipLaunchKernelGGL(k_final_score_dev, dim3(nb), dim3(256), 0, st, n, mean, window, length, hd, (double *)d_final_score, keys,
-                           (unsigned int *)(bins + 256));
-    }
-    TimeScope tsel(ctx, "flx_rank_select");
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 2048));
-    for (int pass = 0; pass < 8; ++pass)
-        hipLaunchKernelGGL(k_select_hist_dev, dim3(grid), dim3(256), 0, st, n, keys, length, passed, hd, pass, bins);
-    hipLaunchKernelGGL(k_select_band_dev, dim3(grid), dim3(256), 0, st, n, keys, length, passed, hd, bins, band_idx, cap);
-    hipLaunchKernelGGL(k_band_gather_dev, dim3(kBandInline / 256), dim3(256), 0, st, hd, kBandInline, band_idx, keys, mean, window,
-                       length, passed, d_recs);
-    FLX_HIP(ctx, hipMemcpyAsync(pin, hd, back_bytes, hipMemcpyDeviceToHost, st));
-    FLX_HIP(ctx, hipStreamSynchronize(st));
-    FLX_HIP(ctx, hipGetLastError());
-
-    // ---- the host's own arithmetic on the folds' sums; everything the device derived must agree with it ---------------
-    flx_stats stats;
-    bool same = flx_stats_finish(h->stats, n, &stats);
-    flx_stats_dev hs = h->stats;
-    hs.mean = stats.mean;
-    hs.stdev = stats.stdev;
-    NormArgs s;
-    {
-        volatile double a = lw, b = mw, c = ww;  // (no constant folding across the call: the same divisions as ever)
-        norm_args(hs, a, b, c, s, &rep->max_z);
-    }
-    same = same && memcmp(&s, &h->s, sizeof s) == 0;
-    const SelState fin = h->st[8];
-    uint64_t k_lo, k_hi;
-    band_keys(fin.prefix, &k_lo, &k_hi);
-    if (!same || (h->need_sort && !fin.nan && !fin.fail && (k_lo != h->k_lo || k_hi != h->k_hi))) return FLX_RANK_REDO_HOST;
-    *s_out = s;
-    rep->mean_quality = stats.mean;
-    rep->stdev_quality = stats.stdev;
-    rep->min_z = s.zmin;
-    rep->target_bases = target;
-    if (!h->need_sort) {  // target >= passed bases: the final scores are written, the flags stay
-        rep->outcome = FLX_CUT_ALREADY_BELOW;
-        return FLX_OK;
-    }
-    rep->outcome = FLX_CUT_SORTED;
-    if (fin.nan) {
-        // NaN scores (stdev == 0 -> 0/0, main.cpp:192-206, or 0/0 window ratios): the reference's comparator is
-        // inconsistent and its outcome is whatever libstdc++'s introsort does on reads2 order -> host path.
-        tsel.end();
-        return exact_host_cut(ctx, n, mean, window, length, passed, nullptr, nullptr, s, target, rep);
-    }
-    if (fin.fail)  // cannot happen when 0 < target < passed_bases
-        return flx_fail(ctx, FLX_ERR_STATE, "radix select ran out of weight (target %lld)", (long long)target);
-    const unsigned band_n = h->band_n;
-    if (band_n > cap) {  // huge tie group (e.g. millions of duplicate reads): let the sort path handle it
-        tsel.end();
-        return FLX_SELECT_BAND_TOO_LARGE;
-    }
-    std::vector<BandRec> recs(h_recs, h_recs + std::min(band_n, kBandInline));
-    if (band_n > kBandInline) {  // a band beyond what came back with the record: all of it, in a second round trip (rare: a plain
-                                 // pageable copy followed by a wait, rather than 2.6 MB of pinned memory held for it)
-        recs.resize(band_n);
-        hipLaunchKernelGGL(k_band_gather_dev, dim3((band_n + 255) / 256), dim3(256), 0, st, hd, cap, band_idx, keys, mean, window, length,
-                           passed, d_recs);
-        FLX_HIP(ctx, hipMemcpyAsync(recs.data(), d_recs, (size_t)band_n * sizeof(BandRec), hipMemcpyDeviceToHost, st));
-        FLX_HIP(ctx, hipStreamSynchronize(st));
-    }
-    std::sort(recs.begin(), recs.end(), [](const BandRec &x, const BandRec &y) { return x.idx < y.idx; });
-    std::vector<Cand> cand(band_n);
-    for (unsigned i = 0; i < band_n; ++i) {
-        const BandRec &b = recs[i];
-        Cand &c = cand[i];
-        c.idx = b.idx;
-        c.key = b.key;
-        c.score = host_final_score(b.len, b.mean, b.window, s);
-        c.len = b.len;
-        c.was_passed = (uint8_t)b.was_passed;
-    }
-    std::vector<uint8_t> keep;
-    long long so_far = 0;
-    const bool order_dependent = audit_walk(cand, (long long)h->weight_before, target, keep, &so_far);
-    tsel.end();
-    if (order_dependent) return exact_host_cut(ctx, n, mean, window, length, passed, nullptr, nullptr, s, target, rep);
-
-    // ---- mark: better than the band -> unchanged; band and worse -> fail; kept band members -> back on ----------
-    hipLaunchKernelGGL(k_select_mark, dim3(nb), dim3(256), 0, st, n, keys, k_lo, passed);
-    unsigned m = 0;
-    for (unsigned i = 0; i < band_n; ++i)
-        if (keep[i]) h_set_idx[m++] = (uint32_t)cand[i].idx;
+    unsigned m = 0;  // this rank's members sit at [my_at, my_at + local_n) of the global band
+    for (unsigned i = 0; i < local_n; ++i)
+        if (keep[my_at + i]) h_set_idx[m++] = (uint32_t)(cand[my_at + i].idx - sh.first);
     if (m) {  // one upload from the context's pinned buffer (it outlives the copy), one kernel
         FLX_HIP(ctx, hipMemcpyAsync(d_set_idx, h_set_idx, (size_t)m * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_set_flags, dim3((m + 255) / 256), dim3(256), 0, st, m, d_set_idx, passed);
@@ -1005,7 +874,7 @@ static int cut_by_sort(flx_ctx *ctx, uint64_t n, const double *mean, const doubl
     FLX_HIP(ctx, hipMemsetAsync(d_acc, 0, 32, st));
     {
         TimeScope t(ctx, "flx_rank_final_score");
-        hipLaunchKernelGGL(k_final_score, dim3(nb), dim3(256), 0, st, n, mean, window, length, s,
+        hipLaunchKernelGGL(k_final_score, dim3(nb), dim3(256), 0, st, n, mean, window, length, s, (const RankDev *)nullptr,
                            (double *)d_final_score, keys0, vals0, (unsigned int *)(d_acc + 2));
     }
 
@@ -1056,9 +925,7 @@ static int cut_by_sort(flx_ctx *ctx, uint64_t n, const double *mean, const doubl
     // p = sorted position of the read that crossed the target.  Every read whose DEVICE score is within
     // a relative band of score[p] could be ordered differently by the reference (host libm pow); re-score
     // those with the host libm and re-decide the cut among them.
-    if (h_acc[1] == 0) return FLX_OK;  // nothing kept (cannot happen when target > 0 and passed_bases > target)
     const uint64_t pstar = h_acc[1] - 1;
-    const double kBand = 1e-11;  // relative; device pow is good to a few ulp (1e-16), so this is generous
     const uint64_t W = 256;
     uint64_t lo = pstar > W ? pstar - W : 0, hi = std::min<uint64_t>(n, pstar + W + 1);
     for (;;) {
@@ -1069,20 +936,13 @@ static int cut_by_sort(flx_ctx *ctx, uint64_t n, const double *mean, const doubl
         FLX_HIP(ctx, hipMemcpy(hk.data(), skeys + lo, m * 8, hipMemcpyDeviceToHost));
         FLX_HIP(ctx, hipMemcpy(hv.data(), svals + lo, m * 4, hipMemcpyDeviceToHost));
         FLX_HIP(ctx, hipMemcpy(hex.data(), excl + lo, m * 8, hipMemcpyDeviceToHost));
-        auto key_to_score = [](uint64_t k) {
-            uint64_t a = ~k;  // ascending key
-            uint64_t b = (a >> 63) ? (a & 0x7fffffffffffffffull) : ~a;
-            double v;
-            memcpy(&v, &b, 8);
-            return v;
-        };
         const double sp = key_to_score(hk[pstar - lo]);
         if (std::isnan(sp)) {
             // NaN scores (stdev == 0, main.cpp:192-195 then 0/0): every comparison is false, the order is the
             // reference's tie order -> host path.
             return exact_host_cut(ctx, n, mean, window, length, passed, svals, pre_sorted, s, target, rep);
         }
-        const double band = std::fabs(sp) * kBand + 1e-300;
+        const double band = band_width(sp);
         // band limits inside the window
         uint64_t a = pstar - lo, b = pstar - lo;
         while (a > 0 && std::fabs(key_to_score(hk[a - 1]) - sp) <= band) --a;
@@ -1109,14 +969,7 @@ static int cut_by_sort(flx_ctx *ctx, uint64_t n, const double *mean, const doubl
         FLX_HIP(ctx, hipMemcpyAsync(recs.data(), d_recs.p, (size_t)mb * sizeof(BandRec), hipMemcpyDeviceToHost, st));
         FLX_HIP(ctx, hipStreamSynchronize(st));
         std::vector<Cand> cand(mb);
-        for (unsigned i = 0; i < mb; ++i) {
-            const BandRec &r = recs[i];
-            cand[i].idx = r.idx;
-            cand[i].key = r.key;
-            cand[i].len = r.len;
-            cand[i].was_passed = (uint8_t)r.was_passed;
-            cand[i].score = host_final_score(r.len, r.mean, r.window, s);
-        }
+        for (unsigned i = 0; i < mb; ++i) cand[i] = to_cand(recs[i], 0, s);
         // exact order inside the band, walk, and the test whether only the reference's std::sort can decide (audit_walk)
         std::vector<uint8_t> keep;
         long long so_far = 0;
@@ -1154,97 +1007,67 @@ static int rank_and_cut_impl(flx_ctx *ctx, uint64_t n_total, const double *mean_
     const double *mean = mean_all + sh.first;
     hipStream_t st = ctx->stream;
     const bool cutting = target_bases_set || keep_percent_set;
+    const int64_t target = cutting ? compute_target(target_bases_set, target_bases, keep_percent_set, keep_percent, total_bases) : 0;
+    const char *x = getenv("FLX_RANK_EXACT");  // test / bench hook: take the tie fallback (the reference's std::sort on the host)
+    const char *e = getenv("FLX_RANK_SORT");   // test hook / fallback selector
+    const bool exact_hook = x && x[0] == '1', sort_hook = e && e[0] == '1';
 
-    // ---- one rank, a cut that the total does not rule out: the whole stage with a single wait in the middle ----------------
-    if (cutting && n_total && !sh.sharded()) {
-        const int64_t t = compute_target(target_bases_set, target_bases, keep_percent_set, keep_percent, total_bases);
-        const char *x = getenv("FLX_RANK_EXACT"), *e = getenv("FLX_RANK_SORT");  // (test hooks: host-driven sequence below)
-        if (t < total_bases && !(x && x[0] == '1') && !(e && e[0] == '1')) {
-            NormArgs sd;
-            int rc = rank_and_cut_device(ctx, n, mean, window, length, passed, lw, mw, ww, t, d_final_score, rep, &sd);
-            if (rc == FLX_SELECT_BAND_TOO_LARGE) rc = cut_by_sort(ctx, n, mean, window, length, passed, sd, t, d_final_score, rep);
-            if (rc != FLX_RANK_REDO_HOST) return rc;
-            memset(rep, 0, sizeof *rep);
-        }
-    }
-
-    // ---- a20: statistics (exact serial folds) -------------------------------------------------
-    flx_stats stats;
-    FLX_CHECK(flx_exact_stats(ctx, n_total, mean_all, &stats));
+    // One rank, a cut that the total does not rule out, no hook: statistics, normalisation and the "already below" test are the
+    // select sequence's own, on the device.  Everything else brings them from the host.
+    const bool on_device = cutting && n_total && !sh.sharded() && target < total_bases && !exact_hook && !sort_hook;
     NormArgs s;
-    s.qmean = stats.mean;
-    s.qstd = stats.stdev;
-    if (stats.stdev > 0.0) {  // main.cpp:188-195
-        s.zmin = (stats.min - stats.mean) / stats.stdev;
-        const double zmax = (stats.max - stats.mean) / stats.stdev;
-        s.zspan = zmax - s.zmin;
-        rep->max_z = zmax;
-    } else {
-        s.zmin = 1.0;
-        s.zspan = 1.0 - 1.0;
-        rep->max_z = 1.0;
-    }
-    s.lw = lw; s.mw = mw; s.ww = ww;
-    rep->mean_quality = stats.mean;
-    rep->stdev_quality = stats.stdev;
-    rep->min_z = s.zmin;
+    if (!on_device) {
+        // ---- a20: statistics (exact serial folds) -------------------------------------------------
+        flx_stats stats;
+        FLX_CHECK(flx_exact_stats(ctx, n_total, mean_all, &stats));
+        host_norm_args(stats, lw, mw, ww, s, rep);
 
-    // ---- early outs that need no sort ----------------------------------------------------------
-    int64_t target = 0;
-    bool need_sort = false;
-    if (cutting && n_total) {
-        void *scr;
-        FLX_CHECK(flx_scratch(ctx, 64, &scr));
-        unsigned long long *d_acc = (unsigned long long *)scr;
-        unsigned long long passed_bases = sh.passed_bases;
-        if (!sh.have_passed_bases) {
-            FLX_HIP(ctx, hipMemsetAsync(d_acc, 0, 8, st));
-            FLX_CHECK(flx_passed_bases_async(ctx, n, length, passed, (uint64_t *)d_acc));
-            FLX_HIP(ctx, hipMemcpyAsync(&passed_bases, d_acc, 8, hipMemcpyDeviceToHost, st));
-            FLX_HIP(ctx, hipStreamSynchronize(st));
-            uint64_t pb = passed_bases;
-            FLX_CHECK(sh.sum(ctx, &pb, 1));
-            passed_bases = pb;
+        // ---- early outs that need no sort ----------------------------------------------------------
+        bool need_sort = false;
+        if (cutting && n_total) {
+            void *scr;
+            FLX_CHECK(flx_scratch(ctx, 64, &scr));
+            unsigned long long *d_acc = (unsigned long long *)scr;
+            unsigned long long passed_bases = sh.passed_bases;
+            if (!sh.have_passed_bases) {
+                FLX_HIP(ctx, hipMemsetAsync(d_acc, 0, 8, st));
+                FLX_CHECK(flx_passed_bases_async(ctx, n, length, passed, (uint64_t *)d_acc));
+                FLX_HIP(ctx, hipMemcpyAsync(&passed_bases, d_acc, 8, hipMemcpyDeviceToHost, st));
+                FLX_HIP(ctx, hipStreamSynchronize(st));
+                uint64_t pb = passed_bases;
+                FLX_CHECK(sh.sum(ctx, &pb, 1));
+                passed_bases = pb;
+            }
+            rep->target_bases = target;
+            if (target >= total_bases) rep->outcome = FLX_CUT_NOT_ENOUGH;
+            else if (target >= (int64_t)passed_bases) rep->outcome = FLX_CUT_ALREADY_BELOW;
+            else { rep->outcome = FLX_CUT_SORTED; need_sort = true; }
+        } else if (cutting) {
+            rep->target_bases = target;
+            rep->outcome = target >= total_bases ? FLX_CUT_NOT_ENOUGH : FLX_CUT_ALREADY_BELOW;
         }
-        target = compute_target(target_bases_set, target_bases, keep_percent_set, keep_percent, total_bases);
-        rep->target_bases = target;
-        if (target >= total_bases) rep->outcome = FLX_CUT_NOT_ENOUGH;
-        else if (target >= (int64_t)passed_bases) rep->outcome = FLX_CUT_ALREADY_BELOW;
-        else { rep->outcome = FLX_CUT_SORTED; need_sort = true; }
-    } else if (cutting) {
-        target = compute_target(target_bases_set, target_bases, keep_percent_set, keep_percent, total_bases);
-        rep->target_bases = target;
-        rep->outcome = target >= total_bases ? FLX_CUT_NOT_ENOUGH : FLX_CUT_ALREADY_BELOW;
-    }
-    if (n_total == 0) return FLX_OK;
+        if (n_total == 0) return FLX_OK;
 
-    // ---- a21/a22: normalise + final score (+ keys) --------------------------------------------
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    if (!need_sort) {
-        if (d_final_score && n) {
-            TimeScope t(ctx, "flx_rank_final_score");
-            hipLaunchKernelGGL(k_final_score, dim3(nb), dim3(256), 0, st, n, mean, window, length, s,
-                               (double *)d_final_score, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                               (unsigned int *)nullptr);
-            t.end();
-            FLX_HIP(ctx, hipStreamSynchronize(st));
+        // ---- a21/a22: normalise + final score, no cut ------------------------------------------------
+        if (!need_sort) {
+            if (d_final_score && n) {
+                TimeScope t(ctx, "flx_rank_final_score");
+                hipLaunchKernelGGL(k_final_score, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, mean, window, length, s,
+                                   (const RankDev *)nullptr, (double *)d_final_score, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                   (unsigned int *)nullptr);
+                t.end();
+                FLX_HIP(ctx, hipStreamSynchronize(st));
+            }
+            return FLX_OK;
         }
-        return FLX_OK;
-    }
-
-    {
-        const char *x = getenv("FLX_RANK_EXACT");  // test / bench hook: take the tie fallback (the reference's std::sort on the host)
-        if (x && x[0] == '1') {
-            if (sh.sharded()) return FLX_NEED_REPLICATED;
-            return exact_host_cut(ctx, n, mean, window, length, passed, nullptr, nullptr, s, target, rep);
-        }
-        const char *e = getenv("FLX_RANK_SORT");  // test hook / fallback selector
-        if (e && e[0] == '1') {
-            if (sh.sharded()) return FLX_NEED_REPLICATED;  // the sort path wants every record on one device
+        if (exact_hook || sort_hook) {
+            if (sh.sharded()) return FLX_NEED_REPLICATED;  // both want every record on one device
+            if (exact_hook) return exact_host_cut(ctx, n, mean, window, length, passed, nullptr, nullptr, s, target, rep);
             return cut_by_sort(ctx, n, mean, window, length, passed, s, target, d_final_score, rep);
         }
     }
-    const int rc = cut_by_select(ctx, n, mean, window, length, passed, s, target, d_final_score, rep, sh);
+    const int rc = cut_by_select(ctx, n, mean, window, length, passed, lw, mw, ww, target, d_final_score, rep, sh,
+                                 on_device ? nullptr : &s, &s);
     if (rc == FLX_SELECT_BAND_TOO_LARGE) return cut_by_sort(ctx, n, mean, window, length, passed, s, target, d_final_score, rep);
     return rc;
 }

@@ -1,6 +1,6 @@
-"""flx_rank_and_cut_dev with the stage's decisions taken on the device (rank.hip: rank_and_cut_device): every outcome of the cut,
-on device arrays, against the oracle — pass flags, report fields, final scores.  Where the single-wait sequence is expected to
-have served the call (no host-driven redo), the timing brackets say so: it never launches the separate passed-bases kernel."""
+"""flx_rank_and_cut_dev with the stage's decisions taken on the device (rank.hip: cut_by_select, the record filled by the
+sequence itself): every outcome of the cut, on device arrays, against the oracle — pass flags, report fields, final scores.  Where
+the single-wait sequence is expected to have served the call (no redo with host values), the timing brackets say so: it never launches the separate passed-bases kernel."""
 import os
 
 import numpy as np

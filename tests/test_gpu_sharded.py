@@ -82,6 +82,11 @@ def run_sharded(shards, mean, window, length, passed, **kw):
 
 
 def check(shards, mean, window, length, passed, **kw):
+    return check_out(shards, mean, window, length, passed, **kw)[:2]
+
+
+def check_out(shards, mean, window, length, passed, **kw):
+    """check(), and what every rank returned: (result, reductions, [(flags, report, need_replicated) per rank])"""
     okw = dict(kw)
     for a, b in (("length_weight", "lw"), ("mean_q_weight", "mw"), ("window_q_weight", "ww")):
         if a in okw:
@@ -93,7 +98,7 @@ def check(shards, mean, window, length, passed, **kw):
     if needs[0]:
         for (lo, hi), (flags, rep, need) in zip(shards, out):
             assert (flags == passed[lo:hi]).all(), "flags modified before a fallback"
-        return "fallback", calls
+        return "fallback", calls, out
     for (lo, hi), (flags, rep, need) in zip(shards, out):
         assert rep.outcome == want["outcome"] and rep.target_bases == want["target_bases"]
         assert rep.mean_quality == want["mean_quality"] and rep.stdev_quality == want["stdev_quality"]
@@ -101,7 +106,7 @@ def check(shards, mean, window, length, passed, **kw):
             assert rep.kept_bases == want["kept_bases"]
         bad = int((flags != want["passed"][lo:hi]).sum())
         assert bad == 0, "rank slice [%d,%d): %d flags differ" % (lo, hi, bad)
-    return "ok", calls
+    return "ok", calls, out
 
 
 def even(n, w):
@@ -156,6 +161,48 @@ def test_single_rank_equals_unsharded():
     mean, window, length, passed = random_reads2(n, 12)
     tot = int(length.astype(np.int64).sum())
     assert check([(0, n)], mean, window, length, passed, target_bases=tot // 3, total_bases=tot)[0] == "ok"
+
+
+def group_at_cut(n, seed, lo, hi, members, reach=None):
+    """`members` reads of [lo, hi) become copies of the slice's read of median mean quality, all passed.  Returns the arrays, the
+    group's indices and the cut's arguments: a target that the walk reaches inside the `reach`-th member (1-based; default: the last) of the group."""
+    mean, window, length, passed = random_reads2(n, seed)
+    rng = np.random.RandomState(seed + 1000)
+    mid = lo + int(np.argsort(mean[lo:hi])[(hi - lo) // 2])
+    group = np.union1d(lo + rng.choice(hi - lo, members, replace=False), [mid])
+    mean[group], window[group], length[group] = mean[mid], window[mid], length[mid]
+    passed[group] = 1
+    tot = int(length.astype(np.int64).sum())
+    fs = _oracle.rank_and_cut(mean, window, length, passed, target_bases=tot)["final_score"]  # (scores only)
+    better = int(length[(fs > fs[mid]) & (passed != 0)].astype(np.int64).sum())
+    target = better + int(length[mid]) * ((reach or len(group)) - 1) + 1
+    return (mean, window, length, passed), group, dict(target_bases=target, total_bases=tot)
+
+
+@pytest.mark.parametrize("n,lo,hi,members", [(4000, 0, 2000, 100), (8000, 4000, 8000, 1500)],
+                         ids=["second-band-exchange", "second-gather-on-a-shard"])
+def test_group_kept_whole_on_one_shard(n, lo, hi, members):
+    """A group of duplicates at the cut inside ONE rank's slice, larger than the 32 inline slots of the first band exchange (the
+    second exchange carries it), resp. larger than the 1024 records that come back with the device record (a second gather on
+    that rank).  Equal lengths and a target that only the group's LAST member reaches keep the whole group in any order: no
+    fallback, the exchanged records themselves are audited on every rank."""
+    arrays, group, cut = group_at_cut(n, 31 + members, lo, hi, members)
+    assert len(group) >= members and lo <= group.min() and group.max() < hi
+    want = _oracle.rank_and_cut(*arrays, **cut)
+    assert want["outcome"] == 3 and want["passed"][group].all()
+    res, calls, out = check_out(even(n, 2), *arrays, **cut)
+    assert res == "ok"
+    for flags, rep, need in out:
+        assert rep.exact_fallback == 0 and rep.audited >= members
+
+
+def test_band_over_capacity_falls_back_on_every_rank():
+    """More equal scores around the cut than the select path audits (2^16), spread over both slices, neither of which exceeds
+    it alone: the summed band sizes send every rank to the replicated stage, flags untouched (check() asserts both)."""
+    n = 200_000
+    arrays, group, cut = group_at_cut(n, 41, 0, n, 70_000, reach=30_001)
+    assert max(int((group < n // 2).sum()), int((group >= n // 2).sum())) < 65536 < len(group)
+    assert check(even(n, 2), *arrays, **cut)[0] == "fallback"
 
 
 @pytest.mark.parametrize("stage", ["sharded", "replicated", "rccl"])
