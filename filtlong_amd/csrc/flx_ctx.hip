@@ -67,7 +67,7 @@ static void build_phred_lut(double *lut257) {
 // (FLX_CLI_* belong to the command line, which checks its own.  tests/test_abi.py holds this list against the getenv calls in the sources.)
 static const char *const kKnownEnv[] = {
     "FLX_API_TIMING", "FLX_KMER_COVER", "FLX_KMER_FOLD", "FLX_KMER_FOLD_EVENTS", "FLX_KMER_FOLD_GRID", "FLX_KMER_FOLD_STREAMS", "FLX_KMER_LOCUS",
-    "FLX_KMER_LOCUS_BUILD", "FLX_KMER_PAIRTABLE", "FLX_KMER_PREFILTER", "FLX_KMER_SAFE1", "FLX_KMER_TEXT_ORDER", "FLX_PHRED_KERNEL",
+    "FLX_KMER_LOCUS_BUILD", "FLX_KMER_PAIRTABLE", "FLX_KMER_PREFILTER", "FLX_KMER_SAFE1", "FLX_KMER_TEXT_ORDER", "FLX_PHRED_FUNNEL", "FLX_PHRED_KERNEL",
     "FLX_PHRED_LONG_MIN", "FLX_PHRED_TABLES", "FLX_RANK_EXACT", "FLX_RANK_SORT", "FLX_RCCL_LIB",
 };
 static const char *const kOwnPrefixes[] = {"FLX_KMER_", "FLX_PHRED_", "FLX_RANK_", "FLX_RCCL_", "FLX_API_"};

@@ -21,7 +21,13 @@
 //     table; a read containing a byte >= 128 (not a FASTQ character) is flagged and re-scored by the direct kernel.
 //
 // The window size enters as A = ws / 16 (template parameter: it fixes which ring pieces hold the trailing edge)
-// and B = ws % 16 (run time: a byte funnel).
+// and B = ws % 16.  B is a run-time value in the 39 x 2 generic instantiations (BS = -1): the 16 trailing bytes of a piece
+// are first shifted into four dwords by a byte funnel, 4 v_alignbyte_b32 per piece.  For the default window 250 (A = 15,
+// B = 10) there is one more instantiation per table variant with B as the template parameter BS: the trailing byte of
+// position k of a piece is byte (16 - B + k) & 3 of dword (16 - B + k) >> 2 of the two ring pieces (p0 : p1), which the
+// address instruction (SDWA byte select / v_perm selector) picks from the ring dword itself — no funnel.  Vector
+// instructions per 64-base round: 384 for the fold (6 per base) + 4 slot reads + 16 funnel = 404 generic, 388 static.
+// FLX_PHRED_FUNNEL=runtime keeps the generic kernel at window 250 (tests, A/B).
 #include <algorithm>
 
 #include "flx_internal.h"
@@ -55,6 +61,16 @@ __device__ __forceinline__ uint32_t tab_addr(uint32_t x, uint32_t laneoff) {
         return __builtin_amdgcn_perm(x, laneoff, sel);
     }
     return lut_addr(x, SEL);  // byte * 8, one SDWA shift
+}
+// table address of byte e of the eight dwords x (e is a constant once the caller's loops are unrolled)
+template <bool PRIV>
+__device__ __forceinline__ uint32_t tab_addr_at(const uint32_t (&x)[8], int e, uint32_t laneoff) {
+    switch (e & 3) {
+        case 0: return tab_addr<PRIV, 0>(x[e >> 2], laneoff);
+        case 1: return tab_addr<PRIV, 1>(x[e >> 2], laneoff);
+        case 2: return tab_addr<PRIV, 2>(x[e >> 2], laneoff);
+        default: return tab_addr<PRIV, 3>(x[e >> 2], laneoff);
+    }
 }
 
 // ---- the FP64 folds as asm statements (see the header comment) ---------------------------------------------
@@ -137,7 +153,8 @@ __device__ __forceinline__ void funnel(const uint32_t (&p0)[4], const uint32_t (
 #undef FLX_FUN
 }
 
-template <int A, bool PRIV, int WAVES>
+// BS: -1 = ws % 16 is read at run time (byte funnel); 0..15 = ws % 16 at compile time (static byte selects, no funnel)
+template <int A, bool PRIV, int WAVES, int BS = -1>
 __global__ void __launch_bounds__(WAVES * 64) flx_score_phred_regs(const PhredArgs a) {
     using T = Tab<PRIV>;
     if (a.use_private && (*a.use_private != 0u) != PRIV) return;  // the other table variant was chosen: no ticket is drawn
@@ -183,7 +200,7 @@ __global__ void __launch_bounds__(WAVES * 64) flx_score_phred_regs(const PhredAr
     const uint32_t laneoff = (uint32_t)(lane & 31) * 8u;
     const uint32_t zaddr = PRIV ? (uint32_t)(T::ZIDX * T::ROW) + laneoff : (uint32_t)(T::ZIDX * T::ROW);
     const int ws = a.ws;
-    const int B = ws & 15;
+    const int B = BS >= 0 ? BS : ws & 15;  // (BS >= 0: the launcher passes only ws = 16 A + BS; B, fD and fsh are constants)
     const int fD = (16 - B) >> 2;
     const uint32_t fsh = (uint32_t)(16 - B) & 3u;
     const double ws_d = a.ws_d;
@@ -256,15 +273,26 @@ __global__ void __launch_bounds__(WAVES * 64) flx_score_phred_regs(const PhredAr
         if (half == 1 && r + 1 < n_rounds) issue_dma((r + 1) >> 1);
     };
     // addresses of the 4 bases of dword d; lanes whose read has ended look up the zero entry instead (exact no-op)
+    auto mask4 = [&](bool masked, int rem, int k0, uint32_t (&o)[4]) {
+        if (__builtin_expect(masked, 0)) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = (k0 + i) < rem ? o[i] : zaddr;
+        }
+    };
     auto addr4 = [&](uint32_t x, bool masked, int rem, int k0, uint32_t (&o)[4]) {
         o[0] = tab_addr<PRIV, 0>(x, laneoff);
         o[1] = tab_addr<PRIV, 1>(x, laneoff);
         o[2] = tab_addr<PRIV, 2>(x, laneoff);
         o[3] = tab_addr<PRIV, 3>(x, laneoff);
-        if (__builtin_expect(masked, 0)) {
+        mask4(masked, rem, k0, o);
+    };
+    // BS >= 0: the trailing bases of positions 4 d .. 4 d + 3 of a piece, bytes 16 - BS + 4 d .. of (p0 : p1), picked from the ring
+    // dwords themselves (dword and byte are constants)
+    auto trail4_static = [&](const uint32_t (&p0)[4], const uint32_t (&p1)[4], int d, bool masked, int rem, uint32_t (&o)[4]) {
+        const uint32_t x[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] = (k0 + i) < rem ? o[i] : zaddr;
-        }
+        for (int i = 0; i < 4; ++i) o[i] = tab_addr_at<PRIV>(x, 16 - BS + 4 * d + i, laneoff);
+        mask4(masked, rem, 4 * d, o);
     };
     auto head_piece = [&](const uint32_t (&lw)[4], int Tp) {  // all 16 positions < window_size
         const bool masked = 16 * (Tp + 1) > Lmin;
@@ -280,12 +308,13 @@ __global__ void __launch_bounds__(WAVES * 64) flx_score_phred_regs(const PhredAr
         const bool masked = 16 * (Tp + 1) > Lmin;
         const int rem = L - 16 * Tp;
         uint32_t tw[4];
-        funnel(p0, p1, fD, fsh, tw);
+        if constexpr (BS < 0) funnel(p0, p1, fD, fsh, tw);
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             uint32_t aj[4], ai[4];
             addr4(lw[d], masked, rem, 4 * d, aj);
-            addr4(tw[d], masked, rem, 4 * d, ai);
+            if constexpr (BS < 0) addr4(tw[d], masked, rem, 4 * d, ai);
+            else trail4_static(p0, p1, d, masked, rem, ai);
             fold4<T::QOFF, T::DOFF>(aj[0], aj[1], aj[2], aj[3], ai[0], ai[1], ai[2], ai[3], s, w, mn);
         }
     };
@@ -293,12 +322,13 @@ __global__ void __launch_bounds__(WAVES * 64) flx_score_phred_regs(const PhredAr
         // piece A: positions 16 A + k; k < B belongs to the first window, k == B - 1 completes it (src/read.cpp:219-224)
         const int rem = L - 16 * Tp;
         uint32_t tw[4];
-        funnel(p0, p1, fD, fsh, tw);
+        if constexpr (BS < 0) funnel(p0, p1, fD, fsh, tw);
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             uint32_t aj[4], ai[4];
             addr4(lw[d], true, rem, 4 * d, aj);
-            addr4(tw[d], true, rem, 4 * d, ai);
+            if constexpr (BS < 0) addr4(tw[d], true, rem, 4 * d, ai);
+            else trail4_static(p0, p1, d, true, rem, ai);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int k = 4 * d + i;
@@ -714,10 +744,10 @@ __global__ void __launch_bounds__(256) flx_score_phred_redo(const PhredArgs a) {
 
 #endif
 
-template <int A, bool PRIV, int WAVES>
+template <int A, bool PRIV, int WAVES, int BS = -1>
 int launch_one(flx_ctx *ctx, PhredArgs &a) {
     using T = Tab<PRIV>;
-    auto kern = flx_score_phred_regs<A, PRIV, WAVES>;
+    auto kern = flx_score_phred_regs<A, PRIV, WAVES, BS>;
     // one persistent workgroup per CU; asking for more than half of the LDS keeps a second one off the CU
     const size_t lds = std::max<size_t>((size_t)T::SLOT0 + (size_t)WAVES * 8192, 84 * 1024);
     FLX_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -743,8 +773,12 @@ struct WavesFor {
     static constexpr int value = PRIV && plain > 11 ? 11 : plain;
 };
 
+// bs: ws % 16 when the window size has a static-B instantiation and may use it, else -1 (only window 250 has one: A = 15, BS = 10)
 template <int A>
-int launch_a(flx_ctx *ctx, PhredArgs &a, bool priv) {
+int launch_a(flx_ctx *ctx, PhredArgs &a, bool priv, int bs) {
+    if constexpr (A == 15) {
+        if (bs == 10) return priv ? launch_one<A, true, WavesFor<A, true>::value, 10>(ctx, a) : launch_one<A, false, WavesFor<A, false>::value, 10>(ctx, a);
+    }
     if constexpr (A >= 32) {  // big rings: plain tables only (each instantiation takes ~30 s to compile)
         return launch_one<A, false, WavesFor<A, false>::value>(ctx, a);
     } else {
@@ -761,38 +795,38 @@ int launch_a(flx_ctx *ctx, PhredArgs &a, bool priv) {
 #define FLX_REGS_CASE(AA) \
     case AA:              \
         *launched = true; \
-        return launch_a<AA>(ctx, a, priv);
+        return launch_a<AA>(ctx, a, priv, bs);
 #define FLX_REGS_CAT2(a, b) a##b
 #define FLX_REGS_CAT(a, b) FLX_REGS_CAT2(a, b)
 #define FLX_REGS_WIDE_NAME FLX_REGS_CAT(flx_launch_score_phred_regs_part, FLX_REGS_PART)
 #if FLX_REGS_PART == 0
-int flx_launch_score_phred_regs_part0(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched) {
+int flx_launch_score_phred_regs_part0(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
     switch (a.ws / 16) { FLX_REGS_CASE(0) FLX_REGS_CASE(1) FLX_REGS_CASE(2) FLX_REGS_CASE(3) FLX_REGS_CASE(4) FLX_REGS_CASE(5) FLX_REGS_CASE(6) FLX_REGS_CASE(7) default: return FLX_OK; }
 }
 #elif FLX_REGS_PART == 1
-int flx_launch_score_phred_regs_part1(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched) {
+int flx_launch_score_phred_regs_part1(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
     switch (a.ws / 16) { FLX_REGS_CASE(8) FLX_REGS_CASE(9) FLX_REGS_CASE(10) FLX_REGS_CASE(11) FLX_REGS_CASE(12) default: return FLX_OK; }
 }
 #elif FLX_REGS_PART == 2
-int flx_launch_score_phred_regs_part2(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched) {
+int flx_launch_score_phred_regs_part2(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
     switch (a.ws / 16) { FLX_REGS_CASE(13) FLX_REGS_CASE(14) FLX_REGS_CASE(15) FLX_REGS_CASE(16) FLX_REGS_CASE(17) default: return FLX_OK; }
 }
 #elif FLX_REGS_PART == 3
-int flx_launch_score_phred_regs_part3(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched) {
+int flx_launch_score_phred_regs_part3(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
     switch (a.ws / 16) { FLX_REGS_CASE(18) FLX_REGS_CASE(19) FLX_REGS_CASE(20) FLX_REGS_CASE(21) FLX_REGS_CASE(22) default: return FLX_OK; }
 }
 #elif FLX_REGS_PART == 4
-int flx_launch_score_phred_regs_part4(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched) {
+int flx_launch_score_phred_regs_part4(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
     switch (a.ws / 16) { FLX_REGS_CASE(23) FLX_REGS_CASE(24) FLX_REGS_CASE(25) FLX_REGS_CASE(26) FLX_REGS_CASE(27) default: return FLX_OK; }
 }
 #elif FLX_REGS_PART == 5
-int flx_launch_score_phred_regs_part5(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched) {
+int flx_launch_score_phred_regs_part5(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
     switch (a.ws / 16) { FLX_REGS_CASE(28) FLX_REGS_CASE(29) FLX_REGS_CASE(30) FLX_REGS_CASE(31) default: return FLX_OK; }
 }
 #else
 // parts 6 and 7: A = 32..35 and 36..38: window sizes 512..623 (beyond them a ring leaves room for one wave per SIMD only, and the
 // dual-slot kernel is faster)
-int FLX_REGS_WIDE_NAME(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched) {
+int FLX_REGS_WIDE_NAME(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
     constexpr int A0 = 32 + 4 * (FLX_REGS_PART - 6);
     switch (a.ws / 16) {
         FLX_REGS_CASE(A0) FLX_REGS_CASE(A0 + 1) FLX_REGS_CASE(A0 + 2)
@@ -806,12 +840,12 @@ int FLX_REGS_WIDE_NAME(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched) {
 #undef FLX_REGS_CASE
 
 #if FLX_REGS_PART == 0
-int flx_launch_score_phred_regs_part1(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched);
-int flx_launch_score_phred_regs_part2(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched);
-int flx_launch_score_phred_regs_part3(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched);
-int flx_launch_score_phred_regs_part4(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched);
-int flx_launch_score_phred_regs_part5(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched);
-#define FLX_REGS_DECL(P) int flx_launch_score_phred_regs_part##P(flx_ctx *ctx, PhredArgs &a, bool priv, bool *launched);
+int flx_launch_score_phred_regs_part1(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
+int flx_launch_score_phred_regs_part2(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
+int flx_launch_score_phred_regs_part3(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
+int flx_launch_score_phred_regs_part4(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
+int flx_launch_score_phred_regs_part5(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
+#define FLX_REGS_DECL(P) int flx_launch_score_phred_regs_part##P(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
 FLX_REGS_DECL(6) FLX_REGS_DECL(7)
 #undef FLX_REGS_DECL
 
@@ -921,6 +955,10 @@ int flx_launch_score_phred_regs(flx_ctx *ctx, PhredArgs a, bool *launched, Phred
         forced = true;
         priv = false;
     }
+    const char *fenv = getenv("FLX_PHRED_FUNNEL");  // "runtime": the generic kernel also where a static-B instantiation exists (tests, A/B)
+    if (fenv && *fenv && strcmp(fenv, "runtime") != 0)
+        return flx_fail(ctx, FLX_ERR_INVALID, "FLX_PHRED_FUNNEL=%s: expected runtime (or unset)", fenv);
+    const int bs = (a.ws == 250 && !(fenv && *fenv)) ? 10 : -1;
     delete (PhredPending *)ctx->phred_pending;  // (a call that failed half way)
     ctx->phred_pending = nullptr;
     // scratch: [0,4) ticket, [4,8) redo count, [8,12) sample workgroups done, [12,16) the choice, [64, 1088) sample histogram,
@@ -943,15 +981,15 @@ int flx_launch_score_phred_regs(flx_ctx *ctx, PhredArgs a, bool *launched, Phred
     a.long_thr = (int)std::min<long long>(flx_phred_long_threshold(ctx, lp, nullptr), 0x7fffffff);
     a.n_groups = (unsigned int)((a.n_reads + 63) / 64);
     auto part = [&](bool pv) -> int {
-        if (A <= 7) return flx_launch_score_phred_regs_part0(ctx, a, pv, launched);
-        if (A <= 12) return flx_launch_score_phred_regs_part1(ctx, a, pv, launched);
-        if (A <= 17) return flx_launch_score_phred_regs_part2(ctx, a, pv, launched);
-        if (A <= 22) return flx_launch_score_phred_regs_part3(ctx, a, pv, launched);
-        if (A <= 27) return flx_launch_score_phred_regs_part4(ctx, a, pv, launched);
-        if (A <= 31) return flx_launch_score_phred_regs_part5(ctx, a, pv, launched);
-        typedef int (*part_fn)(flx_ctx *, PhredArgs &, bool, bool *);
+        if (A <= 7) return flx_launch_score_phred_regs_part0(ctx, a, pv, bs, launched);
+        if (A <= 12) return flx_launch_score_phred_regs_part1(ctx, a, pv, bs, launched);
+        if (A <= 17) return flx_launch_score_phred_regs_part2(ctx, a, pv, bs, launched);
+        if (A <= 22) return flx_launch_score_phred_regs_part3(ctx, a, pv, bs, launched);
+        if (A <= 27) return flx_launch_score_phred_regs_part4(ctx, a, pv, bs, launched);
+        if (A <= 31) return flx_launch_score_phred_regs_part5(ctx, a, pv, bs, launched);
+        typedef int (*part_fn)(flx_ctx *, PhredArgs &, bool, int, bool *);
         static const part_fn wide[2] = {flx_launch_score_phred_regs_part6, flx_launch_score_phred_regs_part7};
-        return wide[(A - 32) / 4](ctx, a, false, launched);
+        return wide[(A - 32) / 4](ctx, a, false, bs, launched);
     };
     long timed_index = -1;
     if (forced) {
