@@ -17,6 +17,7 @@
 // (tables built on the host with the host libm; see flx_ctx.hip) and four dependent FP64 ops
 // (sum += Q; w -= D_old; w += D_new; min).  No pow, no division, no 8 B/base quality vector.
 #include <algorithm>
+#include <memory>
 
 #include "flx_internal.h"
 #include "score_phred_common.h"
@@ -134,15 +135,17 @@ __global__ void __launch_bounds__(WAVES * 64) flx_score_phred_ring(const PhredAr
     group = (unsigned int)__builtin_amdgcn_readfirstlane((int)group);
     if (group >= a.n_groups) break;
     const uint64_t slot = (uint64_t)group * 64 + lane;
-    const bool live = slot < a.n_reads;
+    const bool slot_used = slot < a.n_reads;
     uint32_t rid = 0;
     int L = 0;
     uint64_t base = 0;
-    if (live) {
+    if (slot_used) {
         rid = a.order ? a.order[slot] : (uint32_t)slot;
         L = a.lengths[rid];
         base = a.offsets[rid];
     }
+    const bool live = slot_used && L < a.long_thr;  // a long read's outputs are the cooperative path's
+    if (!live) L = 0;
     const int Lmax = wave_max(L);
     const int Lmin = wave_min(L);
     if (Lmax == 0) {
@@ -348,6 +351,7 @@ __global__ void __launch_bounds__(256) flx_score_phred_direct(const PhredArgs a)
     if (slot >= a.n_reads) return;
     const uint32_t rid = a.order ? a.order[slot] : (uint32_t)slot;
     const int L = a.lengths[rid];
+    if (L >= a.long_thr) return;  // a long read's outputs are the cooperative path's
     const uint8_t *q = a.plane + a.offsets[rid];
     const int ws = a.ws;
     double s = 0.0, w = 0.0, mn = 0.0;
@@ -373,9 +377,70 @@ __global__ void __launch_bounds__(256) flx_score_phred_direct(const PhredArgs a)
 static constexpr size_t kLdsBudget = 160 * 1024;
 static constexpr size_t kLutBytes = 2 * LUT_PAD * sizeof(double);
 
+// *launched = false when the window does not fit the LDS ring (ws > ~2000)
+static int launch_ring(flx_ctx *ctx, PhredArgs a, bool *launched) {
+    const long long n_slots = ((long long)a.ws + CH - 1) / CH + 1;
+    long long slots16 = n_slots * CH / 16 + 1;  // + the 16-byte mirror behind the last slot
+    if ((slots16 & 1) == 0) slots16 += 1;       // odd number of 16-byte slots per row: b128 rows never collide
+    const size_t ring_bytes = (size_t)64 * slots16 * 16;
+    const int waves = (int)std::min<size_t>((kLdsBudget - kLutBytes) / ring_bytes, 7);
+    *launched = waves >= 1;
+    if (!*launched) return FLX_OK;
+    const uint64_t n_waves = (a.n_reads + 63) / 64;
+    a.n_slots = (int)n_slots;
+    a.stride = (int)(slots16 * 16);
+    const size_t lds = (size_t)waves * ring_bytes;  // dynamic part; the tables are static LDS
+    // persistent workgroups: as many as can be resident (LDS allows floor(budget / per-group) per CU), capped by the work
+    const unsigned per_cu = (unsigned)std::max<size_t>(1, kLdsBudget / (lds + kLutBytes));
+    const unsigned resident = (unsigned)ctx->prop.multiProcessorCount * per_cu;
+    const unsigned grid = (unsigned)std::min<uint64_t>((n_waves + waves - 1) / waves, resident);
+    void *scr;
+    FLX_CHECK(flx_scratch(ctx, 64, &scr));
+    FLX_HIP(ctx, hipMemsetAsync(scr, 0, 4, ctx->stream));
+    a.ticket = (unsigned int *)scr;
+    a.n_groups = (unsigned int)n_waves;
+#define FLX_LAUNCH_RING(W)                                                                                    \
+    case W: {                                                                                                 \
+        auto kern = flx_score_phred_ring<W>;                                                                  \
+        FLX_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,      \
+                                         (int)lds));                                                          \
+        ctx->last_phred_kernel = "flx_score_phred_ring";                                                      \
+        flx_time_begin(ctx, "flx_score_phred_ring");                                                          \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(W * 64), lds, ctx->stream, a);                              \
+        flx_time_end(ctx);                                                                                    \
+    } break;
+    switch (waves) {
+        FLX_LAUNCH_RING(1)
+        FLX_LAUNCH_RING(2)
+        FLX_LAUNCH_RING(3)
+        FLX_LAUNCH_RING(4)
+        FLX_LAUNCH_RING(5)
+        FLX_LAUNCH_RING(6)
+        FLX_LAUNCH_RING(7)
+    }
+#undef FLX_LAUNCH_RING
+    FLX_HIP(ctx, hipGetLastError());
+    return FLX_OK;
+}
+
+static int launch_direct(flx_ctx *ctx, const PhredArgs &a) {
+    const unsigned grid = (unsigned)((a.n_reads + 255) / 256);
+    ctx->last_phred_kernel = "flx_score_phred_direct";
+    flx_time_begin(ctx, "flx_score_phred_direct");
+    hipLaunchKernelGGL(flx_score_phred_direct, dim3(grid), dim3(256), 0, ctx->stream, a);
+    flx_time_end(ctx);
+    FLX_HIP(ctx, hipGetLastError());
+    return FLX_OK;
+}
+
+// One sequence for every kernel, with nothing waiting in front of the kernel: the detection counts the long reads, the batch kernel
+// runs over the whole batch and leaves reads of a.long_thr bases or more alone, the counts travel to the pinned buffer, and
+// flx_phred_finish acts on them after the scoring call's synchronisation.
 int flx_launch_score_phred(flx_ctx *ctx, const uint8_t *d_plane, uint64_t plane_bytes, const uint64_t *d_offsets,
                            const int32_t *d_lengths, const uint32_t *d_order, uint64_t n_reads,
                            const flx_params *p, flx_score_out_dev out) {
+    delete (PhredPending *)ctx->phred_pending;  // (a call that failed half way)
+    ctx->phred_pending = nullptr;
     if (n_reads == 0) return FLX_OK;
     if (p->window_size <= 0) return flx_fail(ctx, FLX_ERR_INVALID, "window_size must be positive");
     FLX_CHECK(flx_ensure_lut_d(ctx, p->window_size));
@@ -389,6 +454,8 @@ int flx_launch_score_phred(flx_ctx *ctx, const uint8_t *d_plane, uint64_t plane_
     a.lut_q = ctx->d_lut_q;
     a.lut_d = ctx->d_lut_d;
     a.ws = p->window_size;
+    a.n_slots = 0;
+    a.stride = 0;
     a.ws_d = (double)(size_t)p->window_size;
     {
         volatile double half = 0.5, wsd = a.ws_d;
@@ -403,90 +470,50 @@ int flx_launch_score_phred(flx_ctx *ctx, const uint8_t *d_plane, uint64_t plane_
     a.redo_count = nullptr;
     a.redo_list = nullptr;
     a.use_private = nullptr;
-    a.long_thr = 0x7fffffff;
 
-    const long long n_slots = ((long long)p->window_size + CH - 1) / CH + 1;
-    long long slots16 = n_slots * CH / 16 + 1;  // + the 16-byte mirror behind the last slot
-    if ((slots16 & 1) == 0) slots16 += 1;       // odd number of 16-byte slots per row: b128 rows never collide
-    const size_t ring_bytes = (size_t)64 * slots16 * 16;
+    PhredPending pd;
+    FLX_CHECK(flx_phred_long_detect(ctx, a, plane_bytes, &pd.lp));
+    a.long_thr = (int)std::min<long long>(flx_phred_long_threshold(ctx, &pd.lp, nullptr), 0x7fffffff);
+    pd.a = a;
+    void *pin;
+    FLX_CHECK(flx_pinned(ctx, 1024, &pin));
+    pd.h_flag = (unsigned int *)pin;
+    pd.h_counts = (unsigned long long *)((char *)pin + 64);
 
-    int waves = (int)((kLdsBudget - kLutBytes) / ring_bytes);
-    const char *env = getenv("FLX_PHRED_KERNEL");  // test hook: "direct" / "ring" force the older kernels
+    // default: the register-history kernel where the window size has an instantiation, the dual-slot kernel beyond (window sizes
+    // from 624 on, any size)
+    const char *env = getenv("FLX_PHRED_KERNEL");  // test hook: "direct" / "ring" / "stream" / "dual" force the other kernels
     const bool force_direct = env && strcmp(env, "direct") == 0;
     const bool force_ring = env && strcmp(env, "ring") == 0;
     const bool force_stream = env && strcmp(env, "stream") == 0;
     const bool force_dual = env && strcmp(env, "dual") == 0;
-    // Reads from a length threshold on are scored by the cooperative kernels of score_phred_long.hip; whichever kernel is chosen
-    // below gets the rest of the batch.  The register-history kernel makes the split after the synchronisation it takes anyway.
-    PhredLong lp;
-    FLX_CHECK(flx_phred_long_detect(ctx, a, plane_bytes, &lp));
-    if (force_stream || force_dual) {
-        FLX_CHECK(flx_phred_long_split(ctx, a, &lp));
-        if (a.n_reads == 0) return FLX_OK;
-        return force_stream ? flx_launch_score_phred_stream(ctx, a) : flx_launch_score_phred_dual(ctx, a);
-    }
-    if (!force_direct && !force_ring) {  // default: the register-history kernel, where the window size has an instantiation ...
-        bool launched = false;
-        a.n_slots = 0;
-        a.stride = 0;
-        FLX_CHECK(flx_launch_score_phred_regs(ctx, a, &launched, &lp));
-        if (launched) return FLX_OK;
-        FLX_CHECK(flx_phred_long_split(ctx, a, &lp));
-        if (a.n_reads == 0) return FLX_OK;
-        return flx_launch_score_phred_dual(ctx, a);  // ... and the dual-slot kernel beyond (window sizes from 624 on, any size)
-    }
-    FLX_CHECK(flx_phred_long_split(ctx, a, &lp));
-    if (a.n_reads == 0) return FLX_OK;
-    const uint64_t n_waves = (a.n_reads + 63) / 64;
-
-    if (waves >= 1 && !force_direct) {
-        if (waves > 7) waves = 7;
-        a.n_slots = (int)n_slots;
-        a.stride = (int)(slots16 * 16);
-        const size_t lds = (size_t)waves * ring_bytes;  // dynamic part; the tables are static LDS
-        // persistent workgroups: as many as can be resident (LDS allows floor(budget / per-group) per CU), capped by the work
-        const unsigned per_cu = (unsigned)std::max<size_t>(1, kLdsBudget / (lds + kLutBytes));
-        const unsigned resident = (unsigned)ctx->prop.multiProcessorCount * per_cu;
-        const unsigned grid = (unsigned)std::min<uint64_t>((n_waves + waves - 1) / waves, resident);
-        void *scr;
-        FLX_CHECK(flx_scratch(ctx, 64, &scr));
-        FLX_HIP(ctx, hipMemsetAsync(scr, 0, 4, ctx->stream));
-        a.ticket = (unsigned int *)scr;
-        a.n_groups = (unsigned int)n_waves;
-#define FLX_LAUNCH_RING(W)                                                                                    \
-    case W: {                                                                                                 \
-        auto kern = flx_score_phred_ring<W>;                                                                  \
-        FLX_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,      \
-                                         (int)lds));                                                          \
-        ctx->last_phred_kernel = "flx_score_phred_ring";                                                      \
-        flx_time_begin(ctx, "flx_score_phred_ring");                                                          \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(W * 64), lds, ctx->stream, a);                              \
-        flx_time_end(ctx);                                                                                    \
-    } break;
-        switch (waves) {
-            FLX_LAUNCH_RING(1)
-            FLX_LAUNCH_RING(2)
-            FLX_LAUNCH_RING(3)
-            FLX_LAUNCH_RING(4)
-            FLX_LAUNCH_RING(5)
-            FLX_LAUNCH_RING(6)
-            FLX_LAUNCH_RING(7)
-        }
-#undef FLX_LAUNCH_RING
-    } else if (!force_direct) {
-        // the window does not fit the LDS ring (ws > ~2000): both window edges streamed from global memory, 16-byte loads
-        return flx_launch_score_phred_stream(ctx, a);
+    bool launched = false;
+    if (force_direct) {
+        FLX_CHECK(launch_direct(ctx, a));
+    } else if (force_ring || force_stream) {
+        if (force_ring) FLX_CHECK(launch_ring(ctx, a, &launched));
+        if (!launched) FLX_CHECK(flx_launch_score_phred_stream(ctx, a));  // both window edges streamed from global memory
     } else {
-        a.n_slots = 0;
-        a.stride = 0;
-        a.ticket = nullptr;
-        a.n_groups = 0;
-        const unsigned grid = (unsigned)((a.n_reads + 255) / 256);
-        ctx->last_phred_kernel = "flx_score_phred_direct";
-        flx_time_begin(ctx, "flx_score_phred_direct");
-        hipLaunchKernelGGL(flx_score_phred_direct, dim3(grid), dim3(256), 0, ctx->stream, a);
-        flx_time_end(ctx);
+        if (!force_dual) FLX_CHECK(flx_launch_score_phred_regs(ctx, a, &launched, &pd));
+        if (!launched) FLX_CHECK(flx_launch_score_phred_dual(ctx, a));
     }
-    FLX_HIP(ctx, hipGetLastError());
+    if (pd.lp.on)
+        FLX_HIP(ctx, hipMemcpyAsync(pd.h_counts, pd.lp.d_counts, 3 * PHRED_LONG_NB * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    ctx->phred_pending = new PhredPending(pd);
+    return FLX_OK;
+}
+
+int flx_phred_finish(flx_ctx *ctx) {
+    std::unique_ptr<PhredPending> pd((PhredPending *)ctx->phred_pending);
+    ctx->phred_pending = nullptr;
+    if (!pd) return FLX_OK;
+    if (pd->chosen_on_device) {
+        ctx->last_phred_kernel = *pd->h_flag ? "flx_score_phred_regs_private" : "flx_score_phred_regs";
+        if (pd->timed_index >= 0 && (size_t)pd->timed_index < ctx->timed.size()) ctx->timed[pd->timed_index].name = ctx->last_phred_kernel;
+    }
+    bool scored = false;
+    FLX_CHECK(flx_phred_long_score(ctx, pd->a, pd->lp, pd->h_counts, &scored));
+    if (scored) FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return FLX_OK;
 }

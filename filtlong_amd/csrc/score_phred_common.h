@@ -1,5 +1,5 @@
-// score_phred_common.h — pieces shared by the Phred scoring kernels (score_phred.hip: LDS-ring and direct kernels;
-// score_phred_regs.hip: register-history kernel).
+// score_phred_common.h — pieces shared by the Phred scoring kernels (score_phred.hip: the dispatch, LDS-ring and direct kernels;
+// score_phred_regs.hip: register-history, stream, dual-slot and redo kernels; score_phred_long.hip: the cooperative path).
 #pragma once
 
 #include "flx_internal.h"
@@ -28,11 +28,11 @@ struct PhredArgs {
     unsigned int *ticket;  // ring kernel: next group of 64 reads (persistent waves)
     unsigned int n_groups; // ceil(n_reads / 64)
     unsigned int *redo_count;  // register kernel, bank-private tables: reads holding a byte >= 128 ...
-    uint32_t *redo_list;       // ... are re-scored by the direct kernel (their ids are appended here)
+    uint32_t *redo_list;       // ... are re-scored by the redo kernel (their ids are appended here)
     // register kernel, chosen on the device: both table variants are launched and the one *use_private does not name returns at
-    // once (NULL: this launch is the choice) ...
+    // once (NULL: this launch is the choice)
     const unsigned int *use_private;
-    int long_thr;  // ... and reads of at least this many bases are left to the cooperative path (INT_MAX: none)
+    int long_thr;  // every batch kernel: reads of at least this many bases are left to the cooperative path (INT_MAX: none)
 };
 
 __device__ __forceinline__ int wave_max(int v) {
@@ -97,13 +97,20 @@ constexpr int PHRED_LONG_NB = 13;                // length buckets of the detect
 constexpr long long PHRED_LONG_FLOOR = 1 << 18;  // the threshold's floor
 struct PhredLong {
     bool on = false;       // the detection kernel ran
-    bool fetched = false;  // its counts are copied to the host (valid after the next synchronisation of the stream)
-    bool done = false;     // the split has been made
     bool forced = false;   // FLX_PHRED_LONG_MIN gave the threshold
     int t0 = 0;            // the smallest threshold counted
     uint64_t plane_bytes = 0;  // stands for the batch's bases in the threshold
-    unsigned long long *d_counts = nullptr;
-    unsigned long long h_counts[3 * PHRED_LONG_NB] = {};
+    unsigned long long *d_counts = nullptr;  // [3 * PHRED_LONG_NB] reads, mean chunks, window chunks per length bucket
+};
+
+// What a Phred scoring call leaves for flx_phred_finish (score_phred.hip), which runs after the call's closing synchronisation.
+struct PhredPending {
+    PhredArgs a;  // the whole batch
+    PhredLong lp;
+    unsigned long long *h_counts;  // pinned: the detection's counts
+    unsigned int *h_flag;          // pinned: the table variant, if the device chose it
+    bool chosen_on_device = false;
+    long timed_index = -1;  // the bracket around both variants' launches (-1: timing is off)
 };
 
 }  // namespace flx_phred
@@ -112,18 +119,17 @@ struct PhredLong {
 int flx_phred_long_detect(flx_ctx *ctx, const flx_phred::PhredArgs &a, uint64_t plane_bytes, flx_phred::PhredLong *lp);
 // ... the length from which reads take that path (INT_MAX: the detection is off): known before any count is (*b0: its bucket) ...
 long long flx_phred_long_threshold(const flx_ctx *ctx, const flx_phred::PhredLong *lp, int *b0);
-// ... enqueues the copy of the counts (the caller synchronises the stream: one synchronisation serves both) ...
-int flx_phred_long_fetch(flx_ctx *ctx, flx_phred::PhredLong *lp);
-// ... and, when there are long reads, scores them on the context's stream and leaves in `a` the rest of the batch: a stably compacted
-// order of the other reads and their count (0: nothing is left for the Phred kernel).  Synchronises only if the counts are not
-// fetched yet; a no-op after the first call.
-int flx_phred_long_split(flx_ctx *ctx, flx_phred::PhredArgs &a, flx_phred::PhredLong *lp);
+// ... and, once the counts are on the host (h_counts), scores the long reads on the context's stream if there are any
+// (*scored; the batch kernel has left them alone).  Does not synchronise.
+int flx_phred_long_score(flx_ctx *ctx, const flx_phred::PhredArgs &a, const flx_phred::PhredLong &lp,
+                         const unsigned long long *h_counts, bool *scored);
 
-// score_phred_regs.hip: the register-history kernel.  *launched = false when the window size has no instantiation
-// (the caller then uses the LDS-ring kernel).  Nothing waits in front of the kernel: the table variant is chosen on the device, the
-// kernel skips the long reads itself, and what the host has to know (which variant ran, whether there are long reads to score)
-// comes back in the context's pinned buffer — flx_phred_finish, after the scoring call's synchronisation, acts on it.
-int flx_launch_score_phred_regs(flx_ctx *ctx, flx_phred::PhredArgs a, bool *launched, flx_phred::PhredLong *lp);
+// The batch kernels' launchers.  Each launches over the whole batch (the kernel skips reads of a.long_thr bases or more itself)
+// and nothing waits in front of it.
+// score_phred_regs.hip: the register-history kernel.  *launched = false when the window size has no instantiation (the caller
+// then uses the dual-slot kernel).  The table variant is chosen on the device unless FLX_PHRED_TABLES names it; which one ran
+// comes back in pd->h_flag with the scoring call's synchronisation (pd->chosen_on_device, pd->timed_index).
+int flx_launch_score_phred_regs(flx_ctx *ctx, flx_phred::PhredArgs a, bool *launched, flx_phred::PhredPending *pd);
 // score_phred_regs.hip: any window size, both window edges streamed from global memory (used where the LDS ring does not fit)
 int flx_launch_score_phred_stream(flx_ctx *ctx, flx_phred::PhredArgs a);
 // score_phred_regs.hip: any window size, the trailing edge as a second LDS-DMA stream (nothing of the window stays on chip)

@@ -3,7 +3,7 @@
 //
 // The default Phred kernels fold one read in one lane, strictly left to right, so a read's time grows with its length and gets no
 // help from the rest of the chip: a 4 Mbp read is a serial tail of tens of milliseconds.  Reads from a length threshold on
-// (flx_launch_score_phred picks it, see phred_long_split) are taken out of the batch and scored here, cut into chunks of 1024
+// (flx_launch_score_phred sets it, see flx_phred_long_threshold) are left alone by the batch kernel and scored here, cut into chunks of 1024
 // bases that all run in parallel, with the integer-grid algebra of stats.hip (fold_map.h):
 //
 //   mean fold     s += Q[byte]  (non-negative elements): per chunk an approximate sum, a per-read scan of those (a GUESS of the
@@ -43,7 +43,7 @@ constexpr int CHUNK = 64 * LANE_EL;     // bases per chunk (one wave)
 constexpr long long SAT = 1ll << 61;    // offsets saturate here: far outside any binade, and a sum of two never overflows
 constexpr long long NOSTEP = 1ll << 62; // WinSum::mf of a run without a full step
 constexpr long long M_LO = (1ll << 52) + 1, M_HI = (1ll << 53) - 1;  // the window's range test: one grid unit inside the binade
-constexpr int SLOT_BLOCKS = 1024;       // blocks of the stable split of the processing order
+constexpr int SLOT_BLOCKS = 1024;       // blocks of the stable compaction of the long reads' ids
 constexpr int MAX_OPEN = 16;            // lane-summary attempts in an opened chunk before the rest of it is folded serially ...
 constexpr int MAX_STALL = 2;            // ... or attempts that fitted fewer than MIN_ADVANCE lanes (a value that hovers at a
 constexpr int MIN_ADVANCE = 4;          // binade boundary: a lane summary costs ~30 serial steps)
@@ -185,7 +185,7 @@ __device__ __forceinline__ uint4 load16(const uint8_t *q, long long pos, int L) 
     return *reinterpret_cast<const uint4 *>(q + pos);  // inside the read's 16-byte padded span
 }
 
-// ---------------------------------------------------------------------------------------------------- detection and split
+// ---------------------------------------------------------------------------------------------------- detection and compaction
 // Counts, per length bucket (bucket b: lengths from t0 << b; one bucket when the threshold is given), the reads, their mean and
 // window chunks.  Layout of `out`: n[NB], mean chunks[NB], window chunks[NB].  Global atomics only for long reads: a batch without
 // any costs one pass over the lengths.
@@ -257,51 +257,37 @@ __device__ void block_exclusive_scan(const unsigned long long *in, unsigned long
     if (threadIdx.x == 0) out[n] = carry;
 }
 
-__global__ void __launch_bounds__(1024) flx_score_phred_long_scan(const uint32_t *blk, uint32_t *blk_off, uint32_t G,
-                                                                  unsigned long long *tmp) {
-    for (uint32_t i = threadIdx.x; i < G; i += 1024) tmp[i] = blk[i];
-    __syncthreads();
-    block_exclusive_scan(tmp, tmp + G + 1, G);
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i <= G; i += 1024) blk_off[i] = (uint32_t)tmp[G + 1 + i];
-}
-
-// stable split of the processing order: long reads -> ids (in order), the rest -> rest (in order)
-__global__ void __launch_bounds__(256) flx_score_phred_long_split(const int32_t *lengths, const uint32_t *order, uint64_t n,
-                                                                  uint64_t per, int thr, const uint32_t *blk_off, uint32_t *ids,
-                                                                  uint32_t *rest) {
-    __shared__ int wcount[4];
+// stable compaction of the processing order: the long reads' ids, in order (blk: the counts of flx_score_phred_long_count)
+__global__ void __launch_bounds__(256) flx_score_phred_long_compact(const int32_t *lengths, const uint32_t *order, uint64_t n,
+                                                                    uint64_t per, int thr, const uint32_t *blk, uint32_t *ids) {
+    __shared__ uint32_t wcount[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t c = 0;  // long reads before this block
+    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += 256) c += blk[i];
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) wcount[wave] = c;
+    __syncthreads();
+    uint64_t nl = (uint64_t)wcount[0] + wcount[1] + wcount[2] + wcount[3];
     const uint64_t s0 = (uint64_t)blockIdx.x * per, s1 = min(n, s0 + per);
-    uint64_t nl = blk_off[blockIdx.x];  // long reads before this tile
-    uint64_t nr = s0 - nl;              // other reads before this tile
     for (uint64_t t = s0; t < s1; t += 256) {
         const uint64_t slot = t + threadIdx.x;
-        const bool valid = slot < s1;
         uint32_t rid = 0;
         bool f = false;
-        if (valid) {
+        if (slot < s1) {
             rid = order ? order[slot] : (uint32_t)slot;
             f = lengths[rid] >= thr;
         }
         const unsigned long long m = __ballot(f);
-        const int below = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wcount[wave] = __popcll(m);
+        __syncthreads();  // (the previous tile's counts have been read)
+        if (lane == 0) wcount[wave] = (uint32_t)__popcll(m);
         __syncthreads();
-        int before = 0, tile = 0;
+        uint32_t before = 0, tile = 0;
         for (int w = 0; w < 4; ++w) {
             if (w < wave) before += wcount[w];
             tile += wcount[w];
         }
-        const int pos_long = before + below;                // long reads before this slot in the tile
-        if (valid) {
-            if (f) ids[nl + pos_long] = rid;
-            else rest[nr + (threadIdx.x - pos_long)] = rid;
-        }
-        const int n_valid = (int)min<uint64_t>(256, s1 - t);
+        if (f) ids[nl + before + __popcll(m & ((1ull << lane) - 1ull))] = rid;
         nl += tile;
-        nr += n_valid - tile;
-        __syncthreads();
     }
 }
 
@@ -730,19 +716,12 @@ int flx_phred_long_detect(flx_ctx *ctx, const PhredArgs &a, uint64_t plane_bytes
     FLX_CHECK(flx_workspace(ctx, 3, 4096, &w));
     lp->d_counts = (unsigned long long *)w;
     lp->t0 = (int)t0;
-    FLX_HIP(ctx, hipMemsetAsync(w, 0, sizeof lp->h_counts, ctx->stream));
+    FLX_HIP(ctx, hipMemsetAsync(w, 0, 3 * PHRED_LONG_NB * sizeof(unsigned long long), ctx->stream));
     const unsigned grid = (unsigned)std::min<uint64_t>((a.n_reads + 255) / 256, 2048);
     hipLaunchKernelGGL(flx_score_phred_long_find, dim3(grid), dim3(256), 0, ctx->stream, a.lengths, a.n_reads, a.ws, (int)t0,
                        lp->forced ? 1 : PHRED_LONG_NB, lp->d_counts);
     FLX_HIP(ctx, hipGetLastError());
     lp->on = true;
-    return FLX_OK;
-}
-
-int flx_phred_long_fetch(flx_ctx *ctx, PhredLong *lp) {
-    if (!lp || !lp->on || lp->fetched) return FLX_OK;
-    FLX_HIP(ctx, hipMemcpyAsync(lp->h_counts, lp->d_counts, sizeof lp->h_counts, hipMemcpyDeviceToHost, ctx->stream));
-    lp->fetched = true;  // valid after the caller's next synchronisation of the stream
     return FLX_OK;
 }
 
@@ -767,16 +746,11 @@ long long flx_phred_long_threshold(const flx_ctx *ctx, const PhredLong *lp, int 
     return thr;
 }
 
-int flx_phred_long_split(flx_ctx *ctx, PhredArgs &a, PhredLong *lp) {
-    if (!lp || !lp->on || lp->done) return FLX_OK;
-    lp->done = true;
-    if (!lp->fetched) {
-        FLX_CHECK(flx_phred_long_fetch(ctx, lp));
-        FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    const unsigned long long *h = lp->h_counts;
+int flx_phred_long_score(flx_ctx *ctx, const PhredArgs &a, const PhredLong &lp, const unsigned long long *h, bool *scored) {
+    *scored = false;
+    if (!lp.on) return FLX_OK;
     int b0 = 0;
-    const long long thr = flx_phred_long_threshold(ctx, lp, &b0);
+    const long long thr = flx_phred_long_threshold(ctx, &lp, &b0);
     unsigned long long k = 0, n_mean = 0, n_win = 0;
     for (int b = b0; b < PHRED_LONG_NB; ++b) {
         k += h[b];
@@ -792,13 +766,10 @@ int flx_phred_long_split(flx_ctx *ctx, PhredArgs &a, PhredLong *lp) {
     const uint64_t n = a.n_reads;
     const uint32_t G = (uint32_t)std::min<uint64_t>(SLOT_BLOCKS, (n + 1023) / 1024);
     const uint64_t per = (n + G - 1) / G;
-    const size_t scan_words = std::max<uint64_t>(G, k) + 1;
     size_t off = 4096;  // the counts
     const size_t o_blk = off; off = up256(off + (size_t)G * 4);
-    const size_t o_blk_off = off; off = up256(off + (size_t)(G + 1) * 4);
-    const size_t o_tmp = off; off = up256(off + 2 * scan_words * 8);
+    const size_t o_tmp = off; off = up256(off + 2 * (k + 1) * 8);
     const size_t o_ids = off; off = up256(off + k * 4);
-    const size_t o_rest = off; off = up256(off + (n - k) * 4 + 4);
     const size_t o_mbase = off; off = up256(off + (k + 1) * 4);
     const size_t o_wbase = off; off = up256(off + (k + 1) * 4);
     const size_t o_mread = off; off = up256(off + n_mean * 4);
@@ -829,7 +800,6 @@ int flx_phred_long_split(flx_ctx *ctx, PhredArgs &a, PhredLong *lp) {
     g.clean = (unsigned char *)(base + o_clean);
     g.mmeta = (MeanMeta *)(base + o_mmeta);
     g.wmeta = (WinMeta *)(base + o_wmeta);
-    uint32_t *rest = (uint32_t *)(base + o_rest);
     unsigned long long *tmp = (unsigned long long *)(base + o_tmp);
     hipStream_t st = ctx->stream;
 
@@ -837,10 +807,8 @@ int flx_phred_long_split(flx_ctx *ctx, PhredArgs &a, PhredLong *lp) {
         flx_time_scope ts(ctx, "flx_score_phred_long");
         hipLaunchKernelGGL(flx_score_phred_long_count, dim3(G), dim3(256), 0, st, a.lengths, a.order, n, per, (int)thr,
                            (uint32_t *)(base + o_blk));
-        hipLaunchKernelGGL(flx_score_phred_long_scan, dim3(1), dim3(1024), 0, st, (const uint32_t *)(base + o_blk),
-                           (uint32_t *)(base + o_blk_off), G, tmp);
-        hipLaunchKernelGGL(flx_score_phred_long_split, dim3(G), dim3(256), 0, st, a.lengths, a.order, n, per, (int)thr,
-                           (const uint32_t *)(base + o_blk_off), (uint32_t *)(base + o_ids), rest);
+        hipLaunchKernelGGL(flx_score_phred_long_compact, dim3(G), dim3(256), 0, st, a.lengths, a.order, n, per, (int)thr,
+                           (const uint32_t *)(base + o_blk), (uint32_t *)(base + o_ids));
         hipLaunchKernelGGL(flx_score_phred_long_index, dim3(1), dim3(1024), 0, st, a, g.ids, g.k, tmp, (uint32_t *)g.mbase,
                            (uint32_t *)g.wbase);
         const unsigned per_read_blocks = (unsigned)std::min<uint64_t>((k + 3) / 4, 4096);
@@ -857,8 +825,7 @@ int flx_phred_long_split(flx_ctx *ctx, PhredArgs &a, PhredLong *lp) {
         fprintf(stderr, "[flx_score_batch] %-22s %8.3f ms  (%llu reads of >= %lld bases, %llu + %llu chunks)\n", "phred long reads",
                 (t - t_start) * 1e3, k, thr, n_mean, n_win);
     }
-    a.order = rest;
-    a.n_reads = n - k;
-    if (a.n_reads == 0) ctx->last_phred_kernel = "flx_score_phred_long";
+    if (k == n) ctx->last_phred_kernel = "flx_score_phred_long";  // the batch kernel skipped every read
+    *scored = true;
     return FLX_OK;
 }

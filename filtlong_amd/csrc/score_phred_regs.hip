@@ -18,7 +18,7 @@
 //   * optional bank-private tables (FLX_PHRED_TABLES=private): every table entry is replicated once per bank pair
 //     (lane l reads copy l % 32), so a gather never has a bank conflict whatever the quality distribution is
 //     (plain tables: entries e and e+32 collide; a wide Phred range costs up to 1.5x per gather).  128 entries per
-//     table; a read containing a byte >= 128 (not a FASTQ character) is flagged and re-scored by the direct kernel.
+//     table; a read containing a byte >= 128 (not a FASTQ character) is flagged and re-scored by the redo kernel.
 //
 // The window size enters as A = ws / 16 (template parameter: it fixes which ring pieces hold the trailing edge)
 // and B = ws % 16.  B is a run-time value in the 39 x 2 generic instantiations (BS = -1): the 16 trailing bytes of a piece
@@ -424,15 +424,17 @@ __global__ void __launch_bounds__(1024) flx_score_phred_stream(const PhredArgs a
         group = (unsigned int)__builtin_amdgcn_readfirstlane((int)group);
         if (group >= a.n_groups) break;
         const uint64_t gslot = (uint64_t)group * 64 + lane;
-        const bool live = gslot < a.n_reads;
+        const bool slot_used = gslot < a.n_reads;
         uint32_t rid = 0;
         int L = 0;
         uint64_t base = 0;
-        if (live) {
+        if (slot_used) {
             rid = a.order ? a.order[gslot] : (uint32_t)gslot;
             L = a.lengths[rid];
             base = a.offsets[rid];
         }
+        const bool live = slot_used && L < a.long_thr;  // a long read's outputs are the cooperative path's
+        if (!live) L = 0;
         const int Lmax = wave_max(L);
         if (Lmax == 0) {
             if (live) finish_read(a, rid, L, 0.0, 0.0);
@@ -560,15 +562,17 @@ __global__ void __launch_bounds__(DUAL_WAVES * 64) flx_score_phred_dual(const Ph
         group = (unsigned int)__builtin_amdgcn_readfirstlane((int)group);
         if (group >= a.n_groups) break;
         const uint64_t gslot = (uint64_t)group * 64 + lane;
-        const bool live = gslot < a.n_reads;
+        const bool slot_used = gslot < a.n_reads;
         uint32_t rid = 0;
         int L = 0;
         uint64_t base = 0;
-        if (live) {
+        if (slot_used) {
             rid = a.order ? a.order[gslot] : (uint32_t)gslot;
             L = a.lengths[rid];
             base = a.offsets[rid];
         }
+        const bool live = slot_used && L < a.long_thr;  // a long read's outputs are the cooperative path's
+        if (!live) L = 0;
         const int Lmax = wave_max(L);
         const int Lmin = wave_min(L);
         if (Lmax == 0) {
@@ -764,9 +768,8 @@ int launch_one(flx_ctx *ctx, PhredArgs &a) {
     return FLX_OK;
 }
 
-// waves per CU: 16 (4 per SIMD, <= 128 VGPRs) for rings of up to 12 pieces, 12 (<= 168 VGPRs) up to 20 pieces, 8 (<= 256) up to
-// 43 pieces, 4 beyond (one wave per SIMD: the ring spills into the accumulator half of the unified register file, up to
-// 256 + 102 registers at ws = 1007); the bank-private tables (66 KB) leave room for 11 slots of 8 KiB
+// waves per CU: 16 (4 per SIMD, <= 128 VGPRs) for rings of up to 12 pieces, 12 (<= 168 VGPRs) up to 20 pieces, 8 (<= 256) for
+// the larger rings (44 pieces at A = 38, the last instantiation); the bank-private tables (66 KB) leave room for 11 slots of 8 KiB
 template <int A, bool PRIV>
 struct WavesFor {
     static constexpr int plain = A <= 7 ? 16 : A <= 15 ? 12 : 8;
@@ -786,69 +789,36 @@ int launch_a(flx_ctx *ctx, PhredArgs &a, bool priv, int bs) {
     }
 }
 
+// launches the instantiation of a.ws / 16, if it is one of A .. A_END - 1
+template <int A, int A_END>
+int launch_range(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
+    if constexpr (A < A_END) {
+        if (a.ws / 16 != A) return launch_range<A + 1, A_END>(ctx, a, priv, bs, launched);
+        *launched = true;
+        return launch_a<A>(ctx, a, priv, bs);
+    }
+    return FLX_OK;
+}
+
 }  // namespace
 
-// The instantiations (window sizes 1..1007, A = ws / 16 = 0..62) are spread over fourteen translation units of this same file
-// (-DFLX_REGS_PART=0..13, see the Makefile) so that they compile in parallel.  Rings beyond 36 pieces (A >= 32) need
-// -mllvm -unroll-max-upperbound (the prologue loop has an early exit: LLVM unrolls such loops only up to 8 iterations by
+// The instantiations (window sizes 1..623, A = ws / 16 = 0..38; beyond them a ring leaves room for one wave per SIMD only, and the
+// dual-slot kernel is faster) are spread over eight translation units of this same file (-DFLX_REGS_PART=0..7, see the Makefile)
+// so that they compile in parallel: part P holds A = kPartFirstA[P] .. kPartFirstA[P + 1] - 1.  Rings beyond 36 pieces (A >= 32)
+// need -mllvm -unroll-max-upperbound (the prologue loop has an early exit: LLVM unrolls such loops only up to 8 iterations by
 // default, and a ring that is not indexed statically everywhere ends up in scratch memory) and larger unroll thresholds.
-#define FLX_REGS_CASE(AA) \
-    case AA:              \
-        *launched = true; \
-        return launch_a<AA>(ctx, a, priv, bs);
+#define FLX_REGS_PARTS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
+constexpr int kPartFirstA[] = {0, 8, 13, 18, 23, 28, 32, 36, 39};
+
+#define FLX_REGS_PART_DECL(P) int flx_launch_score_phred_regs_part##P(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
+FLX_REGS_PARTS(FLX_REGS_PART_DECL)
 #define FLX_REGS_CAT2(a, b) a##b
 #define FLX_REGS_CAT(a, b) FLX_REGS_CAT2(a, b)
-#define FLX_REGS_WIDE_NAME FLX_REGS_CAT(flx_launch_score_phred_regs_part, FLX_REGS_PART)
-#if FLX_REGS_PART == 0
-int flx_launch_score_phred_regs_part0(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
-    switch (a.ws / 16) { FLX_REGS_CASE(0) FLX_REGS_CASE(1) FLX_REGS_CASE(2) FLX_REGS_CASE(3) FLX_REGS_CASE(4) FLX_REGS_CASE(5) FLX_REGS_CASE(6) FLX_REGS_CASE(7) default: return FLX_OK; }
+int FLX_REGS_CAT(flx_launch_score_phred_regs_part, FLX_REGS_PART)(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
+    return launch_range<kPartFirstA[FLX_REGS_PART], kPartFirstA[FLX_REGS_PART + 1]>(ctx, a, priv, bs, launched);
 }
-#elif FLX_REGS_PART == 1
-int flx_launch_score_phred_regs_part1(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
-    switch (a.ws / 16) { FLX_REGS_CASE(8) FLX_REGS_CASE(9) FLX_REGS_CASE(10) FLX_REGS_CASE(11) FLX_REGS_CASE(12) default: return FLX_OK; }
-}
-#elif FLX_REGS_PART == 2
-int flx_launch_score_phred_regs_part2(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
-    switch (a.ws / 16) { FLX_REGS_CASE(13) FLX_REGS_CASE(14) FLX_REGS_CASE(15) FLX_REGS_CASE(16) FLX_REGS_CASE(17) default: return FLX_OK; }
-}
-#elif FLX_REGS_PART == 3
-int flx_launch_score_phred_regs_part3(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
-    switch (a.ws / 16) { FLX_REGS_CASE(18) FLX_REGS_CASE(19) FLX_REGS_CASE(20) FLX_REGS_CASE(21) FLX_REGS_CASE(22) default: return FLX_OK; }
-}
-#elif FLX_REGS_PART == 4
-int flx_launch_score_phred_regs_part4(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
-    switch (a.ws / 16) { FLX_REGS_CASE(23) FLX_REGS_CASE(24) FLX_REGS_CASE(25) FLX_REGS_CASE(26) FLX_REGS_CASE(27) default: return FLX_OK; }
-}
-#elif FLX_REGS_PART == 5
-int flx_launch_score_phred_regs_part5(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
-    switch (a.ws / 16) { FLX_REGS_CASE(28) FLX_REGS_CASE(29) FLX_REGS_CASE(30) FLX_REGS_CASE(31) default: return FLX_OK; }
-}
-#else
-// parts 6 and 7: A = 32..35 and 36..38: window sizes 512..623 (beyond them a ring leaves room for one wave per SIMD only, and the
-// dual-slot kernel is faster)
-int FLX_REGS_WIDE_NAME(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched) {
-    constexpr int A0 = 32 + 4 * (FLX_REGS_PART - 6);
-    switch (a.ws / 16) {
-        FLX_REGS_CASE(A0) FLX_REGS_CASE(A0 + 1) FLX_REGS_CASE(A0 + 2)
-#if FLX_REGS_PART < 7
-        FLX_REGS_CASE(A0 + 3)
-#endif
-        default: return FLX_OK;
-    }
-}
-#endif
-#undef FLX_REGS_CASE
 
 #if FLX_REGS_PART == 0
-int flx_launch_score_phred_regs_part1(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
-int flx_launch_score_phred_regs_part2(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
-int flx_launch_score_phred_regs_part3(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
-int flx_launch_score_phred_regs_part4(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
-int flx_launch_score_phred_regs_part5(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
-#define FLX_REGS_DECL(P) int flx_launch_score_phred_regs_part##P(flx_ctx *ctx, PhredArgs &a, bool priv, int bs, bool *launched);
-FLX_REGS_DECL(6) FLX_REGS_DECL(7)
-#undef FLX_REGS_DECL
-
 namespace {
 // Which table layout?  Plain tables are ~6 % faster when a wavefront's quality values stay within ~32 consecutive table
 // entries; bank-private tables cost the same whatever the data is and win (by up to ~11 %) on a wide quality range, where
@@ -892,15 +862,6 @@ __global__ void __launch_bounds__(256) flx_phred_sample(const PhredArgs a, unsig
     *use_private = (!high && 496.0 * conflicts > 3.0) ? 1u : 0u;  // bytes >= 128 would all go through the redo path: stay plain
 }
 
-// what flx_phred_finish needs once the scoring call's synchronisation has passed
-struct PhredPending {
-    PhredArgs a;       // the whole batch, as the kernel got it
-    PhredLong lp;
-    bool chosen_on_device;
-    long timed_index;  // the bracket around both launches (-1: timing is off)
-    const unsigned int *h_flag;
-    const unsigned long long *h_counts;
-};
 }  // namespace
 
 int flx_launch_score_phred_stream(flx_ctx *ctx, PhredArgs a) {
@@ -944,10 +905,11 @@ int flx_launch_score_phred_dual(flx_ctx *ctx, PhredArgs a) {
     return FLX_OK;
 }
 
-int flx_launch_score_phred_regs(flx_ctx *ctx, PhredArgs a, bool *launched, PhredLong *lp) {
+int flx_launch_score_phred_regs(flx_ctx *ctx, PhredArgs a, bool *launched, PhredPending *pd) {
     *launched = false;
     const int A = a.ws / 16;
-    if (A > 38) return FLX_OK;  // the register-history kernel serves window sizes 1 .. 623 (A = ws / 16 = 0 .. 38); beyond: the dual-slot kernel
+    constexpr int n_parts = (int)(sizeof kPartFirstA / sizeof kPartFirstA[0]) - 1;
+    if (A >= kPartFirstA[n_parts]) return FLX_OK;  // window sizes from 624 on: the dual-slot kernel
     const char *env = getenv("FLX_PHRED_TABLES");  // "plain" | "private" | unset = decided on the device from a sample of the data
     bool priv = env && strcmp(env, "private") == 0;
     bool forced = env && (strcmp(env, "private") == 0 || strcmp(env, "plain") == 0);
@@ -959,14 +921,10 @@ int flx_launch_score_phred_regs(flx_ctx *ctx, PhredArgs a, bool *launched, Phred
     if (fenv && *fenv && strcmp(fenv, "runtime") != 0)
         return flx_fail(ctx, FLX_ERR_INVALID, "FLX_PHRED_FUNNEL=%s: expected runtime (or unset)", fenv);
     const int bs = (a.ws == 250 && !(fenv && *fenv)) ? 10 : -1;
-    delete (PhredPending *)ctx->phred_pending;  // (a call that failed half way)
-    ctx->phred_pending = nullptr;
     // scratch: [0,4) ticket, [4,8) redo count, [8,12) sample workgroups done, [12,16) the choice, [64, 1088) sample histogram,
     // [2048, 2048 + 4 n) redo list
     void *scr;
     FLX_CHECK(flx_scratch(ctx, 2048 + a.n_reads * 4, &scr));
-    void *pin;
-    FLX_CHECK(flx_pinned(ctx, 1024, &pin));
     a.ticket = (unsigned int *)scr;
     a.redo_count = (unsigned int *)scr + 1;
     a.redo_list = (uint32_t *)((char *)scr + 2048);
@@ -977,20 +935,14 @@ int flx_launch_score_phred_regs(flx_ctx *ctx, PhredArgs a, bool *launched, Phred
                            (unsigned int *)scr + 2, d_flag);
         a.use_private = d_flag;
     }
-    // long reads: the kernel leaves them out by their length; whether there are any is looked at after the call's synchronisation
-    a.long_thr = (int)std::min<long long>(flx_phred_long_threshold(ctx, lp, nullptr), 0x7fffffff);
     a.n_groups = (unsigned int)((a.n_reads + 63) / 64);
-    auto part = [&](bool pv) -> int {
-        if (A <= 7) return flx_launch_score_phred_regs_part0(ctx, a, pv, bs, launched);
-        if (A <= 12) return flx_launch_score_phred_regs_part1(ctx, a, pv, bs, launched);
-        if (A <= 17) return flx_launch_score_phred_regs_part2(ctx, a, pv, bs, launched);
-        if (A <= 22) return flx_launch_score_phred_regs_part3(ctx, a, pv, bs, launched);
-        if (A <= 27) return flx_launch_score_phred_regs_part4(ctx, a, pv, bs, launched);
-        if (A <= 31) return flx_launch_score_phred_regs_part5(ctx, a, pv, bs, launched);
-        typedef int (*part_fn)(flx_ctx *, PhredArgs &, bool, int, bool *);
-        static const part_fn wide[2] = {flx_launch_score_phred_regs_part6, flx_launch_score_phred_regs_part7};
-        return wide[(A - 32) / 4](ctx, a, false, bs, launched);
-    };
+    typedef int (*part_fn)(flx_ctx *, PhredArgs &, bool, int, bool *);
+#define FLX_REGS_PART_NAME(P) flx_launch_score_phred_regs_part##P,
+    static const part_fn parts[n_parts] = {FLX_REGS_PARTS(FLX_REGS_PART_NAME)};
+#undef FLX_REGS_PART_NAME
+    int P = 0;
+    while (A >= kPartFirstA[P + 1]) ++P;
+    auto part = [&](bool pv) { return parts[P](ctx, a, pv, bs, launched); };
     long timed_index = -1;
     if (forced) {
         FLX_CHECK(part(priv));
@@ -1008,40 +960,11 @@ int flx_launch_score_phred_regs(flx_ctx *ctx, PhredArgs a, bool *launched, Phred
         flx_time_end(ctx);
         FLX_HIP(ctx, hipGetLastError());
     }
-    PhredPending *pd = new PhredPending();
-    pd->a = a;
-    pd->lp = *lp;
-    pd->chosen_on_device = !forced;
-    pd->timed_index = timed_index;
-    pd->h_flag = (const unsigned int *)pin;
-    pd->h_counts = (const unsigned long long *)((char *)pin + 64);
-    ctx->phred_pending = pd;
-    if (!forced) FLX_HIP(ctx, hipMemcpyAsync(pin, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (lp->on) FLX_HIP(ctx, hipMemcpyAsync((char *)pin + 64, lp->d_counts, sizeof lp->h_counts, hipMemcpyDeviceToHost, ctx->stream));
-    lp->done = true;  // (the caller's own split has nothing left to do)
-    return FLX_OK;
-}
-
-int flx_phred_finish(flx_ctx *ctx) {
-    PhredPending *pd = (PhredPending *)ctx->phred_pending;
-    if (!pd) return FLX_OK;
-    ctx->phred_pending = nullptr;
-    struct Free {
-        PhredPending *p;
-        ~Free() { delete p; }
-    } guard{pd};
-    if (pd->chosen_on_device) {
-        ctx->last_phred_kernel = *pd->h_flag ? "flx_score_phred_regs_private" : "flx_score_phred_regs";
-        if (pd->timed_index >= 0 && (size_t)pd->timed_index < ctx->timed.size()) ctx->timed[pd->timed_index].name = ctx->last_phred_kernel;
+    if (!forced) {
+        pd->chosen_on_device = true;
+        pd->timed_index = timed_index;
+        FLX_HIP(ctx, hipMemcpyAsync(pd->h_flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (!pd->lp.on) return FLX_OK;
-    memcpy(pd->lp.h_counts, pd->h_counts, sizeof pd->lp.h_counts);
-    pd->lp.fetched = true;
-    const uint64_t n0 = pd->a.n_reads;
-    PhredArgs a = pd->a;
-    a.use_private = nullptr;
-    FLX_CHECK(flx_phred_long_split(ctx, a, &pd->lp));  // scores the long reads, if there are any, exactly as ever
-    if (a.n_reads != n0) FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return FLX_OK;
 }
 #endif

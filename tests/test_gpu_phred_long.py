@@ -1,7 +1,7 @@
 """Phred scoring of very long reads, many lanes per read (score_phred_long.hip) — bit-identical to the oracle and the reference binary.
 
 Reads from a length threshold on (2^18 bases or more, raised with the batch's bases per lane; FLX_PHRED_LONG_MIN=N forces N, 0 turns
-the path off) are taken out of the batch and folded cooperatively; the rest of the batch goes to the kernel FLX_PHRED_KERNEL selects.
+the path off) are left alone by the batch kernel and folded cooperatively; the kernel FLX_PHRED_KERNEL selects scores the rest of the batch.
 Whether the path ran is visible in flx_timing_get under the prefix "flx_score_phred_long".
 """
 import os
@@ -123,7 +123,7 @@ def adversarial_reads(ws):
 
 
 @pytest.mark.parametrize("ws", [1, 7, 250, 1024, 5000])
-@pytest.mark.parametrize("kernel", ["default", "dual"])
+@pytest.mark.parametrize("kernel", KERNELS)
 def test_adversarial_data_through_the_path(ctx, ws, kernel, monkeypatch):
     monkeypatch.setenv("FLX_PHRED_LONG_MIN", "1000")
     set_kernel(monkeypatch, kernel)
@@ -132,6 +132,127 @@ def test_adversarial_data_through_the_path(ctx, ws, kernel, monkeypatch):
         got, want, launches = score_both(ctx, quals, dict(window_size=ws, min_length=1000, min_window_q=20.0), order)
         assert_same(got, want, "ws=%d %s" % (ws, order))
         assert launches > 0
+
+
+SKIP_WINDOWS = [7, 250, 700]  # 700 takes the dual-slot kernel by default
+SKIP_ORDERS = (None, "random", "desc")
+
+
+def skip_batch(ws, empties):
+    """130 reads, two full waves and a tail of two, around a long threshold of 1000 bases.  In file order: a wave that mixes long, short
+    and (with `empties`) empty reads, a wave of long reads only, a tail without a long read.  In descending order: a wave of long reads
+    only, a wave with the other long reads, short ones and an empty one, a tail of two empty reads."""
+    rng = np.random.default_rng(ws)
+    lens = [0, 1, ws - 1, ws, ws + 1, 999, 1000, 1001, 0, 0]
+    lens += [int(rng.integers(1000, 4000)) if i % 3 == 0 else int(rng.integers(2, 1000)) for i in range(54)]
+    lens += [1000, 1001] + [int(L) for L in rng.integers(1000, 5000, 62)]
+    lens += [500, 37]
+    if not empties:
+        lens = [L if L else 2 + i % 5 for i, L in enumerate(lens)]
+    quals = [ont_qual(L, 7000 + i) if L else b"" for i, L in enumerate(lens)]
+    for i in (5, 70):  # a byte >= 128 in a short and in a long read: the bank-private tables' redo list must not name a skipped read
+        r = np.frombuffer(quals[i], dtype=np.uint8).copy()
+        r[len(r) // 2] = 200
+        quals[i] = r.tobytes()
+    assert len(quals) == 130
+    return quals
+
+
+def wave_kinds(lengths, order, thr):
+    """Per wave of 64 slots of the processing order: "long" (long reads only), "none", or "mixed" (long and other reads; "mixed+empty"
+    if an empty read is among them)."""
+    L = np.asarray(lengths)[order if order is not None else np.arange(len(lengths))]
+    kinds = []
+    for w in range(0, len(L), 64):
+        lw = L[w:w + 64]
+        n_long = int((lw >= thr).sum())
+        kinds.append("long" if n_long == len(lw) else "none" if n_long == 0 else "mixed+empty" if (lw == 0).any() else "mixed")
+    return kinds
+
+
+def score_dev(ctx, packed, ws, order):
+    """score_reads_dev over outputs pre-filled with sentinels (-1.0, -1.0, 7)."""
+    import torch
+    plane, offsets, lengths = packed
+    n = len(lengths)
+    d_plane = torch.from_numpy(plane).cuda()
+    d_off = torch.from_numpy(offsets.view(np.int64)).cuda()
+    d_len = torch.from_numpy(lengths).cuda()
+    d_ord = torch.from_numpy(order.view(np.int32)).cuda() if order is not None else None
+    mean = torch.full((n,), -1.0, dtype=torch.float64, device="cuda")
+    win = torch.full((n,), -1.0, dtype=torch.float64, device="cuda")
+    ok = torch.full((n,), 7, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    ctx.score_reads_dev(d_plane.data_ptr(), len(plane), d_off.data_ptr(), d_len.data_ptr(), d_ord.data_ptr() if order is not None else None,
+                        n, api.make_params(window_size=ws, min_length=200, min_window_q=30.0), mean.data_ptr(), win.data_ptr(), ok.data_ptr())
+    torch.cuda.synchronize()
+    return {"mean_q": mean.cpu().numpy(), "window_q": win.cpu().numpy(), "passed": ok.cpu().numpy(), "kernel": ctx.last_phred_kernel()}
+
+
+def assert_no_sentinel(got, what):
+    assert not (bits(got["mean_q"]) == bits([-1.0])[0]).any(), what + ": a mean was not written"
+    assert not (bits(got["window_q"]) == bits([-1.0])[0]).any(), what + ": a window quality was not written"
+    assert (got["passed"] <= 1).all(), what + ": a pass flag was not written"
+
+
+@pytest.fixture(scope="module")
+def skip_cases(ctx):
+    """Per (window, empties): the packed batch, its three processing orders and the reference, FLX_PHRED_KERNEL=direct with the
+    cooperative path off (one lane per read, byte by byte)."""
+    cases = {}
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("FLX_PHRED_KERNEL", "direct")
+        mp.setenv("FLX_PHRED_LONG_MIN", "0")
+        for ws in SKIP_WINDOWS:
+            for empties in (True, False):
+                packed = api.pack_reads(skip_batch(ws, empties))
+                lengths = packed[2]
+                orders = {None: None, "random": np.random.default_rng(ws).permutation(len(lengths)).astype(np.uint32),
+                          "desc": api.length_order(lengths)}
+                want = score_dev(ctx, packed, ws, None)
+                assert want["kernel"] == "flx_score_phred_direct"
+                assert_no_sentinel(want, "reference ws=%d" % ws)
+                cases[ws, empties] = (packed, orders, want)
+    return cases
+
+
+@pytest.mark.parametrize("ws", SKIP_WINDOWS)
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_skip_inside_a_wave(ctx, skip_cases, kernel, ws, monkeypatch):
+    """The batch kernel leaves the long reads of a wave alone and scores the others, empty ones included; the cooperative path writes
+    the long ones: every field bit-identical to the direct kernel with the path off, no sentinel survives, an empty read has its NaN
+    mean.  File order and descending order each hold a wave of long reads only, a wave without one and a wave that mixes long,
+    short and empty reads; the random order mixes every full wave."""
+    packed, orders, want = skip_cases[ws, True]
+    lengths = packed[2]
+    assert sorted(wave_kinds(lengths, orders[None], 1000)) == ["long", "mixed+empty", "none"]
+    assert sorted(wave_kinds(lengths, orders["desc"], 1000)) == ["long", "mixed+empty", "none"]
+    assert set(wave_kinds(lengths, orders["random"], 1000)[:2]) <= {"mixed", "mixed+empty"}
+    monkeypatch.setenv("FLX_PHRED_LONG_MIN", "1000")
+    set_kernel(monkeypatch, kernel)
+    for name in SKIP_ORDERS:
+        what = "%s ws=%d order=%s" % (kernel, ws, name)
+        got = score_dev(ctx, packed, ws, orders[name])
+        assert_no_sentinel(got, what)
+        assert_same(got, want, what)
+        assert np.isnan(got["mean_q"][lengths == 0]).all() and (lengths == 0).sum() == 3, what
+        assert got["kernel"] != "flx_score_phred_long", what
+
+
+@pytest.mark.parametrize("ws", SKIP_WINDOWS)
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_every_read_skipped(ctx, skip_cases, kernel, ws, monkeypatch):
+    """The same batch without its empty reads, every read long: the batch kernel is launched and writes nothing."""
+    packed, orders, want = skip_cases[ws, False]
+    assert (packed[2] >= 1).all()
+    monkeypatch.setenv("FLX_PHRED_LONG_MIN", "1")
+    set_kernel(monkeypatch, kernel)
+    for name in SKIP_ORDERS:
+        what = "%s ws=%d order=%s all long" % (kernel, ws, name)
+        got = score_dev(ctx, packed, ws, orders[name])
+        assert_no_sentinel(got, what)
+        assert_same(got, want, what)
+        assert got["kernel"] == "flx_score_phred_long", what
 
 
 @pytest.fixture(scope="module")
