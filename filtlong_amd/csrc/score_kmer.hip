@@ -1467,26 +1467,43 @@ static bool build_grid_table(int ws, GridTab &g) {
     return pays;
 }
 
+// The timing bracket of a fold launch says which form ran: flx_score_kmer_fold.m<MODE>.<ring<R> | global>.<fp | grid>.  Every name is
+// a static string (the context keeps the pointer) and complete, so none is a prefix of another; flx_timing_get("flx_score_kmer_fold")
+// still sums all of them — one bracket per launch, none nested, so that sum is the device time of the folds.
+#define FLX_FOLD_NAMES_PATH(m, path) {"flx_score_kmer_fold.m" #m "." path ".fp", "flx_score_kmer_fold.m" #m "." path ".grid"}
+#define FLX_FOLD_NAMES_MODE(m)                                                                                         \
+    {FLX_FOLD_NAMES_PATH(m, "ring32"), FLX_FOLD_NAMES_PATH(m, "ring64"), FLX_FOLD_NAMES_PATH(m, "ring128"),            \
+     FLX_FOLD_NAMES_PATH(m, "ring256"), FLX_FOLD_NAMES_PATH(m, "ring512"), FLX_FOLD_NAMES_PATH(m, "global")}
+static const char *const kFoldTimingNames[7][6][2] = {FLX_FOLD_NAMES_MODE(0), FLX_FOLD_NAMES_MODE(1), FLX_FOLD_NAMES_MODE(2), FLX_FOLD_NAMES_MODE(3),
+                                                      FLX_FOLD_NAMES_MODE(4), FLX_FOLD_NAMES_MODE(5), FLX_FOLD_NAMES_MODE(6)};
+#undef FLX_FOLD_NAMES_MODE
+#undef FLX_FOLD_NAMES_PATH
+
 template <int MODE>
 static int launch_fold(flx_ctx *ctx, FoldArgs &a) {
-    int R = 32;
-    while (R < (MODE == 6 ? 24 : 18) + (a.ws + 31) / 32) R *= 2;  // MODE 6 starts up to 4 words into its first block, and reads one word further
+    int R = 32, path = 0;  // path: 0..4 = the ring of 32 << path words, 5 = global streams
+    while (R < (MODE == 6 ? 24 : 18) + (a.ws + 31) / 32) R *= 2, ++path;  // MODE 6 starts up to 4 words into its first block, and reads one word further
     const char *env = getenv("FLX_KMER_FOLD_STREAMS");  // "global": the round-2 data path (second implementation, tests)
     const bool ring = R <= 512 && !(env && strcmp(env, "global") == 0);
+    if (!ring) path = 5;
     const unsigned threads = (!ring || R <= 64) ? 256u : 64u;
     const unsigned nb = (unsigned)(((MODE == 6 ? a.n_children : a.n_reads) + threads - 1) / threads);
     a.ring_words = R;
-    if (ring && a.grid && !a.events && (MODE == 0 || MODE == 3 || MODE == 6)) {  // the steady state on the integer grid (GridTab)
+    const bool grid = ring && a.grid && !a.events && (MODE == 0 || MODE == 3 || MODE == 6);  // the steady state on the integer grid (GridTab)
+    if (grid) {
         constexpr int M = (MODE == 0 || MODE == 3 || MODE == 6) ? MODE : 0;
         ctx->last_kmer_fold_grid = true;
         const size_t lds = (size_t)(threads / 64) * (size_t)R * 256 + 2048 * FLX_FOLD_WALK_COPIES + 1024;
         FLX_HIP(ctx, hipFuncSetAttribute((const void *)k_kmer_fold<M, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        flx_time_scope tf(ctx, kFoldTimingNames[MODE][path][1]);
         hipLaunchKernelGGL((k_kmer_fold<M, true, true>), dim3(nb), dim3(threads), lds, ctx->stream, a);
     } else if (ring) {
         const size_t lds = (size_t)(threads / 64) * (size_t)R * 256;
         FLX_HIP(ctx, hipFuncSetAttribute((const void *)k_kmer_fold<MODE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        flx_time_scope tf(ctx, kFoldTimingNames[MODE][path][0]);
         hipLaunchKernelGGL((k_kmer_fold<MODE, true>), dim3(nb), dim3(threads), lds, ctx->stream, a);
     } else {
+        flx_time_scope tf(ctx, kFoldTimingNames[MODE][path][0]);
         hipLaunchKernelGGL((k_kmer_fold<MODE, false>), dim3(nb), dim3(threads), 0, ctx->stream, a);
     }
     FLX_HIP(ctx, hipGetLastError());  // (a launch that fails must not pass for a kernel that wrote nothing)
@@ -1625,11 +1642,9 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
     a.child_window_q = out->child_window_q;
     a.child_passed = out->child_passed;
 
+    // (every fold launch opens its own timing bracket: launch_fold)
     if (!want_children) {
-        {
-            flx_time_scope tf(ctx, "flx_score_kmer_fold");
-            FLX_CHECK(launch_fold<0>(ctx, a));
-        }
+        FLX_CHECK(launch_fold<0>(ctx, a));
         if (out->child_offsets) FLX_HIP(ctx, hipMemsetAsync(out->child_offsets, 0, (n_reads + 1) * 8, st));
         FLX_HIP(ctx, hipGetLastError());
         FLX_HIP(ctx, hipStreamSynchronize(st));
@@ -1641,13 +1656,10 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
     // FLX_KMER_FOLD=bits forces the bit-level passes (tests compare the two implementations on every read)
     const char *fold_env = getenv("FLX_KMER_FOLD");
     const bool bit_level = (params->split_set && params->split < 32) || (fold_env && strcmp(fold_env, "bits") == 0);
-    {
-        flx_time_scope tf(ctx, "flx_score_kmer_fold");
-        if (bit_level)
-            FLX_CHECK(launch_fold<1>(ctx, a));  // runs inside one word can be bad ranges
-        else
-            FLX_CHECK(launch_fold<3>(ctx, a));
-    }
+    if (bit_level)
+        FLX_CHECK(launch_fold<1>(ctx, a));  // runs inside one word can be bad ranges
+    else
+        FLX_CHECK(launch_fold<3>(ctx, a));
     // child_offsets = exclusive scan of the counts (n + 1 entries; the last one is the total)
     hipLaunchKernelGGL(k_widen_u32_i64, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, st, n_reads + 1,
                        d_nchild, d_rowb);
@@ -1661,7 +1673,6 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
                         (long long)total_children, (unsigned long long)out->child_capacity);
     if (total_children > 0) {
         a.child_offsets = out->child_offsets;
-        flx_time_scope tf(ctx, "flx_score_kmer_fold");  // (a scope: the checks below may return)
         // FLX_KMER_FOLD=words: the children inside their read's lane (MODE 4, second implementation of the word-level path)
         const bool per_child = !bit_level && !(fold_env && strcmp(fold_env, "words") == 0);
         if (bit_level) {
@@ -1683,19 +1694,20 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
             unsigned int overflow = 1;
             if (d_inline) {  // the ranges MODE 3 left inline go to their places; a read with more than fit sends the batch through MODE 5
                 FLX_HIP(ctx, hipMemsetAsync(d_overflow, 0, 4, st));
-                hipLaunchKernelGGL(k_children_from_inline, dim3(nb), dim3(256), 0, st, n_reads, (const uint32_t *)d_nchild, (const uint64_t *)out->child_offsets,
-                                   (const int32_t *)d_inline, out->child_ranges, a.child_parent, d_overflow);
+                {
+                    flx_time_scope ti(ctx, "flx_score_kmer_fold.inline");  // (part of the folds' device time; closed before the host waits)
+                    hipLaunchKernelGGL(k_children_from_inline, dim3(nb), dim3(256), 0, st, n_reads, (const uint32_t *)d_nchild, (const uint64_t *)out->child_offsets,
+                                       (const int32_t *)d_inline, out->child_ranges, a.child_parent, d_overflow);
+                }
                 FLX_HIP(ctx, hipMemcpyAsync(&overflow, d_overflow, 4, hipMemcpyDeviceToHost, st));
                 FLX_HIP(ctx, hipStreamSynchronize(st));
             }
             if (overflow) FLX_CHECK(launch_fold<5>(ctx, a));
-            tf.end();  // (the sort times its own passes)
             hipLaunchKernelGGL(k_child_keys, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st, nc, out->child_ranges, keys0, vals0);
             uint64_t *skeys = nullptr;
             uint32_t *svals = nullptr;
             FLX_CHECK(flx_radix_sort_pairs(ctx, nc, keys0, keys1, vals0, vals1, d_sortws, sort_ws, &skeys, &svals));
             a.child_order = svals;
-            flx_time_scope tf6(ctx, "flx_score_kmer_fold");
             FLX_CHECK(launch_fold<6>(ctx, a));
         }
     }

@@ -234,3 +234,15 @@ def odd_fastq_bytes(reads, width=61):
         if i % 5 == 2:
             out += b"\n"
     return bytes(out)
+
+
+SCORE_KEYS = ("mean_q", "window_q", "passed", "first", "last", "child_offsets", "child_ranges", "child_mean_q", "child_window_q", "child_passed")
+
+
+def same(a, b, what):
+    """Two score dictionaries (filtlong_amd.api.Context.score_reads / _oracle.score_plane_mt) agree in every field, doubles bit for bit."""
+    for k in SCORE_KEYS:
+        x, y = np.ascontiguousarray(a[k]), np.ascontiguousarray(b[k])
+        if x.dtype == np.float64:
+            x, y = x.view(np.uint64), np.asarray(y, dtype=np.float64).view(np.uint64)
+        assert x.shape == y.shape and (x == np.asarray(y, dtype=x.dtype).reshape(x.shape)).all(), (what, k)

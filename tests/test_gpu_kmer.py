@@ -283,28 +283,47 @@ def test_prefilter_and_fold_variants_give_identical_results(ctx, be, synth, monk
     # the parent's recurrence on the child's slice of the row), inside the read's lane at word level (FLX_KMER_FOLD=words), bit
     # by bit (FLX_KMER_FOLD=bits)
     ks = be.kmers(assembly=synth["contigs"])
+    # ... each of them by the name of its timing bracket (flx_score_kmer_fold.m<mode>.<ring<R> | global>.<fp | grid>): a forced form
+    # that quietly ran as the default one would compare the default with itself
+    ctx.timing_enable(True)
+
+    def launches(mode, form=""):
+        return ctx.timing_get("flx_score_kmer_fold.m%d.%s" % (mode, form))[1]
+
+    parent_ring = {250: "ring32", 31: "ring32", 1: "ring32", 1500: "ring128", 5000: "ring256"}  # (launch_fold: 18 + ceil(ws / 32) words)
     for ws in (250, 31, 1, 1500, 5000):
         for split in (100, 32, 1000):
             pk = dict(pkw, window_size=ws, split=split)
             ring = be.score(reads, pk, ks)
             monkeypatch.setenv("FLX_KMER_FOLD_STREAMS", "global")
+            ctx.timing_reset()
             glob_ = be.score(reads, pk, ks)
             monkeypatch.delenv("FLX_KMER_FOLD_STREAMS")
+            assert launches(3, "global.fp") == launches(3) >= 1 and launches(6, "global.fp") == launches(6) >= 1, (ws, split)
+            assert [launches(m) for m in (0, 1, 2, 4)] == [0, 0, 0, 0] and launches(5, "global.fp") == launches(5), (ws, split)
             monkeypatch.setenv("FLX_KMER_FOLD_EVENTS", "1")  # the steady state by events (positions where the window's edges differ)
             events = be.score(reads, pk, ks)
             monkeypatch.delenv("FLX_KMER_FOLD_EVENTS")
             for (name, _s, _q), a, b in zip(reads, ring, events):
                 assert bits(a) == bits(b), (name, ws, split, "events")
             monkeypatch.setenv("FLX_KMER_FOLD", "words")
+            ctx.timing_reset()
             words = be.score(reads, pk, ks)
+            assert launches(3, parent_ring[ws] + ".") == launches(3) >= 1 and launches(4, parent_ring[ws] + ".fp") == launches(4) >= 1, (ws, split)
+            assert [launches(m) for m in (0, 1, 2, 5, 6)] == [0, 0, 0, 0, 0], (ws, split)
             monkeypatch.setenv("FLX_KMER_FOLD", "bits")
+            ctx.timing_reset()
             bitl = be.score(reads, pk, ks)
             monkeypatch.delenv("FLX_KMER_FOLD")
+            assert launches(1, parent_ring[ws] + ".fp") == launches(1) >= 1 and launches(2, parent_ring[ws] + ".fp") == launches(2) >= 1, (ws, split)
+            assert [launches(m) for m in (0, 3, 4, 5, 6)] == [0, 0, 0, 0, 0], (ws, split)
             assert sum(len(a["child_ranges"]) for a in ring) > 0
             for (name, _s, _q), a, b, c, d in zip(reads, ring, glob_, words, bitl):
                 assert bits(a) == bits(b), (name, ws, split, "global streams")
                 assert bits(a) == bits(c), (name, ws, split, "words")
                 assert bits(a) == bits(d), (name, ws, split, "bits")
+    ctx.timing_enable(False)
+    ctx.timing_reset()
     monkeypatch.setenv("FLX_KMER_PREFILTER", "0")
     monkeypatch.setenv("FLX_KMER_FOLD", "bits")
     # the two implementations of the coverage kernel: the wave-level one (pair tables, outermost-member search, far-first spans;
@@ -810,14 +829,7 @@ def test_integer_grid_folds_vs_oracle(ctx, monkeypatch):
         reads.append(seq.tobytes())
     plane, offsets, lengths = api.pack_reads(reads)
     order = api.length_order(lengths)
-    keys = ("mean_q", "window_q", "passed", "first", "last", "child_offsets", "child_ranges", "child_mean_q", "child_window_q", "child_passed")
-
-    def same(a, b, what):
-        for k in keys:
-            x, y = np.ascontiguousarray(a[k]), np.ascontiguousarray(b[k])
-            if x.dtype == np.float64:
-                x, y = x.view(np.uint64), np.asarray(y, dtype=np.float64).view(np.uint64)
-            assert x.shape == y.shape and (x == np.asarray(y, dtype=x.dtype).reshape(x.shape)).all(), (what, k)
+    same = _cases.same
 
     for ws, grid in ((250, True), (500, True), (128, True), (64, True), (100, None), (96, None), (333, None), (1000, False), (31, False), (2047, None), (7, False)):
         for pkw in (dict(window_size=ws), dict(window_size=ws, trim=True, split=max(32, ws // 2))):
