@@ -22,6 +22,7 @@
 #include "kmerset.h"
 #include "cover_common.h"
 #include "rank_internal.h"
+#include "score_kmer_common.h"
 
 #ifndef FLX_FARFIRST_LANES
 #define FLX_FARFIRST_LANES 16  // settled lanes of a span from which the next span asks the exact table first (score_kmer.hip, below)
@@ -727,91 +728,7 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
 #ifndef FLX_FOLD_FMA
 #define FLX_FOLD_FMA 1
 #endif
-// ---- the window recurrence on the integer grid (round 5) ------------------------------------------------------------------------
-// src/read.cpp:228-231 with qualities 0.0 / 1.0 is  w = fl(fl(w - tb * d) + lb * d),  d = fl(1 / ws), and the drift of those
-// roundings is part of the result.  But WHERE w rounds is known: on the grid of its binade.  Let d_E be d rounded to the grid of
-// binade E (2^(E-52)); a GROUP is a run of binades on which d_E is the same real number d* (and no binade rounds d on a tie).  While
-//   * w stays strictly above the bottom of its group (and above 4 d: a step that takes a base out and puts one in dips by d, and the
-//     way back is only exact from at most one binade down), and
-//   * w does not reach a binade above the one it was in when the regime began (there w's own low bits would be rounded away),
-// every step is EXACT:  w = w_b + c * d*  with c the number of covered bases that entered the window minus those that left — all
-// operands are multiples of the regime's grid, nothing rounds.  A word of 32 positions then is three small integers — the total,
-// the lowest and the highest prefix of its +-1 walk (a table over the (new, old) nibble pairs in LDS) — two compares and two adds;
-// the minimum of w over the word is w_b + (lowest prefix) * d*.  A word that leaves the regime is replayed in floating point, FOR
-// THAT LANE (the others keep their integer step), and the regime begins again from the value it ends on.  ws = 250 (the default):
-// d* = d + 4 ulp on every binade from 2^-4 up, so one regime holds while 16 of the 250 bases are covered and w has been as high
-// before; on the synthetic reads 0.7 % of a lane's words are replayed (the way into and out of a junk block, the first time a read's
-// window fills up).  tools/sim_fold_grid.cpp: the same regime logic on the host against the plain recurrence, 180 000 bit streams x
-// 6000 window sizes, bit for bit — and the tests hold this kernel against the FP kernel (FLX_KMER_FOLD_GRID=0) on every read and child.
-struct GridTab {
-    enum { kMax = 26 };
-    double dstar[kMax];  // per binade of w (biased exponent e0 + i): d on that binade's grid; 0 = no regime there (a tie, or outside)
-    double lv[kMax];     // the value w must stay strictly above: max(bottom of the binade's group, 4 d)
-    int top[kMax];       // biased exponent of the highest binade of the binade's group
-    int e0, n;
-};
-
-constexpr int kInlineChildren = 8;
-struct FoldArgs {
-    GridTab gt;
-    const uint32_t *cov;
-    const uint64_t *cov_off;
-    const int32_t *lengths;
-    const uint32_t *order;
-    uint64_t n_reads;
-    const int32_t *count;
-    const int32_t *first;
-    const int32_t *last;
-    int ws;
-    int ring_words;  // RING kernels: words per lane in the LDS ring (a power of two)
-    int events;      // FLX_KMER_FOLD_EVENTS=1: the steady state walks the positions where the window's edges differ (measured: not faster)
-    int grid;        // 1: the steady state runs on the integer grid (GridTab below; FLX_KMER_FOLD_GRID=0 and windows without a wide group: 0)
-    double ws_d;
-    double delta;  // fl(1.0 / ws): the value of q/ws for a covered base (src/read.cpp:228-229)
-    double clamp;  // 0.5 / ws
-    flx_params p;
-    double *mean_q;
-    double *window_q;
-    uint8_t *passed;
-    // MODE 3 leaves the first kInlineChildren ranges of every read here ([n_reads][kInlineChildren][2], or NULL): they are moved to
-    // their places in the CSR once the counts have been scanned, and the ranges pass (MODE 5) only runs for a batch in which some
-    // read has more (round 5: MODE 5 walked every row again for ~1 child per read — 7.7 of C4's 33 ms of folds)
-    int32_t *inline_ranges;
-    // MODE 5 / 6: one lane per child
-    uint32_t *child_parent;         // [n_children] read index of every child (written by MODE 5, read by MODE 6)
-    const uint32_t *child_order;    // [n_children] children by descending length (MODE 6)
-    uint64_t n_children;
-    // children
-    uint32_t *n_child;              // [n] (count pass)
-    const uint64_t *child_offsets;  // [n+1] (emit pass)
-    int32_t *child_ranges;
-    double *child_mean_q;
-    double *child_window_q;
-    uint8_t *child_passed;
-};
-
-__device__ __forceinline__ uint8_t cutoffs(const flx_params &p, int L, double mean, double window) {
-    bool ok = true;  // src/read.cpp:64-73
-    if (p.min_length_set && L < p.min_length) ok = false;
-    else if (p.max_length_set && L > p.max_length) ok = false;
-    else if (p.min_mean_q_set && mean < p.min_mean_q) ok = false;
-    else if (p.min_window_q_set && window < p.min_window_q) ok = false;
-    return ok ? 1 : 0;
-}
-
-struct Win {  // one sliding-window recurrence (parent or current child)
-    int cnt;    // covered bases so far
-    double w;   // window quality
-    double mn;  // its minimum
-};
-
-__device__ __forceinline__ double window_result(const FoldArgs &a, int len, int cnt, double mn) {
-    const double mean = 100.0 * (double)cnt / (double)len;
-    if (len <= a.ws) return mean;  // src/read.cpp:217-218
-    if (mn < a.clamp) mn = 0.0;
-    return 100.0 * mn;
-}
-
+// (the grid table, the folds' arguments and the shared result code: fold_grid_tab.h, score_kmer_common.h)
 // MODE 0: parent only (no --trim/--split).  MODE 1: parent + count children, bit by bit.  MODE 2: emit children.
 // MODE 4: emit children with the zero-run events found at word level and a branch-light bit loop (same condition as 3).
 // MODE 3: parent + count children at WORD level — a zero run can only be a bad range if it starts at position 0, reaches
@@ -834,7 +751,7 @@ __device__ __forceinline__ double window_result(const FoldArgs &a, int len, int 
 template <int MODE, bool RING, bool GRID = false>
 __global__ void __launch_bounds__(256) FLX_FOLD_OCC k_kmer_fold(const FoldArgs a) {
     const uint64_t slot = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = slot < (MODE == 6 ? a.n_children : a.n_reads);
+    bool live = slot < (MODE == 6 ? a.n_children : a.n_reads);
     uint32_t rid = 0;  // MODE 6: the child's index
     int L = 0;
     const uint32_t *row = a.cov;
@@ -854,6 +771,11 @@ __global__ void __launch_bounds__(256) FLX_FOLD_OCC k_kmer_fold(const FoldArgs a
         row = a.cov + (a.cov_off[parent] >> 2) + base_word;
         row_words_left = ((a.lengths[parent] + 31) >> 5) - base_word;
         bit_off = (uint32_t)(start - 32 * base_word);
+    }
+    if ((MODE == 0 || MODE == 3 || MODE == 5 || MODE == 6) && a.long_min > 0 && L >= a.long_min) {
+        // a long read or child: the cooperative path's (score_kmer_long.hip) — this lane folds nothing and writes nothing
+        live = false;
+        L = 0;
     }
     int Lmax = L;
     for (int o = 32; o > 0; o >>= 1) Lmax = max(Lmax, __shfl_xor(Lmax, o, 64));
@@ -1379,9 +1301,16 @@ __global__ void __launch_bounds__(256) FLX_FOLD_OCC k_kmer_fold(const FoldArgs a
     }
 }
 
-__global__ void k_cov_row_bytes(uint64_t n, const int32_t *lengths, int64_t *row_bytes) {
+// (long_min > 0: also counts the batch's long reads and their 32-position steps for the cooperative path, score_kmer_long.hip)
+__global__ void k_cov_row_bytes(uint64_t n, const int32_t *lengths, int64_t *row_bytes, int long_min, int ws, KmerLongCounts *long_reads) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) row_bytes[i] = (int64_t)((((uint64_t)lengths[i] + 7) / 8 + 15) & ~15ull);
+    if (i >= n) return;
+    const int L = lengths[i];
+    row_bytes[i] = (int64_t)((((uint64_t)L + 7) / 8 + 15) & ~15ull);
+    if (long_min > 0 && L >= long_min) {
+        atomicAdd(&long_reads->n, 1ull);
+        atomicAdd(&long_reads->words, flx_kmer_long_words(L, ws));
+    }
 }
 
 __global__ void k_widen_u32_i64(uint64_t n, const uint32_t *in, int64_t *out) {
@@ -1391,11 +1320,13 @@ __global__ void k_widen_u32_i64(uint64_t n, const uint32_t *in, int64_t *out) {
 
 // the ranges MODE 3 left inline -> their places in the CSR (+ every child's read); counts the reads that have more than fit inline
 __global__ void __launch_bounds__(256) k_children_from_inline(uint64_t n, const uint32_t *n_child, const uint64_t *child_offsets, const int32_t *inline_ranges,
-                                                              int32_t *child_ranges, uint32_t *child_parent, unsigned int *overflow) {
+                                                              int32_t *child_ranges, uint32_t *child_parent, unsigned int *overflow,
+                                                              const int32_t *lengths, int long_min) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t nc = n_child[i];
     if (nc == 0) return;
+    if (long_min > 0 && lengths[i] >= long_min) return;  // a long read: the cooperative path writes its ranges, however many
     if (nc > (uint32_t)kInlineChildren) {
         atomicAdd(overflow, 1u);
         return;
@@ -1422,51 +1353,6 @@ __global__ void k_child_keys(uint64_t n, const int32_t *ranges, uint64_t *keys, 
 
 // the fold kernels: with the LDS ring when it fits (R words per lane; 4 waves per workgroup up to R = 64, one wave up to R = 512),
 // else (windows beyond ~15 000 positions) both streams from global memory
-// The grid table of a window size (GridTab, above): per binade of w the step d rounded to that binade's grid, the groups of binades
-// that share it, and whether the integer-grid steady state pays — the group that holds [1, 2) must reach down to 2^-3 at least (ws =
-// 250: 2^-4; ws = 1000: d rounds differently on either side of 1.0, where the window of a clean read sits — the FP kernel then).
-static bool build_grid_table(int ws, GridTab &g) {
-    memset(&g, 0, sizeof g);
-    if (ws < 8 || ws > (1 << 20)) return false;
-    volatile double one = 1.0, wsd = (double)ws;
-    const double delta = one / wsd;
-    uint64_t bits;
-    memcpy(&bits, &delta, 8);
-    const int e_d = (int)((bits >> 52) & 0x7ff) - 1023;
-    const uint64_t M = (bits & ((1ull << 52) - 1)) | (1ull << 52);  // delta = M * 2^(e_d - 52)
-    const int e_min = e_d - 2, e_max = 1;
-    const int n = e_max - e_min + 1;
-    if (n > GridTab::kMax) return false;
-    bool tie[GridTab::kMax];
-    for (int i = 0; i < n; ++i) {
-        const int shift = (e_min + i) - e_d;  // the grid of binade E is 2^shift ulps of delta
-        tie[i] = false;
-        if (shift <= 0) {
-            g.dstar[i] = delta;
-        } else {
-            const uint64_t rem = M & ((1ull << shift) - 1), half = 1ull << (shift - 1);
-            tie[i] = rem == half;
-            g.dstar[i] = ldexp((double)((M >> shift) + (rem > half ? 1 : 0)), shift + e_d - 52);
-        }
-    }
-    bool pays = false;
-    for (int i = 0; i < n;) {  // groups: maximal runs of binades without a tie that share d*
-        if (tie[i]) { g.dstar[i] = 0.0; g.lv[i] = 0.0; ++i; continue; }
-        int j = i;
-        while (j + 1 < n && !tie[j + 1] && g.dstar[j + 1] == g.dstar[i]) ++j;
-        const double bottom = std::max(ldexp(1.0, e_min + i), 4.0 * delta);
-        for (int k = i; k <= j; ++k) {
-            g.lv[k] = bottom;
-            g.top[k] = 1023 + e_min + j;
-        }
-        if (e_min + i <= -3 && e_min + j >= 0) pays = true;
-        i = j + 1;
-    }
-    g.e0 = 1023 + e_min;
-    g.n = n;
-    return pays;
-}
-
 // The timing bracket of a fold launch says which form ran: flx_score_kmer_fold.m<MODE>.<ring<R> | global>.<fp | grid>.  Every name is
 // a static string (the context keeps the pointer) and complete, so none is a prefix of another; flx_timing_get("flx_score_kmer_fold")
 // still sums all of them — one bracket per launch, none nested, so that sum is the device time of the folds.
@@ -1513,8 +1399,10 @@ static int launch_fold(flx_ctx *ctx, FoldArgs &a) {
 int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_plane, uint64_t plane_bytes,
                        const uint64_t *d_offsets, const int32_t *d_lengths, const uint32_t *d_order,
                        uint64_t n_reads, const flx_params *params, flx_scores *out) {
-    (void)plane_bytes;
     out->n_children = 0;
+    ctx->last_kmer_redo = nullptr;  // (they name workspace 0 of the previous call: not past the first return of this one)
+    ctx->last_kmer_redo_n = 0;
+    ctx->last_kmer_cover = "";
     if (n_reads == 0) return FLX_OK;
     hipStream_t st = ctx->stream;
     const bool want_children = params->trim || params->split_set;
@@ -1529,8 +1417,21 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const char *fold_env0 = getenv("FLX_KMER_FOLD");
     const bool inline_children = want_children && !(params->split_set && params->split < 32) && !fold_env0;  // (the one-lane-per-child path)
+    // The cooperative path for ultra-long reads and children (score_kmer_long.hip) applies where the one-lane kernels would fold on
+    // the integer grid: a window size whose grid table pays, none of the test-only fold variants, --split absent or >= 32.
+    GridTab gt;
+    const bool grid_pays = build_grid_table(params->window_size, gt);
+    bool grid_on, events_on;
+    {
+        const char *ev_env = getenv("FLX_KMER_FOLD_EVENTS");
+        events_on = ev_env && ev_env[0] == '1';
+        const char *grid_env = getenv("FLX_KMER_FOLD_GRID");  // "0": the floating-point steady state (the second implementation; tests, A/B)
+        grid_on = grid_pays && !(grid_env && grid_env[0] == '0');
+    }
+    KmerLong kl;
+    FLX_CHECK(flx_kmer_long_threshold(ctx, plane_bytes, grid_on && !events_on && !fold_env0 && !(params->split_set && params->split < 32), &kl));
     const size_t small_bytes = 2 * up((n_reads + 1) * 8) + 3 * up(n_reads * 4) + up((n_reads + 1) * 4) + up(scan_ws) + up(n_reads) +
-                               (inline_children ? up(n_reads * (size_t)kInlineChildren * 8) + up(64) : 0);
+                               (inline_children ? up(n_reads * (size_t)kInlineChildren * 8) + up(64) : 0) + up(64);
     void *small = nullptr;
     FLX_CHECK(flx_workspace(ctx, 0, small_bytes, &small));
     char *wp = (char *)small;
@@ -1546,14 +1447,21 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
     int32_t *d_inline = inline_children ? (int32_t *)carve(n_reads * (size_t)kInlineChildren * 8) : nullptr;
     unsigned int *d_overflow = inline_children ? (unsigned int *)carve(64) : nullptr;
     int32_t *first = out->first ? out->first : d_first_tmp, *last = out->last ? out->last : d_last_tmp;
+    kl.d_reads = (KmerLongCounts *)carve(64);  // the long reads' and (at + 1) the long children's counts
+    kl.d_children = kl.d_reads + 1;
     FLX_HIP(ctx, hipMemsetAsync(d_rowb, 0, (n_reads + 1) * 8, st));
-    hipLaunchKernelGGL(k_cov_row_bytes, dim3(nb), dim3(256), 0, st, n_reads, d_lengths, d_rowb);
+    if (kl.on) FLX_HIP(ctx, hipMemsetAsync(kl.d_reads, 0, 2 * sizeof(KmerLongCounts), st));
+    hipLaunchKernelGGL(k_cov_row_bytes, dim3(nb), dim3(256), 0, st, n_reads, d_lengths, d_rowb, kl.on ? kl.thr : 0, params->window_size, kl.d_reads);
     FLX_CHECK(flx_exclusive_scan_i64(ctx, n_reads + 1, d_rowb, d_covoff, d_scanws, scan_ws));
     int64_t cov_bytes = 0;
+    KmerLongCounts long_reads = {0, 0}, long_children = {0, 0};
     FLX_HIP(ctx, hipMemcpyAsync(&cov_bytes, d_covoff + n_reads, 8, hipMemcpyDeviceToHost, st));
+    if (kl.on) FLX_HIP(ctx, hipMemcpyAsync(&long_reads, kl.d_reads, sizeof long_reads, hipMemcpyDeviceToHost, st));  // (with the wait below)
     FLX_HIP(ctx, hipStreamSynchronize(st));
     void *d_cov = nullptr;
-    FLX_CHECK(flx_workspace(ctx, 1, (size_t)cov_bytes + 64, &d_cov));
+    const size_t cov_room = up((size_t)cov_bytes + 64), long_room = long_reads.n ? flx_kmer_long_reads_workspace(long_reads) : 0;
+    FLX_CHECK(flx_workspace(ctx, 1, cov_room + long_room, &d_cov));
+    void *d_long_reads = long_reads.n ? (char *)d_cov + cov_room : nullptr, *d_long_children = nullptr;
 
     // ---- kernel 1: lookups -> coverage bits ----
     {
@@ -1568,8 +1476,6 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
         flx_time_scope tc(ctx, "flx_score_kmer_cover");
         ctx->last_kmer_locus = false;
         ctx->last_kmer_cover = "v2";
-        ctx->last_kmer_redo = nullptr;
-        ctx->last_kmer_redo_n = 0;
         if (!old_cover) {
             const unsigned wgrid = (unsigned)std::min<uint64_t>((n_reads + FLX_COVER_THREADS / 64 - 1) / (FLX_COVER_THREADS / 64), 1u << 22);
             const char *locus_env = getenv("FLX_KMER_LOCUS");  // "0": without the assembly text (the round-3 kernel; tests, A/B)
@@ -1621,13 +1527,11 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
         a.clamp = half / wsd;
     }
     a.p = *params;
-    {
-        const char *ev_env = getenv("FLX_KMER_FOLD_EVENTS");
-        a.events = ev_env && ev_env[0] == '1';
-        const char *grid_env = getenv("FLX_KMER_FOLD_GRID");  // "0": the floating-point steady state (the second implementation; tests, A/B)
-        a.grid = build_grid_table(params->window_size, a.gt) && !(grid_env && grid_env[0] == '0');
-        ctx->last_kmer_fold_grid = false;  // (launch_fold says so when a grid kernel really runs)
-    }
+    a.gt = gt;
+    a.events = events_on;
+    a.grid = grid_on;
+    a.long_min = kl.on ? kl.thr : 0;
+    ctx->last_kmer_fold_grid = false;  // (launch_fold says so when a grid kernel really runs)
     a.mean_q = out->mean_q;
     a.window_q = out->window_q;
     a.passed = out->passed;
@@ -1645,10 +1549,11 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
     // (every fold launch opens its own timing bracket: launch_fold)
     if (!want_children) {
         FLX_CHECK(launch_fold<0>(ctx, a));
+        if (long_reads.n) FLX_CHECK(flx_kmer_long_reads(ctx, a, &kl, long_reads, false, d_long_reads, long_room));
         if (out->child_offsets) FLX_HIP(ctx, hipMemsetAsync(out->child_offsets, 0, (n_reads + 1) * 8, st));
         FLX_HIP(ctx, hipGetLastError());
         FLX_HIP(ctx, hipStreamSynchronize(st));
-        return FLX_OK;
+        return flx_kmer_long_report(ctx, kl, d_long_reads, nullptr);
     }
 
     FLX_HIP(ctx, hipMemsetAsync(d_nchild, 0, (n_reads + 1) * 4, st));
@@ -1660,12 +1565,15 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
         FLX_CHECK(launch_fold<1>(ctx, a));  // runs inside one word can be bad ranges
     else
         FLX_CHECK(launch_fold<3>(ctx, a));
+    // the long reads: their folds, their n_child, and how many of their children are long themselves
+    if (long_reads.n) FLX_CHECK(flx_kmer_long_reads(ctx, a, &kl, long_reads, true, d_long_reads, long_room));
     // child_offsets = exclusive scan of the counts (n + 1 entries; the last one is the total)
     hipLaunchKernelGGL(k_widen_u32_i64, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, st, n_reads + 1,
                        d_nchild, d_rowb);
     FLX_CHECK(flx_exclusive_scan_i64(ctx, n_reads + 1, d_rowb, (int64_t *)out->child_offsets, d_scanws, scan_ws));
     int64_t total_children = 0;
     FLX_HIP(ctx, hipMemcpyAsync(&total_children, (int64_t *)out->child_offsets + n_reads, 8, hipMemcpyDeviceToHost, st));
+    if (long_reads.n) FLX_HIP(ctx, hipMemcpyAsync(&long_children, kl.d_children, sizeof long_children, hipMemcpyDeviceToHost, st));
     FLX_HIP(ctx, hipStreamSynchronize(st));
     out->n_children = (uint64_t)total_children;
     if ((uint64_t)total_children > out->child_capacity)
@@ -1684,12 +1592,14 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
             const uint64_t nc = (uint64_t)total_children;
             const size_t sort_ws = flx_radix_sort_workspace(nc);
             void *cw = nullptr;
-            FLX_CHECK(flx_workspace(ctx, 2, 2 * up(nc * 8) + 3 * up(nc * 4) + up(sort_ws), &cw));
+            const size_t long_child_room = long_reads.n ? flx_kmer_long_children_workspace(long_children) : 0;
+            FLX_CHECK(flx_workspace(ctx, 2, 2 * up(nc * 8) + 3 * up(nc * 4) + up(sort_ws) + long_child_room, &cw));
             wp = (char *)cw;
             uint64_t *keys0 = (uint64_t *)carve(nc * 8), *keys1 = (uint64_t *)carve(nc * 8);
             uint32_t *vals0 = (uint32_t *)carve(nc * 4), *vals1 = (uint32_t *)carve(nc * 4);
             a.child_parent = (uint32_t *)carve(nc * 4);
             void *d_sortws = carve(sort_ws);
+            if (long_reads.n) d_long_children = carve(long_child_room);
             a.n_children = nc;
             unsigned int overflow = 1;
             if (d_inline) {  // the ranges MODE 3 left inline go to their places; a read with more than fit sends the batch through MODE 5
@@ -1697,12 +1607,14 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
                 {
                     flx_time_scope ti(ctx, "flx_score_kmer_fold.inline");  // (part of the folds' device time; closed before the host waits)
                     hipLaunchKernelGGL(k_children_from_inline, dim3(nb), dim3(256), 0, st, n_reads, (const uint32_t *)d_nchild, (const uint64_t *)out->child_offsets,
-                                       (const int32_t *)d_inline, out->child_ranges, a.child_parent, d_overflow);
+                                       (const int32_t *)d_inline, out->child_ranges, a.child_parent, d_overflow, d_lengths, a.long_min);
                 }
                 FLX_HIP(ctx, hipMemcpyAsync(&overflow, d_overflow, 4, hipMemcpyDeviceToHost, st));
                 FLX_HIP(ctx, hipStreamSynchronize(st));
             }
             if (overflow) FLX_CHECK(launch_fold<5>(ctx, a));
+            // the long reads' ranges, and the folds of the children that are long themselves (MODE 6 below leaves those alone)
+            if (long_reads.n) FLX_CHECK(flx_kmer_long_children(ctx, a, &kl, long_reads, long_children, d_long_reads, d_long_children, long_child_room));
             hipLaunchKernelGGL(k_child_keys, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st, nc, out->child_ranges, keys0, vals0);
             uint64_t *skeys = nullptr;
             uint32_t *svals = nullptr;
@@ -1713,5 +1625,5 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
     }
     FLX_HIP(ctx, hipGetLastError());
     FLX_HIP(ctx, hipStreamSynchronize(st));
-    return FLX_OK;
+    return flx_kmer_long_report(ctx, kl, d_long_reads, d_long_children);
 }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Ultra-long reads in Phred mode: what 100 reads of 0.5-4 Mbp add to a C2-shaped scoring step, with the cooperative long-read path
+"""Ultra-long reads.  With --kmer: k-mer mode (see main_kmer below).  Without: Phred mode: what 100 reads of 0.5-4 Mbp add to a C2-shaped scoring step, with the cooperative long-read path
 (score_phred_long.hip) and without it (FLX_PHRED_LONG_MIN=0: every read in one lane of the default kernel), and one 4 Mbp read alone.
 
     python tools/bench_ultralong.py [--reads 1000000] [--steps 5] [--warmup 2] [--junk 0.03] [--centre 5,3] [--out FILE]
@@ -43,7 +43,11 @@ def main():
                     help="share of 300-base runs of the extra reads at Phred 0-3 (windows around quality 0.5: the serial case)")
     ap.add_argument("--centre", default="5,3", help="gamma shape,scale of the runs' Phred centres (5,3: mean 15; 9,1.8: mean 16, fewer low runs)")
     ap.add_argument("--out", default="")
+    ap.add_argument("--kmer", action="store_true", help="k-mer mode: the cooperative folds of score_kmer_long.hip against FLX_KMER_LONG_MIN=0")
+    ap.add_argument("--crossover", action="store_true", help="--kmer: also one read of 2^16 .. 2^22 bases alone, with and without the path")
     args = ap.parse_args()
+    if args.kmer:
+        return main_kmer(args)
 
     import torch
     from filtlong_amd import api, synth
@@ -148,6 +152,173 @@ def main():
                 fh.write(json.dumps(r) + "\n")
     ctx.close()
     return 0 if summary["same_bits_with_and_without_the_path"] else 1
+
+
+def main_kmer(args):
+    """k-mer mode (window 250, reference: 5 Mbp of random bases as an assembly).  Rows, each with the cooperative path (default
+    threshold) and without it (FLX_KMER_LONG_MIN=0), plain and with --trim --split 500:
+      * a C3-shaped step of --reads reads plus --extra reads of 0.5-4 Mbp (tiled from the reference, 3 % substitutions, junk blocks);
+      * one 4 Mbp read alone;  with --crossover one read of 2^16 .. 2^22 bases alone.
+    Per row the device time of flx_score_kmer_cover, flx_score_kmer_fold and flx_score_kmer_long (medians over --steps), the wall
+    time per step, and the words the path replayed in floating point (from the FLX_API_TIMING stage line)."""
+    import re
+    import tempfile
+    import torch
+    from filtlong_amd import api, synth, _lib
+
+    ctx = api.Context(0)
+    dev = torch.device("cuda", 0)
+    ref_len = 5_000_000
+    ref = synth.bases_read(synth.STREAM_REF, 0, 0, ref_len)
+    ks = api.Kmers(ctx)
+    ks.add_assembly_fasta([ref.tobytes()])
+    ks.finalize()
+    d_ref = torch.from_numpy(ref).to(dev)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    rows = []
+
+    def long_read(L, seed):
+        rng = np.random.default_rng(seed)
+        parts, have = [], 0
+        while have < L:
+            n = int(rng.integers(20_000, 150_000))
+            a = int(rng.integers(0, ref_len - n))
+            parts.append(ref[a:a + n])
+            have += n
+        seq = np.concatenate(parts)[:L].copy()
+        sub = rng.random(L) < 0.03
+        seq[sub] = acgt[rng.integers(0, 4, int(sub.sum()))]
+        for _ in range(L // 100_000):
+            n = int(rng.choice([40, 300, 600, 3000]))
+            a = int(rng.integers(0, L - n))
+            seq[a:a + n] = acgt[rng.integers(0, 4, n)]
+        return seq
+
+    def setup(lengths_base, extra):
+        n0 = len(lengths_base)
+        lengths = np.concatenate([lengths_base, np.array([len(x) for x in extra], dtype=np.int32)]).astype(np.int32)
+        n = len(lengths)
+        offsets = np.zeros(n, dtype=np.uint64)
+        pb = C.c_uint64()
+        ctx.L.flx_plane_layout(lengths.ctypes.data, n, offsets.ctypes.data, C.byref(pb))
+        d_plane = torch.zeros(pb.value, dtype=torch.uint8, device=dev)
+        d_off = torch.from_numpy(offsets.view(np.int64)).to(dev)
+        d_len = torch.from_numpy(lengths).to(dev)
+        if n0:
+            d_ids = torch.arange(0, n0, dtype=torch.int64, device=dev)
+            ctx.synth_seq_dev(synth.SEED, d_plane.data_ptr(), pb.value, d_off.data_ptr(), d_len.data_ptr(), d_ids.data_ptr(), n0, d_ref.data_ptr(), ref_len)
+        for i, q in enumerate(extra):
+            o = int(offsets[n0 + i])
+            d_plane[o:o + len(q)].copy_(torch.from_numpy(q))
+        d_ord = torch.from_numpy(api.length_order(lengths).view(np.int32)).to(dev)
+        cap = 4 * n + 100_000
+        t = {k: torch.zeros(sz, dtype=dt, device=dev) for k, sz, dt in (
+            ("mean", n, torch.float64), ("win", n, torch.float64), ("pass", n, torch.uint8), ("first", n, torch.int32), ("last", n, torch.int32),
+            ("coff", n + 1, torch.int64), ("crng", 2 * cap, torch.int32), ("cmean", cap, torch.float64), ("cwin", cap, torch.float64),
+            ("cpass", cap, torch.uint8))}
+        sc = _lib.Scores()
+        sc.mean_q, sc.window_q, sc.passed, sc.first, sc.last = (t["mean"].data_ptr(), t["win"].data_ptr(), t["pass"].data_ptr(),
+                                                               t["first"].data_ptr(), t["last"].data_ptr())
+        sc.child_offsets, sc.child_ranges, sc.child_mean_q, sc.child_window_q, sc.child_passed = (
+            t["coff"].data_ptr(), t["crng"].data_ptr(), t["cmean"].data_ptr(), t["cwin"].data_ptr(), t["cpass"].data_ptr())
+        sc.child_capacity = cap
+        torch.cuda.synchronize()
+        return dict(n=n, bases=int(lengths.astype(np.int64).sum()), plane=d_plane, pb=pb.value, off=d_off, len=d_len, ord=d_ord, t=t, sc=sc)
+
+    def run(name, b, children, long_min, steps=None):
+        steps = steps or args.steps
+        if long_min is None:
+            os.environ.pop("FLX_KMER_LONG_MIN", None)
+        else:
+            os.environ["FLX_KMER_LONG_MIN"] = str(long_min)
+        params = api.make_params(window_size=args.window_size, trim=children, split=500 if children else None)
+
+        def once():
+            ctx.score_kmer_dev(ks, b["plane"].data_ptr(), b["pb"], b["off"].data_ptr(), b["len"].data_ptr(), b["ord"].data_ptr(), b["n"], params, b["sc"])
+            torch.cuda.synchronize()
+
+        # one call with the stage line on: the library writes it to file descriptor 2
+        replayed = None
+        with tempfile.TemporaryFile() as tmp:
+            saved = os.dup(2)
+            os.environ["FLX_API_TIMING"] = "1"
+            os.dup2(tmp.fileno(), 2)
+            try:
+                once()
+            finally:
+                os.dup2(saved, 2)
+                os.close(saved)
+                del os.environ["FLX_API_TIMING"]
+            tmp.seek(0)
+            m = re.search(rb"kmer long reads.*\((\d+) reads and (\d+) children of >= (\d+) bases, (\d+) words, (\d+) replayed\)", tmp.read())
+            if m:
+                replayed = dict(long_reads=int(m.group(1)), long_children=int(m.group(2)), threshold=int(m.group(3)), words=int(m.group(4)),
+                                words_replayed=int(m.group(5)))
+        for _ in range(max(0, args.warmup - 1)):
+            once()
+        ts, parts = [], {"flx_score_kmer_cover": [], "flx_score_kmer_fold": [], "flx_score_kmer_long": []}
+        for _ in range(steps):
+            ctx.timing_enable(True)
+            ctx.timing_reset()
+            t0 = time.perf_counter()
+            once()
+            ts.append((time.perf_counter() - t0) * 1e3)
+            for k in parts:
+                parts[k].append(ctx.timing_get(k)[0])
+            ctx.timing_enable(False)
+        nc = int(b["sc"].n_children)
+        res = [b["t"][k].cpu().numpy().copy() for k in ("mean", "win", "pass")] + [b["t"]["crng"][:2 * nc].cpu().numpy().copy(),
+                                                                                  b["t"]["cmean"][:nc].cpu().numpy().copy(), b["t"]["cwin"][:nc].cpu().numpy().copy()]
+        row = {"row": name, "mode": "trim+split500" if children else "plain", "reads": b["n"], "bases": b["bases"], "FLX_KMER_LONG_MIN": long_min,
+               "ms_per_step": round(float(np.median(ts)), 3), "children": nc}
+        for k, v in parts.items():
+            row[k + "_ms"] = round(float(np.median(v)), 3)
+        if replayed:
+            row.update(replayed)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        return row, res
+
+    same = True
+
+    def pair(name, b, children, steps=None):
+        nonlocal same
+        r_on, a = run(name, b, children, None, steps)
+        r_off, c = run(name, b, children, 0, steps)
+        same = same and all(x.shape == y.shape and (x.view(np.uint8) == y.view(np.uint8)).all() for x, y in zip(a, c))
+        return r_on, r_off
+
+    one = setup(np.zeros(0, dtype=np.int32), [long_read(4_000_000, 99)])
+    one_plain = pair("one_4mbp_read", one, False)
+    one_children = pair("one_4mbp_read", one, True)
+    del one
+    if args.crossover:
+        for e in range(16, 23):
+            b = setup(np.zeros(0, dtype=np.int32), [long_read(1 << e, 500 + e)])
+            run("one_read_2^%d" % e, b, False, 1 << 12, 3)  # (forced: the cooperative path at every length)
+            run("one_read_2^%d" % e, b, False, 0, 3)
+            del b
+    if args.reads > 0:
+        rng = np.random.default_rng(2024)
+        extra = [long_read(int(L), 7000 + i) for i, L in enumerate(rng.integers(500_000, 4_000_001, args.extra))]
+        withx = setup(synth.lengths(args.reads), extra)
+        pair("c3_shape+%d_ultralong" % args.extra, withx, False)
+        pair("c3_shape+%d_ultralong" % args.extra, withx, True)
+        del withx
+    os.environ.pop("FLX_KMER_LONG_MIN", None)
+    summary = {"summary": "ultra-long reads, k-mer mode, window %d" % args.window_size, "device": ctx.device_info()["name"],
+               "one_4mbp_long_ms": one_plain[0]["flx_score_kmer_long_ms"], "one_4mbp_one_lane_fold_ms": one_plain[1]["flx_score_kmer_fold_ms"],
+               "one_4mbp_children_long_ms": one_children[0]["flx_score_kmer_long_ms"],
+               "one_4mbp_children_one_lane_fold_ms": one_children[1]["flx_score_kmer_fold_ms"],
+               "same_bits_with_and_without_the_path": bool(same)}
+    print(json.dumps(summary), flush=True)
+    if args.out:
+        with open(args.out, "a") as fh:
+            for r in rows + [summary]:
+                fh.write(json.dumps(r) + "\n")
+    ks.close()
+    ctx.close()
+    return 0 if same else 1
 
 
 if __name__ == "__main__":
