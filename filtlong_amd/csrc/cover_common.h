@@ -4,6 +4,7 @@
 #pragma once
 #include "flx_internal.h"
 #include "kmerset.h"
+#include "cover_segments.h"
 
 #ifndef FLX_COVER_THREADS
 #define FLX_COVER_THREADS 256  // threads per workgroup of the wave-level cover kernels (their waves are independent)
@@ -72,7 +73,14 @@ struct CoverArgs {
     int32_t *count, *first, *last;
     // k_kmer_cover_q: a mark per slot of the processing order — the reads the first kernel hands to the one with a diagonal per lane
     uint8_t *redo;
+    // The cooperative path of long reads (cover_long.hip, cover_segments.h).  A batch launch leaves every read of at least long_min
+    // bases alone (kCoverNoLong: none): nothing folded, nothing written, never marked.  A segment launch (template flag SEGMENTS)
+    // runs on the segment table — offsets / lengths / cov_off / count / first / last / redo are the table's, one entry per virtual
+    // read, `order` is NULL — and `emit` holds every segment's emit range in its virtual read's coordinates
+    uint32_t long_min;
+    const int2 *emit;
 };
+constexpr uint32_t kCoverNoLong = 0xffffffffu;
 // (a pointer out of an integer: without the global address space on it every access would be a flat load with a 64-bit address
 // built in vector registers — one more vector instruction per access)
 #define FLX_GLOBAL_PTR(elem) const elem __attribute__((address_space(1))) *
@@ -80,4 +88,26 @@ struct CoverArgs {
 
 // cover_queue.hip: the cover kernel of round 6 (sets with a text); returns a HIP launch error through the context
 // (every_read_to_second: FLX_KMER_COVER=q2, tests — every read goes straight to the kernel with a diagonal per lane)
-int flx_cover_queue_launch(flx_ctx *ctx, const CoverArgs &args, bool has_prefilter, unsigned grid, bool every_read_to_second);
+// (segments: args name a segment table — the kernels' SEGMENTS instantiations)
+int flx_cover_queue_launch(flx_ctx *ctx, const CoverArgs &args, bool has_prefilter, unsigned grid, bool every_read_to_second, bool segments = false);
+
+// ---- cover_long.hip: the cooperative path of the coverage stage — long reads covered as segments, one wave each ----
+struct CoverLongCounts {  // counted by k_cov_row_bytes, read back with the coverage plane's size; the cursors serve the table kernel
+    unsigned long long n_reads, n_segs, read_cursor, seg_cursor;
+};
+struct CoverLong {
+    bool on = false;  // the path applies to this call
+    int thr = 0;      // reads of at least thr bases are covered in segments
+    int spans = 0;    // spans (1024 bases) per segment
+    CoverLongCounts n = {0, 0, 0, 0};
+    double t_start = 0.0;
+};
+// FLX_KMER_COVER_LONG_MIN / FLX_KMER_COVER_LONG_SPANS and the default rule -> cl (an invalid value of either switch: FLX_ERR_INVALID)
+int flx_cover_long_threshold(flx_ctx *ctx, uint64_t plane_bytes, bool applies, CoverLong *cl);
+size_t flx_cover_long_workspace(const CoverLongCounts &n);
+// builds the segment table in `work` (stream-ordered) and turns the batch's arguments into the segment launch's
+int flx_cover_long_table(flx_ctx *ctx, CoverLong &cl, const CoverArgs &batch, CoverLongCounts *d_counts, void *work, size_t work_bytes, CoverArgs *seg);
+// after the segment launch: every long read's count / first / last out of its segments', and the padding words of its row
+int flx_cover_long_reduce(flx_ctx *ctx, const CoverLong &cl, const CoverArgs &batch, void *work);
+// FLX_API_TIMING: the stage line (after the wait that ends the call's device work)
+void flx_cover_long_report(const CoverLong &cl);

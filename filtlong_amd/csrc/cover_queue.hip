@@ -211,7 +211,9 @@ __device__ __attribute__((noinline)) LaneDiag lane_diagonals(LdsPtr Sp, int lane
 // substitutions (whose seed finds the same diagonal) — is handed over: the wave drops it and appends it to a list (a.redo).  INDELS = true runs on that list afterwards and lets every lane follow a diagonal of its own (lane_diagonals
 // above).  Two kernels of one source because the lane-diagonal code inside the span loop cost the loop 21 spilled vector registers
 // and C3 a quarter of its speed (a cold call instead: a fifth — measured, profiles/r06_microbench.txt).
-template <bool HAS_PREFILTER, bool INDELS>
+// SEGMENTS: the launch on the segment table of the batch's long reads (cover_long.hip): a "read" is a virtual read [S, T) of a long
+// read, its row starts at the word of base S in that read's row, and only the pieces inside its emit range are written and counted.
+template <bool HAS_PREFILTER, bool INDELS, bool SEGMENTS = false>
 __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_q(const CoverArgs a) {
     __shared__ WaveLds lds_all[FLX_COVER_THREADS / 64];
     WaveLds &S = lds_all[threadIdx.x >> 6];
@@ -236,10 +238,17 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
         const uint64_t slot_r = slot_0 + (INDELS ? (uint64_t)(__ffsll((long long)marked) - 1) : 0ull);
         const uint32_t rid = __builtin_amdgcn_readfirstlane(order ? order[slot_r] : (uint32_t)slot_r);
         const int L = __builtin_amdgcn_readfirstlane(lengths[rid]);
+        if (!SEGMENTS && (uint32_t)L >= a.long_min) continue;  // a long read: covered in segments
         const uint8_t *seq = plane + offsets[rid];
         uint32_t *row = cov + (cov_off[rid] >> 2);
         const int row_words = (((L + 7) / 8 + 15) & ~15) >> 2;
         const int n_spans = (L + 1023) >> 10;
+        int emit_lo = 0, emit_hi = 0;  // SEGMENTS: multiples of 32, or the virtual read's end
+        if (SEGMENTS) {
+            const int2 er = a.emit[slot_r];
+            emit_lo = __builtin_amdgcn_readfirstlane(er.x);
+            emit_hi = __builtin_amdgcn_readfirstlane(er.y);
+        }
         int cnt = 0, fst = 0x7fffffff, lst = -1;
         // carried from lane 63 of the previous span (wave-uniform)
         uint32_t c_lo = 0, c_known15 = 0, c_t12 = 0;
@@ -301,6 +310,8 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
                 if (p0 >= L) c16 = 0;
                 else if (p0 + 16 > L) c16 &= (1u << (L - p0)) - 1u;
             }
+            const bool emitted = !SEGMENTS || (p0 >= emit_lo && p0 < emit_hi);  // (a piece lies inside the emit range or outside it)
+            if (!emitted) c16 = 0;
             cnt += __popc(c16);
             if (c16) {
                 fst = min(fst, p0 + (__ffs(c16) - 1));
@@ -308,7 +319,7 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
             }
             const uint32_t up = flx_from_right(c16, 0u);  // (only the even lanes write: lane 63's is never used)
             const int word = p0 >> 5;
-            if ((lane & 1) == 0 && word < row_words) __builtin_nontemporal_store(c16 | (up << 16), &row[(uint32_t)word]);
+            if ((lane & 1) == 0 && (SEGMENTS ? emitted : word < row_words)) __builtin_nontemporal_store(c16 | (up << 16), &row[(uint32_t)word]);
         };
 
         // ---- phase B: the first n (<= 64) entries of the queue, one per lane ----
@@ -813,13 +824,14 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
         while (q_n > 0) serve(q_n < 64 ? q_n : 64);
         wave_lds_sync();
         while (fin < n_spans) finalize(fin++);
-        for (int wd = n_spans * 32 + lane; wd < row_words; wd += 64) row[wd] = 0;  // (only L == 0 leaves words unwritten)
+        if (!SEGMENTS)
+            for (int wd = n_spans * 32 + lane; wd < row_words; wd += 64) row[wd] = 0;  // (only L == 0 leaves words unwritten)
         for (int o = 32; o > 0; o >>= 1) {
             cnt += __shfl_xor(cnt, o, 64);
             fst = min(fst, __shfl_xor(fst, o, 64));
             lst = max(lst, __shfl_xor(lst, o, 64));
         }
-        if (lane == 0) {
+        if (lane == 0) {  // (SEGMENTS: the segment's, in its virtual read's coordinates — flx_cover_long_reduce)
             count[rid] = cnt;
             first[rid] = cnt ? fst : -1;  // m_first_base_in_kmer / m_last_base_in_kmer, src/read.cpp:75-84
             last[rid] = cnt ? lst : -1;
@@ -831,20 +843,26 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
 
 }  // namespace
 
-int flx_cover_queue_launch(flx_ctx *ctx, const CoverArgs &args, bool has_prefilter, unsigned grid, bool every_read_to_second) {
+template <bool SEGMENTS>
+static void launch_both(flx_ctx *ctx, const CoverArgs &args, bool has_prefilter, unsigned grid, unsigned grid2, bool every_read_to_second) {
+    if (has_prefilter) {
+        if (!every_read_to_second) hipLaunchKernelGGL((k_kmer_cover_q<true, false, SEGMENTS>), dim3(grid), dim3(FLX_COVER_THREADS), 0, ctx->stream, args);
+        hipLaunchKernelGGL((k_kmer_cover_q<true, true, SEGMENTS>), dim3(grid2), dim3(FLX_COVER_THREADS), 0, ctx->stream, args);
+    } else {
+        if (!every_read_to_second) hipLaunchKernelGGL((k_kmer_cover_q<false, false, SEGMENTS>), dim3(grid), dim3(FLX_COVER_THREADS), 0, ctx->stream, args);
+        hipLaunchKernelGGL((k_kmer_cover_q<false, true, SEGMENTS>), dim3(grid2), dim3(FLX_COVER_THREADS), 0, ctx->stream, args);
+    }
+}
+
+int flx_cover_queue_launch(flx_ctx *ctx, const CoverArgs &args, bool has_prefilter, unsigned grid, bool every_read_to_second, bool segments) {
     if (!args.redo) return flx_fail(ctx, FLX_ERR_INVALID, "cover kernel: no room for the marks of reads with insertions / deletions");
     FLX_HIP(ctx, hipMemsetAsync(args.redo, every_read_to_second ? 1 : 0, args.n_reads, ctx->stream));
     // every read; then the reads the first kernel handed over (marked on the device: no host round trip, a grid of resident
     // workgroups walks the marks 64 at a time).  every_read_to_second (FLX_KMER_COVER=q2; tests): every read is marked beforehand and the
     // first kernel does not run — the second one must give the same bits on ANY read, not only on those that are handed to it
     const unsigned grid2 = std::min(grid, 8u * 256u);
-    if (has_prefilter) {
-        if (!every_read_to_second) hipLaunchKernelGGL((k_kmer_cover_q<true, false>), dim3(grid), dim3(FLX_COVER_THREADS), 0, ctx->stream, args);
-        hipLaunchKernelGGL((k_kmer_cover_q<true, true>), dim3(grid2), dim3(FLX_COVER_THREADS), 0, ctx->stream, args);
-    } else {
-        if (!every_read_to_second) hipLaunchKernelGGL((k_kmer_cover_q<false, false>), dim3(grid), dim3(FLX_COVER_THREADS), 0, ctx->stream, args);
-        hipLaunchKernelGGL((k_kmer_cover_q<false, true>), dim3(grid2), dim3(FLX_COVER_THREADS), 0, ctx->stream, args);
-    }
+    if (segments) launch_both<true>(ctx, args, has_prefilter, grid, grid2, every_read_to_second);
+    else launch_both<false>(ctx, args, has_prefilter, grid, grid2, every_read_to_second);
     FLX_HIP(ctx, hipGetLastError());
     return FLX_OK;
 }

@@ -66,7 +66,7 @@ static void build_phred_lut(double *lut257) {
 // and is ignored, as the reference would ignore it (round-5 review: a foreign FLX_FOO must not stop a drop-in binary).
 // (FLX_CLI_* belong to the command line, which checks its own.  tests/test_abi.py holds this list against the getenv calls in the sources.)
 static const char *const kKnownEnv[] = {
-    "FLX_API_TIMING", "FLX_KMER_COVER", "FLX_KMER_FOLD", "FLX_KMER_FOLD_EVENTS", "FLX_KMER_FOLD_GRID", "FLX_KMER_FOLD_STREAMS", "FLX_KMER_LOCUS", "FLX_KMER_LONG_MIN",
+    "FLX_API_TIMING", "FLX_KMER_COVER", "FLX_KMER_COVER_LONG_MIN", "FLX_KMER_COVER_LONG_SPANS", "FLX_KMER_FOLD", "FLX_KMER_FOLD_EVENTS", "FLX_KMER_FOLD_GRID", "FLX_KMER_FOLD_STREAMS", "FLX_KMER_LOCUS", "FLX_KMER_LONG_MIN",
     "FLX_KMER_LOCUS_BUILD", "FLX_KMER_PAIRTABLE", "FLX_KMER_PREFILTER", "FLX_KMER_SAFE1", "FLX_KMER_TEXT_ORDER", "FLX_PHRED_FUNNEL", "FLX_PHRED_KERNEL",
     "FLX_PHRED_LONG_MIN", "FLX_PHRED_TABLES", "FLX_RANK_EXACT", "FLX_RANK_SORT", "FLX_RCCL_LIB",
 };

@@ -260,7 +260,8 @@ __global__ void __launch_bounds__(COVER_THREADS) k_kmer_cover(const uint8_t *pla
 // may still occur elsewhere).  The diagonal comes from the seed table: eight lanes look their own 16 bases up (one far request
 // each) when the wave has none or the last 16 lanes of the previous span matched nowhere; a seed that fails leaves the old
 // diagonal in place as a hypothesis that costs nothing to test.
-template <bool HAS_PREFILTER, bool LOCUS>
+// SEGMENTS: the launch on the segment table of the batch's long reads (cover_long.hip), as in k_kmer_cover_q.
+template <bool HAS_PREFILTER, bool LOCUS, bool SEGMENTS = false>
 __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_w(const CoverArgs a) {
     const uint8_t *plane = a.plane;
     const uint64_t *offsets = a.offsets;
@@ -278,10 +279,17 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
     for (uint64_t slot = wave0; slot < n_reads; slot += n_waves) {
         const uint32_t rid = __builtin_amdgcn_readfirstlane(order ? order[slot] : (uint32_t)slot);
         const int L = __builtin_amdgcn_readfirstlane(lengths[rid]);
+        if (!SEGMENTS && (uint32_t)L >= a.long_min) continue;  // a long read: covered in segments
         const uint8_t *seq = plane + offsets[rid];
         uint32_t *row = cov + (cov_off[rid] >> 2);
         const int row_words = (((L + 7) / 8 + 15) & ~15) >> 2;
         const int n_spans = (L + 1023) >> 10;
+        int emit_lo = 0, emit_hi = 0;  // SEGMENTS: multiples of 32, or the virtual read's end
+        if (SEGMENTS) {
+            const int2 er = a.emit[slot];
+            emit_lo = __builtin_amdgcn_readfirstlane(er.x);
+            emit_hi = __builtin_amdgcn_readfirstlane(er.y);
+        }
         int cnt = 0, fst = 0x7fffffff, lst = -1;
         // carried from lane 63 of the previous span (wave-uniform)
         uint32_t c_lo = 0, c_p12 = 0, c_cand15 = 0, c_hit15 = 0;
@@ -326,6 +334,8 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
                 if (p0 >= L) c16 = 0;
                 else if (p0 + 16 > L) c16 &= (1u << (L - p0)) - 1u;
             }
+            const bool emitted = !SEGMENTS || (p0 >= emit_lo && p0 < emit_hi);  // (a piece lies inside the emit range or outside it)
+            if (!emitted) c16 = 0;
             cnt += __popc(c16);
             if (c16) {
                 fst = min(fst, p0 + (__ffs(c16) - 1));
@@ -333,7 +343,7 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
             }
             const uint32_t up = flx_from_right(c16, 0u);  // (only the even lanes write: lane 63's is never used)
             const int word = p0 >> 5;
-            if ((lane & 1) == 0 && word < row_words) __builtin_nontemporal_store(c16 | (up << 16), &row[(uint32_t)word]);
+            if ((lane & 1) == 0 && (SEGMENTS ? emitted : word < row_words)) __builtin_nontemporal_store(c16 | (up << 16), &row[(uint32_t)word]);
         };
 
         uint4 raw = make_uint4(0, 0, 0, 0);
@@ -708,13 +718,14 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
             }
         }
         if (n_spans > 0) finalize(n_spans - 1, prev_hits, 0u);
-        for (int wd = n_spans * 32 + lane; wd < row_words; wd += 64) row[wd] = 0;  // (only L == 0 leaves words unwritten)
+        if (!SEGMENTS)
+            for (int wd = n_spans * 32 + lane; wd < row_words; wd += 64) row[wd] = 0;  // (only L == 0 leaves words unwritten)
         for (int o = 32; o > 0; o >>= 1) {
             cnt += __shfl_xor(cnt, o, 64);
             fst = min(fst, __shfl_xor(fst, o, 64));
             lst = max(lst, __shfl_xor(lst, o, 64));
         }
-        if (lane == 0) {
+        if (lane == 0) {  // (SEGMENTS: the segment's, in its virtual read's coordinates — flx_cover_long_reduce)
             count[rid] = cnt;
             first[rid] = cnt ? fst : -1;  // m_first_base_in_kmer / m_last_base_in_kmer, src/read.cpp:75-84
             last[rid] = cnt ? lst : -1;
@@ -1301,8 +1312,10 @@ __global__ void __launch_bounds__(256) FLX_FOLD_OCC k_kmer_fold(const FoldArgs a
     }
 }
 
-// (long_min > 0: also counts the batch's long reads and their 32-position steps for the cooperative path, score_kmer_long.hip)
-__global__ void k_cov_row_bytes(uint64_t n, const int32_t *lengths, int64_t *row_bytes, int long_min, int ws, KmerLongCounts *long_reads) {
+// (long_min > 0: also counts the batch's long reads and their 32-position steps for the cooperative path, score_kmer_long.hip;
+// cover_min > 0: the reads the coverage stage covers in segments, and their segments — cover_long.hip)
+__global__ void k_cov_row_bytes(uint64_t n, const int32_t *lengths, int64_t *row_bytes, int long_min, int ws, KmerLongCounts *long_reads,
+                                int cover_min, int seg_bases, CoverLongCounts *cover_long) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int L = lengths[i];
@@ -1310,6 +1323,10 @@ __global__ void k_cov_row_bytes(uint64_t n, const int32_t *lengths, int64_t *row
     if (long_min > 0 && L >= long_min) {
         atomicAdd(&long_reads->n, 1ull);
         atomicAdd(&long_reads->words, flx_kmer_long_words(L, ws));
+    }
+    if (cover_min > 0 && L >= cover_min) {
+        atomicAdd(&cover_long->n_reads, 1ull);
+        atomicAdd(&cover_long->n_segs, (unsigned long long)flx_cover_seg_count(L, seg_bases));
     }
 }
 
@@ -1364,6 +1381,18 @@ static const char *const kFoldTimingNames[7][6][2] = {FLX_FOLD_NAMES_MODE(0), FL
                                                       FLX_FOLD_NAMES_MODE(4), FLX_FOLD_NAMES_MODE(5), FLX_FOLD_NAMES_MODE(6)};
 #undef FLX_FOLD_NAMES_MODE
 #undef FLX_FOLD_NAMES_PATH
+
+template <bool SEGMENTS>
+static void launch_cover_w(const CoverArgs &ca, bool prefilter, bool locus, unsigned grid, hipStream_t st) {
+    if (prefilter && locus)
+        hipLaunchKernelGGL((k_kmer_cover_w<true, true, SEGMENTS>), dim3(grid), dim3(FLX_COVER_THREADS), 0, st, ca);
+    else if (prefilter)
+        hipLaunchKernelGGL((k_kmer_cover_w<true, false, SEGMENTS>), dim3(grid), dim3(FLX_COVER_THREADS), 0, st, ca);
+    else if (locus)
+        hipLaunchKernelGGL((k_kmer_cover_w<false, true, SEGMENTS>), dim3(grid), dim3(FLX_COVER_THREADS), 0, st, ca);
+    else
+        hipLaunchKernelGGL((k_kmer_cover_w<false, false, SEGMENTS>), dim3(grid), dim3(FLX_COVER_THREADS), 0, st, ca);
+}
 
 template <int MODE>
 static int launch_fold(flx_ctx *ctx, FoldArgs &a) {
@@ -1430,6 +1459,15 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
     }
     KmerLong kl;
     FLX_CHECK(flx_kmer_long_threshold(ctx, plane_bytes, grid_on && !events_on && !fold_env0 && !(params->split_set && params->split < 32), &kl));
+    // FLX_KMER_COVER: "v2" = round 2's workgroup-per-read kernel, "w" = the wave-level kernel of rounds 3-5 for every set (second
+    // and third implementation; default: k_kmer_cover_q, cover_queue.hip, for a set with a text, k_kmer_cover_w for one without),
+    // "q2" = k_kmer_cover_q with EVERY read in its second launch (a diagonal per lane: tests)
+    const char *cover_env = getenv("FLX_KMER_COVER");
+    const bool old_cover = (cover_env && strcmp(cover_env, "v2") == 0) || !flx_kmerset_exact15(set);  // (no pair table: finalize found no room for it)
+    // The cooperative path of the coverage stage (cover_long.hip): long reads are covered as segments, one wave each, by the
+    // wave-level kernels — whatever the window size, --split and the fold variant; k_kmer_cover (v2) keeps them in its own launch
+    CoverLong cvl;
+    FLX_CHECK(flx_cover_long_threshold(ctx, plane_bytes, !old_cover, &cvl));
     const size_t small_bytes = 2 * up((n_reads + 1) * 8) + 3 * up(n_reads * 4) + up((n_reads + 1) * 4) + up(scan_ws) + up(n_reads) +
                                (inline_children ? up(n_reads * (size_t)kInlineChildren * 8) + up(64) : 0) + up(64);
     void *small = nullptr;
@@ -1447,30 +1485,41 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
     int32_t *d_inline = inline_children ? (int32_t *)carve(n_reads * (size_t)kInlineChildren * 8) : nullptr;
     unsigned int *d_overflow = inline_children ? (unsigned int *)carve(64) : nullptr;
     int32_t *first = out->first ? out->first : d_first_tmp, *last = out->last ? out->last : d_last_tmp;
-    kl.d_reads = (KmerLongCounts *)carve(64);  // the long reads' and (at + 1) the long children's counts
-    kl.d_children = kl.d_reads + 1;
+    // the counters of the cooperative paths, 64 bytes: the long reads' and (at + 1) the long children's counts for the folds, then
+    // the coverage stage's long reads and segments — zeroed by one memset, read back by one copy with the wait below
+    struct LongCounters {
+        KmerLongCounts reads, children;
+        CoverLongCounts cover;
+    };
+    static_assert(sizeof(LongCounters) == 64, "the counters' block");
+    LongCounters *d_counters = (LongCounters *)carve(64);
+    kl.d_reads = &d_counters->reads;
+    kl.d_children = &d_counters->children;
     FLX_HIP(ctx, hipMemsetAsync(d_rowb, 0, (n_reads + 1) * 8, st));
-    if (kl.on) FLX_HIP(ctx, hipMemsetAsync(kl.d_reads, 0, 2 * sizeof(KmerLongCounts), st));
-    hipLaunchKernelGGL(k_cov_row_bytes, dim3(nb), dim3(256), 0, st, n_reads, d_lengths, d_rowb, kl.on ? kl.thr : 0, params->window_size, kl.d_reads);
+    if (kl.on || cvl.on) FLX_HIP(ctx, hipMemsetAsync(d_counters, 0, sizeof(LongCounters), st));
+    hipLaunchKernelGGL(k_cov_row_bytes, dim3(nb), dim3(256), 0, st, n_reads, d_lengths, d_rowb, kl.on ? kl.thr : 0, params->window_size, kl.d_reads,
+                       cvl.on ? cvl.thr : 0, cvl.spans * 1024, &d_counters->cover);
     FLX_CHECK(flx_exclusive_scan_i64(ctx, n_reads + 1, d_rowb, d_covoff, d_scanws, scan_ws));
     int64_t cov_bytes = 0;
     KmerLongCounts long_reads = {0, 0}, long_children = {0, 0};
+    LongCounters counters;
+    memset(&counters, 0, sizeof counters);
     FLX_HIP(ctx, hipMemcpyAsync(&cov_bytes, d_covoff + n_reads, 8, hipMemcpyDeviceToHost, st));
-    if (kl.on) FLX_HIP(ctx, hipMemcpyAsync(&long_reads, kl.d_reads, sizeof long_reads, hipMemcpyDeviceToHost, st));  // (with the wait below)
+    if (kl.on || cvl.on) FLX_HIP(ctx, hipMemcpyAsync(&counters, d_counters, sizeof counters, hipMemcpyDeviceToHost, st));  // (with the wait below)
     FLX_HIP(ctx, hipStreamSynchronize(st));
+    long_reads = counters.reads;
+    cvl.n = counters.cover;
     void *d_cov = nullptr;
     const size_t cov_room = up((size_t)cov_bytes + 64), long_room = long_reads.n ? flx_kmer_long_reads_workspace(long_reads) : 0;
-    FLX_CHECK(flx_workspace(ctx, 1, cov_room + long_room, &d_cov));
+    const size_t cover_long_room = cvl.n.n_segs ? flx_cover_long_workspace(cvl.n) : 0;
+    const size_t cover_long_at = up(cov_room + long_room);
+    FLX_CHECK(flx_workspace(ctx, 1, cover_long_at + cover_long_room, &d_cov));
     void *d_long_reads = long_reads.n ? (char *)d_cov + cov_room : nullptr, *d_long_children = nullptr;
+    void *d_cover_long = cvl.n.n_segs ? (char *)d_cov + cover_long_at : nullptr;
 
     // ---- kernel 1: lookups -> coverage bits ----
     {
         const unsigned grid = (unsigned)std::min<uint64_t>(n_reads, 1u << 20);
-        // FLX_KMER_COVER: "v2" = round 2's workgroup-per-read kernel, "w" = the wave-level kernel of rounds 3-5 for every set (second
-        // and third implementation; default: k_kmer_cover_q, cover_queue.hip, for a set with a text, k_kmer_cover_w for one without),
-        // "q2" = k_kmer_cover_q with EVERY read in its second launch (a diagonal per lane: tests)
-        const char *cover_env = getenv("FLX_KMER_COVER");
-        const bool old_cover = (cover_env && strcmp(cover_env, "v2") == 0) || !flx_kmerset_exact15(set);  // (no pair table: finalize found no room for it)
         const bool wave_cover = cover_env && strcmp(cover_env, "w") == 0;
         const bool second_only = cover_env && strcmp(cover_env, "q2") == 0;  // every read through the kernel with a diagonal per lane (tests)
         flx_time_scope tc(ctx, "flx_score_kmer_cover");
@@ -1484,21 +1533,32 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
             memset(&none, 0, sizeof none);
             ctx->last_kmer_locus = lp != nullptr;
             const uint8_t *pre11 = flx_kmerset_pre11(set);
-            CoverArgs ca = {d_plane, d_offsets, d_lengths, d_order, n_reads, flx_kmerset_exact15(set), pre11, lp ? *lp : none, (uint32_t *)d_cov, (const uint64_t *)d_covoff, d_cnt, first, last, d_redo};
+            CoverArgs ca = {d_plane, d_offsets, d_lengths, d_order, n_reads, flx_kmerset_exact15(set), pre11, lp ? *lp : none, (uint32_t *)d_cov, (const uint64_t *)d_covoff, d_cnt, first, last, d_redo,
+                            cvl.on ? (uint32_t)cvl.thr : kCoverNoLong, nullptr};
             ctx->last_kmer_cover = (lp && !wave_cover) ? (second_only ? "q2" : "q") : "w";
-            if (lp && !wave_cover) {
+            // one launch of the form this call runs: on the batch, then (segments) on the segment table of its long reads
+            auto launch_cover = [&](const CoverArgs &args, unsigned g, bool segments) -> int {
+                if (lp && !wave_cover) return flx_cover_queue_launch(ctx, args, pre11 != nullptr, g, second_only, segments);
+                if (segments) launch_cover_w<true>(args, pre11 != nullptr, lp != nullptr, g, st);
+                else launch_cover_w<false>(args, pre11 != nullptr, lp != nullptr, g, st);
+                return FLX_OK;
+            };
+            if (lp && !wave_cover) {  // (the batch's marks: flx_last_kmer_handed_over does not count the segments')
                 ctx->last_kmer_redo = d_redo;
                 ctx->last_kmer_redo_n = n_reads;
-                const int rc = flx_cover_queue_launch(ctx, ca, pre11 != nullptr, wgrid, second_only);
-                if (rc != FLX_OK) return rc;
-            } else if (pre11 && lp)
-                hipLaunchKernelGGL((k_kmer_cover_w<true, true>), dim3(wgrid), dim3(FLX_COVER_THREADS), 0, st, ca);
-            else if (pre11)
-                hipLaunchKernelGGL((k_kmer_cover_w<true, false>), dim3(wgrid), dim3(FLX_COVER_THREADS), 0, st, ca);
-            else if (lp)
-                hipLaunchKernelGGL((k_kmer_cover_w<false, true>), dim3(wgrid), dim3(FLX_COVER_THREADS), 0, st, ca);
-            else
-                hipLaunchKernelGGL((k_kmer_cover_w<false, false>), dim3(wgrid), dim3(FLX_COVER_THREADS), 0, st, ca);
+            }
+            FLX_CHECK(launch_cover(ca, wgrid, false));
+            tc.end();
+            if (cvl.n.n_segs) {
+                // The long reads, one wave per segment.  A bracket of its own behind the batch's (brackets of one stage do not nest):
+                // flx_timing_get("flx_score_kmer_cover") still sums the whole stage's device time
+                flx_time_scope tl(ctx, "flx_score_kmer_cover.long");
+                CoverArgs sa;
+                FLX_CHECK(flx_cover_long_table(ctx, cvl, ca, &d_counters->cover, d_cover_long, cover_long_room, &sa));
+                const unsigned sgrid = (unsigned)std::min<uint64_t>((sa.n_reads + FLX_COVER_THREADS / 64 - 1) / (FLX_COVER_THREADS / 64), 1u << 22);
+                FLX_CHECK(launch_cover(sa, sgrid, true));
+                FLX_CHECK(flx_cover_long_reduce(ctx, cvl, ca, d_cover_long));
+            }
         } else {
         hipLaunchKernelGGL(k_kmer_cover<256>, dim3(grid), dim3(256), 0, st, d_plane, d_offsets, d_lengths, d_order, n_reads,
                            flx_kmerset_bitmap(set), flx_kmerset_prefilter(set), (uint32_t *)d_cov, (const uint64_t *)d_covoff, d_cnt, first,
@@ -1553,6 +1613,7 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
         if (out->child_offsets) FLX_HIP(ctx, hipMemsetAsync(out->child_offsets, 0, (n_reads + 1) * 8, st));
         FLX_HIP(ctx, hipGetLastError());
         FLX_HIP(ctx, hipStreamSynchronize(st));
+        flx_cover_long_report(cvl);
         return flx_kmer_long_report(ctx, kl, d_long_reads, nullptr);
     }
 
@@ -1625,5 +1686,6 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
     }
     FLX_HIP(ctx, hipGetLastError());
     FLX_HIP(ctx, hipStreamSynchronize(st));
+    flx_cover_long_report(cvl);
     return flx_kmer_long_report(ctx, kl, d_long_reads, d_long_children);
 }

@@ -44,7 +44,9 @@ def main():
     ap.add_argument("--centre", default="5,3", help="gamma shape,scale of the runs' Phred centres (5,3: mean 15; 9,1.8: mean 16, fewer low runs)")
     ap.add_argument("--out", default="")
     ap.add_argument("--kmer", action="store_true", help="k-mer mode: the cooperative folds of score_kmer_long.hip against FLX_KMER_LONG_MIN=0")
-    ap.add_argument("--crossover", action="store_true", help="--kmer: also one read of 2^16 .. 2^22 bases alone, with and without the path")
+    ap.add_argument("--crossover", action="store_true", help="--kmer: also one read of 2^16 .. 2^22 bases alone, with and without the paths, and "
+                    "the cover path's spans per segment (8 .. 128) on one 4 Mbp read")
+    ap.add_argument("--ultralong-only", type=int, default=2000, help="--kmer: reads of the ultralong_only row (0.1-4 Mbp each, nothing else; 0: no such row)")
     args = ap.parse_args()
     if args.kmer:
         return main_kmer(args)
@@ -155,12 +157,15 @@ def main():
 
 
 def main_kmer(args):
-    """k-mer mode (window 250, reference: 5 Mbp of random bases as an assembly).  Rows, each with the cooperative path (default
-    threshold) and without it (FLX_KMER_LONG_MIN=0), plain and with --trim --split 500:
+    """k-mer mode (window 250, reference: 5 Mbp of random bases as an assembly).  Rows, each with both cooperative paths (default
+    thresholds), with the cover path off (FLX_KMER_COVER_LONG_MIN=0) and with the folds' path off as well (FLX_KMER_LONG_MIN=0), plain
+    and with --trim --split 500:
       * a C3-shaped step of --reads reads plus --extra reads of 0.5-4 Mbp (tiled from the reference, 3 % substitutions, junk blocks);
-      * one 4 Mbp read alone;  with --crossover one read of 2^16 .. 2^22 bases alone.
-    Per row the device time of flx_score_kmer_cover, flx_score_kmer_fold and flx_score_kmer_long (medians over --steps), the wall
-    time per step, and the words the path replayed in floating point (from the FLX_API_TIMING stage line)."""
+      * one 4 Mbp read alone;  ultralong_only: --ultralong-only reads of 0.1-4 Mbp and nothing else (synthesised on the device);
+      * with --crossover one read of 2^16 .. 2^22 bases alone, and one 4 Mbp read at 8 .. 128 spans per segment of the cover path.
+    Per row the device time of flx_score_kmer_cover (the whole stage), flx_score_kmer_cover.long (its segment launches),
+    flx_score_kmer_fold and flx_score_kmer_long (medians over --steps), the wall time per step, and the words the folds' path replayed in
+    floating point (from the FLX_API_TIMING stage line)."""
     import re
     import tempfile
     import torch
@@ -225,12 +230,13 @@ def main_kmer(args):
         torch.cuda.synchronize()
         return dict(n=n, bases=int(lengths.astype(np.int64).sum()), plane=d_plane, pb=pb.value, off=d_off, len=d_len, ord=d_ord, t=t, sc=sc)
 
-    def run(name, b, children, long_min, steps=None):
+    def run(name, b, children, long_min, steps=None, cover_min=None, spans=None):
         steps = steps or args.steps
-        if long_min is None:
-            os.environ.pop("FLX_KMER_LONG_MIN", None)
-        else:
-            os.environ["FLX_KMER_LONG_MIN"] = str(long_min)
+        for key, value in (("FLX_KMER_LONG_MIN", long_min), ("FLX_KMER_COVER_LONG_MIN", cover_min), ("FLX_KMER_COVER_LONG_SPANS", spans)):
+            if value is None:
+                os.environ.pop(key, None)
+            else:
+                os.environ[key] = str(value)
         params = api.make_params(window_size=args.window_size, trim=children, split=500 if children else None)
 
         def once():
@@ -250,13 +256,15 @@ def main_kmer(args):
                 os.close(saved)
                 del os.environ["FLX_API_TIMING"]
             tmp.seek(0)
-            m = re.search(rb"kmer long reads.*\((\d+) reads and (\d+) children of >= (\d+) bases, (\d+) words, (\d+) replayed\)", tmp.read())
+            stage_lines = tmp.read()
+            m = re.search(rb"kmer long reads.*\((\d+) reads and (\d+) children of >= (\d+) bases, (\d+) words, (\d+) replayed\)", stage_lines)
+            mc = re.search(rb"kmer long cover.*\((\d+) reads of >= (\d+) bases in (\d+) segments of (\d+) spans\)", stage_lines)
             if m:
                 replayed = dict(long_reads=int(m.group(1)), long_children=int(m.group(2)), threshold=int(m.group(3)), words=int(m.group(4)),
                                 words_replayed=int(m.group(5)))
         for _ in range(max(0, args.warmup - 1)):
             once()
-        ts, parts = [], {"flx_score_kmer_cover": [], "flx_score_kmer_fold": [], "flx_score_kmer_long": []}
+        ts, parts = [], {"flx_score_kmer_cover": [], "flx_score_kmer_cover.long": [], "flx_score_kmer_fold": [], "flx_score_kmer_long": []}
         for _ in range(steps):
             ctx.timing_enable(True)
             ctx.timing_reset()
@@ -270,11 +278,13 @@ def main_kmer(args):
         res = [b["t"][k].cpu().numpy().copy() for k in ("mean", "win", "pass")] + [b["t"]["crng"][:2 * nc].cpu().numpy().copy(),
                                                                                   b["t"]["cmean"][:nc].cpu().numpy().copy(), b["t"]["cwin"][:nc].cpu().numpy().copy()]
         row = {"row": name, "mode": "trim+split500" if children else "plain", "reads": b["n"], "bases": b["bases"], "FLX_KMER_LONG_MIN": long_min,
-               "ms_per_step": round(float(np.median(ts)), 3), "children": nc}
+               "FLX_KMER_COVER_LONG_MIN": cover_min, "FLX_KMER_COVER_LONG_SPANS": spans, "ms_per_step": round(float(np.median(ts)), 3), "children": nc}
         for k, v in parts.items():
             row[k + "_ms"] = round(float(np.median(v)), 3)
         if replayed:
             row.update(replayed)
+        if mc:
+            row.update(cover_long_reads=int(mc.group(1)), cover_threshold=int(mc.group(2)), cover_segments=int(mc.group(3)), cover_spans=int(mc.group(4)))
         print(json.dumps(row), flush=True)
         rows.append(row)
         return row, res
@@ -284,9 +294,11 @@ def main_kmer(args):
     def pair(name, b, children, steps=None):
         nonlocal same
         r_on, a = run(name, b, children, None, steps)
-        r_off, c = run(name, b, children, 0, steps)
-        same = same and all(x.shape == y.shape and (x.view(np.uint8) == y.view(np.uint8)).all() for x, y in zip(a, c))
-        return r_on, r_off
+        r_cover_off, c0 = run(name, b, children, None, steps, cover_min=0)
+        r_off, c = run(name, b, children, 0, steps, cover_min=0)
+        for other in (c0, c):
+            same = same and all(x.shape == y.shape and (x.view(np.uint8) == y.view(np.uint8)).all() for x, y in zip(a, other))
+        return r_on, r_off, r_cover_off
 
     one = setup(np.zeros(0, dtype=np.int32), [long_read(4_000_000, 99)])
     one_plain = pair("one_4mbp_read", one, False)
@@ -295,9 +307,18 @@ def main_kmer(args):
     if args.crossover:
         for e in range(16, 23):
             b = setup(np.zeros(0, dtype=np.int32), [long_read(1 << e, 500 + e)])
-            run("one_read_2^%d" % e, b, False, 1 << 12, 3)  # (forced: the cooperative path at every length)
-            run("one_read_2^%d" % e, b, False, 0, 3)
+            run("one_read_2^%d" % e, b, False, 1 << 12, 3, cover_min=1 << 12)  # (forced: the cooperative paths at every length)
+            run("one_read_2^%d" % e, b, False, 0, 3, cover_min=0)
             del b
+        b = setup(np.zeros(0, dtype=np.int32), [long_read(4_000_000, 99)])
+        for spans in (8, 16, 32, 64, 128):
+            run("one_4mbp_read_spans_%d" % spans, b, False, None, 3, spans=spans)
+        del b
+    if args.ultralong_only > 0:
+        only = setup(np.random.default_rng(77).integers(100_000, 4_000_001, args.ultralong_only).astype(np.int32), [])
+        pair("ultralong_only", only, False, 3)
+        del only
+        torch.cuda.empty_cache()
     if args.reads > 0:
         rng = np.random.default_rng(2024)
         extra = [long_read(int(L), 7000 + i) for i, L in enumerate(rng.integers(500_000, 4_000_001, args.extra))]
@@ -305,8 +326,10 @@ def main_kmer(args):
         pair("c3_shape+%d_ultralong" % args.extra, withx, False)
         pair("c3_shape+%d_ultralong" % args.extra, withx, True)
         del withx
-    os.environ.pop("FLX_KMER_LONG_MIN", None)
+    for key in ("FLX_KMER_LONG_MIN", "FLX_KMER_COVER_LONG_MIN", "FLX_KMER_COVER_LONG_SPANS"):
+        os.environ.pop(key, None)
     summary = {"summary": "ultra-long reads, k-mer mode, window %d" % args.window_size, "device": ctx.device_info()["name"],
+               "one_4mbp_cover_ms": one_plain[0]["flx_score_kmer_cover_ms"], "one_4mbp_cover_one_wave_ms": one_plain[2]["flx_score_kmer_cover_ms"],
                "one_4mbp_long_ms": one_plain[0]["flx_score_kmer_long_ms"], "one_4mbp_one_lane_fold_ms": one_plain[1]["flx_score_kmer_fold_ms"],
                "one_4mbp_children_long_ms": one_children[0]["flx_score_kmer_long_ms"],
                "one_4mbp_children_one_lane_fold_ms": one_children[1]["flx_score_kmer_fold_ms"],
