@@ -1,6 +1,6 @@
 // cover_long.hip — the cooperative path of the coverage stage of k-mer mode: ultra-long reads covered as segments, one wave each.
 //
-// k_kmer_cover_q / k_kmer_cover_w give a read to ONE wave, which walks it span by span.  Inside a batch of 10^11 bases, longest
+// k_kmer_cover_q (cover_queue.hip) / k_kmer_cover_w (cover_wave.hip) give a read to ONE wave, which walks it span by span.  Inside a batch of 10^11 bases, longest
 // first, that hides a 4 Mbp read; in a streamed chunk or an ultra-long dataset of a few Gbases the read is a serial tail many times
 // the batch's own time.  Coverage is a pure function of the read and the set — base i is covered iff a member 16-mer starts in
 // [i - 15, i] (src/read.cpp:43-58) — and the text, seed and diagonal machinery of the kernels only takes exact shortcuts to those

@@ -2,7 +2,7 @@
 //
 // Reference semantics: the k-mer branch of Read::Read, src/read.cpp:43-58 — a rolling 2-bit 16-mer, one set lookup per position,
 // bases i-15..i marked on a hit; here: seq plane -> coverage bit plane + covered count / first / last covered base per read
-// (src/read.cpp:75-84).  Same outputs, bit for bit, as k_kmer_cover_w (score_kmer.hip), which stays as the second implementation
+// (src/read.cpp:75-84).  Same outputs, bit for bit, as k_kmer_cover_w (cover_wave.hip), which stays as the second implementation
 // (FLX_KMER_COVER=w) and is what a set without a text runs.
 //
 // Why a second structure.  k_kmer_cover_w is bound by its vector instructions (0.67 per position, profiles/r05_kmer_issue_mix_c3.txt):
@@ -136,64 +136,8 @@ __device__ __attribute__((noinline)) LaneDiag lane_diagonals(LdsPtr Sp, int lane
         const uint32_t b32 = flags32(w0y, w1y, w2y);                    // base i is the first of a piece
         const uint32_t u32 = flags32(w0y >> 16, w1y >> 16, w2y >> 16);  // a unique 13-mer starts at base i
         const uint32_t s32 = flags32(w0s, w1s, w2s);                    // the text's 16 bases from base i on are S1
-        auto mismatches = [](uint32_t x) -> uint32_t {  // bit j: base j of the 16 differs
-            uint32_t m = (x | (x >> 1)) & 0x55555555u;
-            m = (m | (m >> 1)) & 0x33333333u;
-            m = (m | (m >> 2)) & 0x0f0f0f0fu;
-            m = (m | (m >> 4)) & 0x00ff00ffu;
-            m = (m | (m >> 8)) & 0xffffu;
-            return __brev(m) >> 16;
-        };
-        const uint32_t z = ~(mismatches(hi ^ t_hi) | (mismatches(lo ^ t_own) << 16));  // bit i: base i of the window matches
-        uint32_t r = z & (z >> 1);
-        r &= r >> 2;
-        r &= r >> 4;
-        r &= r >> 8;  // bit i: bases i .. i + 15 match
-        uint32_t q = ~b32 >> 1;  // bit i: no piece starts at base i + 1
-        q &= q >> 1;
-        q &= q >> 2;
-        q &= q >> 4;
-        q &= q >> 7;  // bit i: none at i + 1 .. i + 15 — the 16 bases from i on lie in one piece of the text
-        {
-            uint32_t m12 = z & (z >> 1);
-            m12 &= m12 >> 2;
-            m12 &= m12 >> 4;
-            m12 &= m12 >> 4;  // bit i: bases i .. i + 11 match
-            uint32_t q12 = ~b32 >> 1;
-            q12 &= q12 >> 1;
-            q12 &= q12 >> 2;
-            q12 &= q12 >> 4;
-            q12 &= q12 >> 3;  // bit i: no piece starts at i + 1 .. i + 11
-            text12 |= ((m12 & q12) >> 5) & 0xffffu;
-        }
-        r &= q;
-        known |= (r >> 1) & valid16;
-        uint32_t g = z & (z >> 1);
-        g &= g >> 2;
-        g &= g >> 4;
-        g &= g >> 5;  // bit i: bases i .. i + 12 match the text
-        g &= u32;     // ... and that 13-mer occurs nowhere else
-        g |= g >> 1;
-        g |= g >> 2;
-        uint32_t one = ~z, two;  // S1: exactly one of the 16 bases from i on differs (saturating two-bit counter per window)
-        two = one & (one >> 1);
-        one ^= one >> 1;
-        {
-            const uint32_t t2 = two | (two >> 2) | (one & (one >> 2));
-            one = (one ^ (one >> 2)) & ~t2;
-            two = t2;
-        }
-        {
-            const uint32_t t2 = two | (two >> 4) | (one & (one >> 4));
-            one = (one ^ (one >> 4)) & ~t2;
-            two = t2;
-        }
-        {
-            const uint32_t t2 = two | (two >> 8) | (one & (one >> 8));
-            one = (one ^ (one >> 8)) & ~t2;
-        }
-        one &= q & s32;
-        refuted |= (((g & ~r) | one) >> 1) & valid16;
+        const uint32_t z = ~(mismatch16(hi ^ t_hi) | (mismatch16(lo ^ t_own) << 16));  // bit i: base i of the window matches
+        refuted |= text_verdict(z, b32, u32, s32, valid16, true, known, text12);
     };
     compare_at(dl);
     const int dleft = (int)flx_from_left((uint32_t)dl, (uint32_t)c_dl);
@@ -217,39 +161,20 @@ template <bool HAS_PREFILTER, bool INDELS, bool SEGMENTS = false>
 __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_q(const CoverArgs a) {
     __shared__ WaveLds lds_all[FLX_COVER_THREADS / 64];
     WaveLds &S = lds_all[threadIdx.x >> 6];
-    const uint8_t *plane = a.plane;
-    const uint64_t *offsets = a.offsets;
-    const int32_t *lengths = a.lengths;
-    const uint32_t *order = a.order;
-    const uint64_t n_reads = a.n_reads;
-    uint32_t *cov = a.cov;
-    const uint64_t *cov_off = a.cov_off;
-    int32_t *count = a.count, *first = a.first, *last = a.last;
-    const uint32_t loc_n_alloc = a.loc.n_alloc, loc_seed_mask = a.loc.seed_mask;
-    const int loc_seed_shift = a.loc.seed_shift;
     const int lane = threadIdx.x & 63;
     const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const LocusText text(a, lane);
     // INDELS: the wave takes 64 slots of the processing order at a time and serves the ones the first kernel has marked
-    for (uint64_t slot_0 = wave0 * (INDELS ? 64 : 1); slot_0 < n_reads; slot_0 += n_waves * (INDELS ? 64 : 1)) {
+    for (uint64_t slot_0 = wave0 * (INDELS ? 64 : 1); slot_0 < a.n_reads; slot_0 += n_waves * (INDELS ? 64 : 1)) {
       unsigned long long marked = 1ull;
-      if (INDELS) marked = __ballot(slot_0 + (uint64_t)lane < n_reads && a.redo[slot_0 + (uint64_t)lane] != 0);
+      if (INDELS) marked = __ballot(slot_0 + (uint64_t)lane < a.n_reads && a.redo[slot_0 + (uint64_t)lane] != 0);
       for (; marked; marked &= marked - 1) {
         const uint64_t slot_r = slot_0 + (INDELS ? (uint64_t)(__ffsll((long long)marked) - 1) : 0ull);
-        const uint32_t rid = __builtin_amdgcn_readfirstlane(order ? order[slot_r] : (uint32_t)slot_r);
-        const int L = __builtin_amdgcn_readfirstlane(lengths[rid]);
-        if (!SEGMENTS && (uint32_t)L >= a.long_min) continue;  // a long read: covered in segments
-        const uint8_t *seq = plane + offsets[rid];
-        uint32_t *row = cov + (cov_off[rid] >> 2);
-        const int row_words = (((L + 7) / 8 + 15) & ~15) >> 2;
-        const int n_spans = (L + 1023) >> 10;
-        int emit_lo = 0, emit_hi = 0;  // SEGMENTS: multiples of 32, or the virtual read's end
-        if (SEGMENTS) {
-            const int2 er = a.emit[slot_r];
-            emit_lo = __builtin_amdgcn_readfirstlane(er.x);
-            emit_hi = __builtin_amdgcn_readfirstlane(er.y);
-        }
-        int cnt = 0, fst = 0x7fffffff, lst = -1;
+        CoverRead rd;
+        if (!cover_read<SEGMENTS>(a, slot_r, rd)) continue;
+        const int L = rd.L, n_spans = rd.n_spans;
+        CoverTally tally;
         // carried from lane 63 of the previous span (wave-uniform)
         uint32_t c_lo = 0, c_known15 = 0, c_t12 = 0;
         // the diagonal (wave-uniform), the text of this span / the next one, lane 63's carries of the text comparison
@@ -258,7 +183,6 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
         uint32_t c_mb = 0xffffffffu /* mismatches | piece starts << 16 of lane 63 */, c_us = 0 /* its U13 | S1 << 16 */, c_twx = 0, c_twy = 0xffffu;
         uint2 tw = make_uint2(0, 0xffffu), tw_next = make_uint2(0, 0xffffu);
         uint32_t ts = 0, ts_next = 0, c_ts = 0;  // S1 bits of those text words (kmerset.h: safe1); lane 63's for the next span
-        const bool has_s1 = a.loc.safe1 != nullptr;
         // a read with insertions / deletions: every lane follows a diagonal of its own (below); c_dl = lane 63's shift against the
         // wave's diagonal as the next span sees it
         bool indel_mode = false;
@@ -267,59 +191,11 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
         // the queue: q_head = slot of the oldest entry, q_n = entries; fin = the next span to turn into coverage
         int q_head = 0, q_n = 0, fin = 0;
 
-        // the text word that holds the LAST base of the lane's 16 at this diagonal, for the lane whose 16 bases start at `base` +
-        // 16 * lane (index clamped into the padded array).  The diagonal and `base` are wave-uniform: the 64-bit part of the index
-        // is scalar work, a lane adds its number and clamps
-        auto word_index = [&](long long dg, int base) -> uint32_t {
-            long long u = ((dg + base + 15) >> 4) + (long long)kLocusPad;  // (16 * lane + c) >> 4 == lane + (c >> 4)
-            u = u < -64 ? -64 : (u > (long long)loc_n_alloc ? (long long)loc_n_alloc : u);
-            const int w = (int)u + lane;
-            return (uint32_t)max(0, min(w, (int)loc_n_alloc - 1));
-        };
-        auto text_word = [&](long long dg, int base) -> uint2 {
-            // (a 32-bit byte offset on a scalar base: one address register — the text has at most 2^28 positions, 2^27 bytes)
-            const uint64_t tv = *(FLX_GLOBAL_PTR(uint64_t))(FLX_KARG_PTR(uint8_t, loc.text) + (uint32_t)(word_index(dg, base) * 8u));
-            return make_uint2((uint32_t)tv, (uint32_t)(tv >> 32));
-        };
-        auto safe_word = [&](long long dg, int base) -> uint32_t {  // the S1 bits of that word
-            return has_s1 ? (uint32_t)*(FLX_GLOBAL_PTR(uint16_t))(FLX_KARG_PTR(uint8_t, loc.safe1) + (uint32_t)(word_index(dg, base) * 2u)) : 0u;
-        };
-
-        // the five words around the span's 64 that lanes on a shifted diagonal reach into: lanes 0..2 fetch W0 - 3 .. W0 - 1, lanes 3 and 4
-        // W0 + 64 and W0 + 65 (the others fetch a clamped word nobody uses)
-        auto edge_index = [&](long long dg, int base) -> uint32_t {
-            long long u = ((dg + base + 15) >> 4) + (long long)kLocusPad;
-            u = u < -64 ? -64 : (u > (long long)loc_n_alloc ? (long long)loc_n_alloc : u);
-            const int w = (int)u + (lane < 3 ? lane - 3 : lane + 61);
-            return (uint32_t)max(0, min(w, (int)loc_n_alloc - 1));
-        };
-
         // hits of span sp (complete in the ring) -> coverage bits, counts, row words
         auto finalize = [&](int sp) {
-            const int p0 = (sp << 10) + lane * 16;
             const uint32_t h = S.ring[sp & (kRing - 1)][lane];
             const uint32_t right_of_63 = sp + 1 < n_spans ? (uint32_t)S.ring[(sp + 1) & (kRing - 1)][0] : 0u;
-            const uint32_t next = flx_from_right(h, right_of_63);
-            uint32_t x = h | (next << 16);
-            x |= x >> 1;
-            x |= x >> 2;
-            x |= x >> 4;
-            x |= x >> 8;  // bit j = OR of hit bits j .. j+15: base p0+j lies in a member 16-mer (src/read.cpp:53-54)
-            uint32_t c16 = x & 0xffffu;
-            if (((sp + 1) << 10) > L) {  // (wave-uniform: only the read's last span has positions to cut off)
-                if (p0 >= L) c16 = 0;
-                else if (p0 + 16 > L) c16 &= (1u << (L - p0)) - 1u;
-            }
-            const bool emitted = !SEGMENTS || (p0 >= emit_lo && p0 < emit_hi);  // (a piece lies inside the emit range or outside it)
-            if (!emitted) c16 = 0;
-            cnt += __popc(c16);
-            if (c16) {
-                fst = min(fst, p0 + (__ffs(c16) - 1));
-                lst = max(lst, p0 + (32 - __clz(c16)));
-            }
-            const uint32_t up = flx_from_right(c16, 0u);  // (only the even lanes write: lane 63's is never used)
-            const int word = p0 >> 5;
-            if ((lane & 1) == 0 && (SEGMENTS ? emitted : word < row_words)) __builtin_nontemporal_store(c16 | (up << 16), &row[(uint32_t)word]);
+            emit_piece<SEGMENTS>(rd, sp, lane, h, flx_from_right(h, right_of_63), tally);
         };
 
         // ---- phase B: the first n (<= 64) entries of the queue, one per lane ----
@@ -342,12 +218,8 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
             if (__any(act && (id == 0 || (int)(id << 4) + 16 > L))) {
                 const int p0 = (int)(id << 4);
                 if (act) {
-                    if (p0 < 11) valid12 &= ~((1u << (11 - p0)) - 1u);
-                    if (p0 < 15) valid16 &= ~((1u << (15 - p0)) - 1u);
-                    if (p0 + 16 > L) {
-                        valid12 &= (1u << (L - p0)) - 1u;
-                        valid16 &= (1u << (L - p0)) - 1u;
-                    }
+                    valid12 = piece_valid_mask(p0, L, 12);
+                    valid16 = piece_valid_mask(p0, L, 16);
                 }
             }
             // ---- 12-mer prefilter over the 20 positions -4 .. 15 (bit i <-> position i - 4): pair k = positions 2k - 4, 2k - 3;
@@ -364,12 +236,7 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
                 // mismatch against the text, so it is absent more often than not.  Round 1 fetches the even pairs where needed; every
                 // 16-mer holds two or three of their positions, so most are out after it.  Round 2 fetches an odd pair only if one of
                 // the 16-mers that hold its 12-mers is still alive under the assumption that every 12-mer not yet seen is present.
-                // (the reverse complement of the whole 32-base window once: the canonical form of every pair's 11-mer is then one
-                // funnel shift, and a byte read for the other strand is looked at bit-reversed — kmerset.h, flx_pre11)
-                auto rc32 = [](uint32_t w) {
-                    const uint32_t r = __brev(w);
-                    return ~(((r >> 1) & 0x55555555u) | ((r & 0x55555555u) << 1));
-                };
+                // (the reverse complement of the whole 32-base window once: rc32, pre11_pair_index)
                 const uint64_t hl64 = ((uint64_t)hi << 32) | lo;
                 const uint64_t r64 = ((uint64_t)rc32(lo) << 32) | rc32(hi);
                 auto fetch = [&](uint32_t want, int parity) -> uint32_t {  // actual bits of the pairs k = parity, parity + 2, .. that hold a wanted position; 1 elsewhere
@@ -379,18 +246,13 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
                     for (int j = 0; j < 5; ++j) {
                         const int k = 2 * j + parity;
                         const uint32_t x13 = (uint32_t)(hl64 >> (36 - 4 * k));  // x.C.y, the 13 bases ending at position 2k - 3
-                        const uint32_t c = (x13 >> 2) & 0x3FFFFFu, rc = (uint32_t)(r64 >> (4 + 4 * k)) & 0x3FFFFFu;
-                        const uint32_t kk = (x13 & 0x2000u) ? rc : c;  // the middle base of C is G or T: the byte belongs to the other strand
-                        const uint32_t index = ((kk >> 12) << 11) | (kk & 0x7FFu);
-                        byte[j] = ((want >> (2 * k)) & 3u) ? pre11[index] : 0xffu;
+                        byte[j] = ((want >> (2 * k)) & 3u) ? pre11[pre11_pair_index(x13, (uint32_t)(r64 >> (4 + 4 * k)) & 0x3FFFFFu)] : 0xffu;
                     }
 #pragma unroll
                     for (int j = 0; j < 5; ++j) {
                         const int k = 2 * j + parity;
                         const uint32_t x13 = (uint32_t)(hl64 >> (36 - 4 * k));
-                        const uint32_t b = (x13 & 0x2000u) ? (__brev(byte[j]) >> 24) : byte[j];
-                        const uint32_t two = ((b >> ((x13 >> 24) & 3u)) & 1u) | (((b >> (4u + (x13 & 3u))) & 1u) << 1);
-                        got |= two << (2 * k);  // (a pair that was not fetched holds 0xff: both present)
+                        got |= pre11_pair_bits(x13, byte[j]) << (2 * k);  // (a pair that was not fetched holds 0xff: both present)
                     }
                     return got;
                 };
@@ -434,59 +296,23 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
             cand &= P >> 4;  // all five 12-mers present
             cand &= valid16 & (~refuted | known);  // (a member known on one diagonal cannot be refuted on another — its 13-mers then occur twice in the text — but nothing is lost by saying so)
 
-            // ---- exact membership: one byte of exact15 answers the pair of positions (a, a + 1), any a in 0..14 — the 15 bases
-            // ending at a are the byte's index, the base before them picks the bit of position a, the base after them the bit of
-            // a + 1.  A question from ABOVE (top-down search) takes the pair that ENDS at the asked position, one from below the
-            // pair that starts there: either way the request also settles the next candidate in the direction of the search. ----
+            // ---- exact membership and the search for the outermost members (exact_pair_probe, next_asks) ----
             uint32_t hits = known & cand, probed = known | (~cand & 0xffffu);
-            auto probe = [&](int top, int bot) {  // positions asked from above / from below, -1 = none
-                const int a0 = top > 0 ? top - 1 : 0, a1 = bot < 14 ? bot : 14;
-                uint32_t g0 = 0, g1 = 0;
-                FLX_GLOBAL_PTR(uint8_t) exact15 = FLX_KARG_PTR(uint8_t, exact15);
-                if (top >= 0) g0 = exact15[__builtin_amdgcn_alignbit(hi, lo, 30 - 2 * a0) & 0x3FFFFFFFu];
-                if (bot >= 0) g1 = exact15[__builtin_amdgcn_alignbit(hi, lo, 30 - 2 * a1) & 0x3FFFFFFFu];
-                if (top >= 0) {
-                    const uint32_t x = (hi >> (28 - 2 * a0)) & 3u, y = (lo >> (28 - 2 * a0)) & 3u;
-                    hits |= (((g0 >> x) & 1u) | (((g0 >> (4 + y)) & 1u) << 1)) << a0;
-                    probed |= 3u << a0;
-                }
-                if (bot >= 0) {
-                    const uint32_t x = (hi >> (28 - 2 * a1)) & 3u, y = (lo >> (28 - 2 * a1)) & 3u;
-                    hits |= (((g1 >> x) & 1u) | (((g1 >> (4 + y)) & 1u) << 1)) << a1;
-                    probed |= 3u << a1;
-                }
-                hits &= cand;  // positions outside the read hold no 16-mer
-            };
-            // One step of the search in the piece's window of 17 positions (bit 0 = the left neighbour's last position, bit j + 1 =
-            // position j): the highest open candidate above the confirmed members and the lowest one below them.
-            auto next_asks = [&](uint32_t left_member, int &top, int &bot) -> bool {
-                const uint32_t H = (hits << 1) | left_member;
-                const uint32_t open = (cand & ~probed) << 1;
-                uint32_t above = open, below = open;
-                if (H) {
-                    above = open & ~((2u << (31 - __clz(H))) - 1u);
-                    below = open & ((H & (0u - H)) - 1u);
-                }
-                top = above ? 30 - __clz(above) : -1;  // position = bit - 1
-                bot = below ? __ffs(below) - 2 : -1;
-                if (bot >= 0 && bot + 1 >= top && top >= 0) bot = -1;  // the two questions meet: the pair that ends at `top` answers both
-                return (top & bot) != -1;
-            };
             // the left neighbour's last position: a known member (exact, from phase A), or — where the left neighbour is the entry in
             // front of this one — what its own search finds.  First step on a BET: a candidate there is taken for a member (it is the
             // top of that piece's search, so its answer arrives with this round's), corrected right after.
             int top, bot;
             {
                 const uint32_t lcand = flx_from_left(cand >> 15, 0u);
-                const bool need = next_asks(lk | (adj ? lcand : 0u), top, bot);
-                if (__any(need)) probe(top, bot);
+                const bool need = next_asks(cand, hits, probed, lk | (adj ? lcand : 0u), top, bot);
+                if (__any(need)) exact_pair_probe(a, hi, lo, top, bot, cand, hits, probed);
             }
             const uint32_t lh = flx_from_left(hits >> 15, 0u);
             const uint32_t lhit = lk | (adj ? lh : 0u);
             for (;;) {
-                const bool need = next_asks(lhit, top, bot);
+                const bool need = next_asks(cand, hits, probed, lhit, top, bot);
                 if (!__any(need)) break;
-                probe(top, bot);
+                exact_pair_probe(a, hi, lo, top, bot, cand, hits, probed);
             }
             if (act) S.ring[(id >> 6) & (kRing - 1)][id & 63u] = (uint16_t)hits;
             q_head = (q_head + n) & (kQueue - 1);
@@ -496,14 +322,14 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
 
         uint4 raw = make_uint4(0, 0, 0, 0);
         // (offsets as unsigned 32-bit values: a uniform base plus a 32-bit lane offset is one address register, not two)
-        if (lane * 16 < L) raw = flx_plane16(seq + (uint32_t)(lane * 16));  // rows are 16-byte aligned and padded
+        if (lane * 16 < L) raw = flx_plane16(rd.seq + (uint32_t)(lane * 16));  // rows are 16-byte aligned and padded
         for (int sp = 0; sp < n_spans; ++sp) {
             const int p0 = (sp << 10) + lane * 16;
             uint4 raw_next = make_uint4(0, 0, 0, 0);
-            if (p0 + 1024 < L) raw_next = flx_plane16(seq + (uint32_t)(p0 + 1024));
+            if (p0 + 1024 < L) raw_next = flx_plane16(rd.seq + (uint32_t)(p0 + 1024));
             if (have_diag && !indel_mode && sp + 1 < n_spans) {  // (indel mode: the diagonal moves at the end of the span, the words are fetched there)
-                tw_next = text_word(diag, (sp << 10) + 1024);
-                ts_next = safe_word(diag, (sp << 10) + 1024);
+                tw_next = text.word(diag, (sp << 10) + 1024);
+                ts_next = text.safe(diag, (sp << 10) + 1024);
             }
             // 2 bits per base, earliest base on top: lo = my 16 bases, hi = the 16 before them
             const uint32_t lo = (codes4(raw.x) << 24) | (codes4(raw.y) << 16) | (codes4(raw.z) << 8) | codes4(raw.w);
@@ -513,9 +339,7 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
             if (sp > 0 && ((sp + 1) << 10) <= L) {  // (wave-uniform: a span inside the read has every position, no lane computes masks)
                 valid16 = 0xffffu;
             } else if (p0 < L) {
-                valid16 = 0xffffu;
-                if (p0 < 15) valid16 &= ~((1u << (15 - p0)) - 1u);
-                if (p0 + 16 > L) valid16 &= (1u << (L - p0)) - 1u;
+                valid16 = piece_valid_mask(p0, L, 16);
             }
             // ---- members known from the text along the diagonal ----
             uint32_t known = 0, refuted = 0;  // refuted: not a text match, but holds a text-matching 13-mer that occurs nowhere else (U13), or is one substitution away from a text window without such members (S1)
@@ -527,7 +351,7 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
                 auto compare = [&]() {
                     const int e = (int)((diag + 15) & 15);  // index of my last base in my word (p0 is a multiple of 16: the same for every lane)
                     // lane 0's left word: the carry, or behind a new seed a load (wave-uniform choice; only lane 0's copy is used)
-                    const uint2 tw0 = carry_ok ? make_uint2(c_twx, c_twy) : text_word(diag, (sp << 10) - 16);
+                    const uint2 tw0 = carry_ok ? make_uint2(c_twx, c_twy) : text.word(diag, (sp << 10) - 16);
                     uint2 twl;
                     twl.x = flx_from_left(tw.x, tw0.x);
                     twl.y = flx_from_left(tw.y, tw0.y);
@@ -542,73 +366,14 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
                     const uint32_t u_own = (((twl.y >> 16) >> (e + 1)) | ((tw.y >> 16) << (15 - e))) & 0xffffu;  // bit j: a unique 13-mer starts at my base j
                     const uint32_t s_own = ((tsl >> (e + 1)) | (ts << (15 - e))) & 0xffffu;  // bit j: the text's 16 bases from my base j on are S1
                     t_diag = t_own;
-                    const uint32_t x = lo ^ t_own;
-                    uint32_t m = (x | (x >> 1)) & 0x55555555u;  // even bit 2k: the base k places from the END differs
-                    m = (m | (m >> 1)) & 0x33333333u;
-                    m = (m | (m >> 2)) & 0x0f0f0f0fu;
-                    m = (m | (m >> 4)) & 0x00ff00ffu;
-                    m = (m | (m >> 8)) & 0xffffu;
-                    const uint32_t mml = __brev(m) >> 16;  // bit j: my base j differs from the text
+                    const uint32_t mml = mismatch16(lo ^ t_own);  // bit j: my base j differs from the text
                     mm_cnt = __popc(mml);
                     const uint32_t mmh = flx_from_left(mml, mb0 & 0xffffu);
                     uint32_t bh = 0;
                     if (any_start) bh = flx_from_left(b_own, mb0 >> 16);
                     const uint32_t uh = flx_from_left(u_own, us0 & 0xffffu), sh = flx_from_left(s_own, us0 >> 16);
                     const uint32_t z = ~(mmh | (mml << 16));  // bit i: base i of the window [p0 - 16, p0 + 16) matches
-                    uint32_t r = z & (z >> 1);
-                    r &= r >> 2;
-                    r &= r >> 4;
-                    r &= r >> 8;  // bit i: bases i .. i + 15 match
-                    uint32_t q = 0xffffffffu, q12 = 0xffffffffu;  // (no piece start in sight: every window lies inside one piece)
-                    if (any_start) {
-                        q = ~(bh | (b_own << 16)) >> 1;  // bit i: no piece starts at base i + 1
-                        q &= q >> 1;
-                        q &= q >> 2;
-                        q &= q >> 4;
-                        q &= q >> 7;  // bit i: none at i + 1 .. i + 15 — the 16 bases from i on lie in one piece of the text
-                        q12 = ~(bh | (b_own << 16)) >> 1;
-                        q12 &= q12 >> 1;
-                        q12 &= q12 >> 2;
-                        q12 &= q12 >> 4;
-                        q12 &= q12 >> 3;  // bit i: no piece starts at i + 1 .. i + 11 (a piece has at least 16 bases: the 12-mer lies in one of its 16-mers)
-                    }
-                    {
-                        uint32_t m12 = z & (z >> 1);
-                        m12 &= m12 >> 2;
-                        m12 &= m12 >> 4;
-                        m12 &= m12 >> 4;  // bit i: bases i .. i + 11 match
-                        text12 |= ((m12 & q12) >> 5) & 0xffffu;  // the 12-mer ending at my position j starts at base j + 5
-                    }
-                    r &= q;
-                    known |= (r >> 1) & valid16;  // the 16-mer ending at my position j starts at base j + 1 of the window
-                    uint32_t g = z & (z >> 1);
-                    g &= g >> 2;
-                    g &= g >> 4;
-                    g &= g >> 5;  // bit i: bases i .. i + 12 match the text
-                    g &= uh | (u_own << 16);  // ... and that 13-mer occurs nowhere else (U13 is only set inside one piece)
-                    g |= g >> 1;
-                    g |= g >> 2;  // bit i: such a 13-mer starts at base i, i + 1, i + 2 or i + 3: inside the 16 bases from i on
-                    // S1: exactly ONE of the 16 bases from i on differs from the text, and no 16-mer one base away from the text's is a
-                    // member (counted with a saturating two-bit counter per window: `one` = exactly one mismatch, `two` = more)
-                    uint32_t one = ~z, two;
-                    two = one & (one >> 1);
-                    one ^= one >> 1;
-                    {
-                        const uint32_t t2 = two | (two >> 2) | (one & (one >> 2));
-                        one = (one ^ (one >> 2)) & ~t2;
-                        two = t2;
-                    }
-                    {
-                        const uint32_t t2 = two | (two >> 4) | (one & (one >> 4));
-                        one = (one ^ (one >> 4)) & ~t2;
-                        two = t2;
-                    }
-                    {
-                        const uint32_t t2 = two | (two >> 8) | (one & (one >> 8));
-                        one = (one ^ (one >> 8)) & ~t2;
-                    }
-                    one &= q & (sh | (s_own << 16));
-                    uint32_t rf = (((g & ~r) | one) >> 1) & valid16;
+                    uint32_t rf = text_verdict(z, bh | (b_own << 16), uh | (u_own << 16), sh | (s_own << 16), valid16, any_start, known, text12);
                     // (lane 0 behind a new seed knows nothing about the 16 bases in front of it — taken for mismatches above, which is
                     // safe for `known` and would be wrong here: only the window made of its own 16 bases can be refuted)
                     if (lane == 0 && !carry_ok) rf &= 0x8000u;
@@ -647,23 +412,7 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
                         tries = (lane & (seeds_left == FLX_LOCUS_SEEDS - 1 ? 31 : 7)) == 3 && ((whole >> lane) & 1ull);
                     }
                     uint32_t tpos = kLocusEmpty;
-                    if (tries) {
-                        uint32_t h = flx_locus_hash(lo, loc_seed_shift);
-                        FLX_GLOBAL_PTR(uint32_t) seed_tab = FLX_KARG_PTR(uint32_t, loc.seed);
-                        FLX_GLOBAL_PTR(uint32_t) seed_text = FLX_KARG_PTR(uint32_t, loc.text);  // (.x of text word i at dword 2 i)
-#pragma unroll 1
-                        for (int probe_no = 0; probe_no < 4; ++probe_no) {
-                            const uint32_t v = seed_tab[h];
-                            if (v == kLocusEmpty) break;
-                            {  // (flx_locus_kmer_at, kmerset.h, on the global-space pointer)
-                                const uint32_t tw_i = (v >> 4) + kLocusPad, ts_i = v & 15u;
-                                const uint32_t t0 = seed_text[2 * tw_i];
-                                const uint32_t at = ts_i == 0 ? t0 : __builtin_amdgcn_alignbit(t0, seed_text[2 * tw_i + 2], 32 - 2 * ts_i);
-                                if (at == lo) { tpos = v; break; }
-                            }
-                            h = (h + 1) & loc_seed_mask;
-                        }
-                    }
+                    if (tries) tpos = text.seed(lo);
                     const unsigned long long found = __ballot(tpos != kLocusEmpty);
                     if (!found) {
                         if (!kn && seeds_left == FLX_LOCUS_SEEDS - 1) {  // the two first lanes held no exact 16-mer: eight more
@@ -682,11 +431,11 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
                     diag = nd;
                     have_diag = true;
                     carry_ok = false;
-                    tw = text_word(diag, sp << 10);
-                    ts = safe_word(diag, sp << 10);
+                    tw = text.word(diag, sp << 10);
+                    ts = text.safe(diag, sp << 10);
                     if (sp + 1 < n_spans) {
-                        tw_next = text_word(diag, (sp << 10) + 1024);
-                        ts_next = safe_word(diag, (sp << 10) + 1024);
+                        tw_next = text.word(diag, (sp << 10) + 1024);
+                        ts_next = text.safe(diag, (sp << 10) + 1024);
                     }
                     again = true;
                 }
@@ -723,13 +472,14 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
                 if (INDELS && !indel_mode && have_diag) lane_diag = __popcll(__ballot(((valid16 >> 15) != 0) && mm_cnt >= 6)) >= 4;
                 if (INDELS && lane_diag && have_diag) {
                     const int e = (int)((diag + 15) & 15);
-                    const uint32_t xi = edge_index(diag, sp << 10);
+                    // the five words around the span's 64 that lanes on a shifted diagonal reach into: lanes 0..2 fetch W0 - 3 .. W0 - 1,
+                    // lanes 3 and 4 W0 + 64 and W0 + 65
+                    const uint32_t xi = text.index(diag, sp << 10, lane < 3 ? lane - 3 : lane + 61);
                     uint2 xw = make_uint2(0, 0xffffu);
                     uint32_t xs = 0;
                     if (lane < 5) {
-                        const uint64_t tv = *(FLX_GLOBAL_PTR(uint64_t))(FLX_KARG_PTR(uint8_t, loc.text) + (uint32_t)(xi * 8u));
-                        xw = make_uint2((uint32_t)tv, (uint32_t)(tv >> 32));
-                        if (has_s1) xs = (uint32_t)*(FLX_GLOBAL_PTR(uint16_t))(FLX_KARG_PTR(uint8_t, loc.safe1) + (uint32_t)(xi * 2u));
+                        xw = text.word_at(xi);
+                        xs = text.safe_at(xi);
                     }
                     // (a function of its own, not inlined: inside the span loop its registers cost the loop 21 spilled vector registers
                     // and C3 a quarter of its speed — measured; the call is on the cold side of a wave-uniform branch)
@@ -751,8 +501,8 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
                     if (was_indel_mode || indel_mode) {  // (the span's own prefetch was left out, or the diagonal has moved)
                         diag += step;
                         if (sp + 1 < n_spans) {
-                            tw_next = text_word(diag, (sp << 10) + 1024);
-                            ts_next = safe_word(diag, (sp << 10) + 1024);
+                            tw_next = text.word(diag, (sp << 10) + 1024);
+                            ts_next = text.safe(diag, (sp << 10) + 1024);
                         }
                     }
                 } else {
@@ -824,18 +574,7 @@ __global__ void __launch_bounds__(FLX_COVER_THREADS) FLX_COVER_OCC k_kmer_cover_
         while (q_n > 0) serve(q_n < 64 ? q_n : 64);
         wave_lds_sync();
         while (fin < n_spans) finalize(fin++);
-        if (!SEGMENTS)
-            for (int wd = n_spans * 32 + lane; wd < row_words; wd += 64) row[wd] = 0;  // (only L == 0 leaves words unwritten)
-        for (int o = 32; o > 0; o >>= 1) {
-            cnt += __shfl_xor(cnt, o, 64);
-            fst = min(fst, __shfl_xor(fst, o, 64));
-            lst = max(lst, __shfl_xor(lst, o, 64));
-        }
-        if (lane == 0) {  // (SEGMENTS: the segment's, in its virtual read's coordinates — flx_cover_long_reduce)
-            count[rid] = cnt;
-            first[rid] = cnt ? fst : -1;  // m_first_base_in_kmer / m_last_base_in_kmer, src/read.cpp:75-84
-            last[rid] = cnt ? lst : -1;
-        }
+        wave_reduce_and_store<SEGMENTS>(a, rd, lane, tally);
         wave_lds_sync();  // (the next read's first span must not overtake this read's last ring reads)
       }
     }

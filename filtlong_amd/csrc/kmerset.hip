@@ -719,7 +719,7 @@ extern "C" int flx_kmerset_finalize(flx_kmerset *s) {
         FLX_HIP(ctx, hipStreamSynchronize(st));
     }
     if (sz > 0) {  // the pair form of the exact bitmap (what the cover kernel asks)
-        // (no room for it: the set works without — scoring then takes the kernel that asks the 512 MiB bitmap, score_kmer.hip: k_kmer_cover)
+        // (no room for it: the set works without — scoring then takes the kernel that asks the 512 MiB bitmap, cover_wave.hip: k_kmer_cover)
         const char *pt = getenv("FLX_KMER_PAIRTABLE");  // "0": as if the allocation had failed (tests)
         hipError_t e = (pt && pt[0] == '0') ? hipErrorOutOfMemory : hipMalloc((void **)&s->exact15, (size_t)1 << 30);
         if (e != hipSuccess) {

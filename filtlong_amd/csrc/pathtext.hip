@@ -1,5 +1,5 @@
 // pathtext.hip — a 16-mer set without an assembly (short reads, src/kmers.cpp:142-166) as a TEXT for the locus path of the cover
-// kernel (kmerset.h: flx_locus; score_kmer.hip: k_kmer_cover_w<.., LOCUS>).
+// kernel (kmerset.h: flx_locus; cover_wave.hip: k_kmer_cover_w<.., LOCUS>, cover_queue.hip: k_kmer_cover_q).
 //
 // The locus path needs a text in which every 16-base window inside one piece is a member, and — for the refutation by unique
 // 13-mers — in which every member IS such a window.  An assembly is that text for its own 16-mers.  For any other set the

@@ -392,11 +392,14 @@ def test_reads2_gather_matches_oracle(ctx, be, synth):
     assert len(ctx.reads2_gather(np.zeros(0, np.int32), empty)["mean_q"]) == 0
 
 
-def test_cover_kernel_boundaries_vs_oracle(be, synth):
-    """The wave-level coverage kernel at its seams, against the oracle: read lengths around its lane (16) and span (1024) sizes, a
+def test_cover_kernel_boundaries_vs_oracle(ctx, be, synth, monkeypatch):
+    """The coverage kernels at their seams, against the oracle: read lengths around their lane (16) and span (1024) sizes, a
     single error / a run of errors placed exactly at lane and span boundaries, isolated members (one clean 16-mer in noise),
     clean reads (the far-first mode), homopolymers and tandem repeats (every position the same few 16-mers), the reverse strand,
-    non-ACGT bytes — each with and without the prefilter, and with --trim / --split so that first / last / children are checked."""
+    non-ACGT bytes — each with and without the prefilter, and with --trim / --split so that first / last / children are checked.
+    Every form of the stage runs the batch (they share the filter's rules through cover_common.h: a rule changed for one form only
+    shows here): the default, the kernel with a diagonal per lane for every read, the wave-level kernel with and without the text,
+    and the workgroup-per-read kernel."""
     import os
     contigs = synth["contigs"]
     c0 = contigs[0]
@@ -431,6 +434,11 @@ def test_cover_kernel_boundaries_vs_oracle(be, synth):
     # a reference that holds the homopolymer and the repeats as well
     ref = contigs + [b"A" * 300, b"AC" * 200, c0[100:400] + b"ACG" * 100]
     orc = _oracle.KmerSet(); orc.add_assembly(ref)
+    # (switches, what ctx.last_kmer_cover() must name, whether the text is in use)
+    forms = (({}, "q", True), ({"FLX_KMER_COVER": "q2"}, "q2", True), ({"FLX_KMER_COVER": "w"}, "w", True),
+             ({"FLX_KMER_COVER": "v2"}, "v2", False), ({"FLX_KMER_LOCUS": "0"}, "w", False))
+    for name in ("FLX_KMER_COVER", "FLX_KMER_LOCUS"):
+        monkeypatch.delenv(name, raising=False)
     for pf in ("1", "0"):
         os.environ["FLX_KMER_PREFILTER"] = pf
         try:
@@ -439,15 +447,20 @@ def test_cover_kernel_boundaries_vs_oracle(be, synth):
             del os.environ["FLX_KMER_PREFILTER"]
         assert len(ks) == len(orc)
         for pkw in (dict(), dict(trim=True, split=20), dict(trim=True, split=300, window_size=40)):
-            got = be.score(reads, pkw, ks)
             p = _oracle.make_params(**pkw)
-            for (name, seq, q), o in zip(reads, got):
-                w = _oracle.score_read(seq, q, p, orc, cap=65536)
-                assert w["mean_q"] == o["mean_q"] and w["window_q"] == o["window_q"], (name, pf, pkw, w["mean_q"], o["mean_q"])
-                assert (w["first"], w["last"], w["passed"]) == (o["first"], o["last"], o["passed"]), (name, pf, pkw)
-                assert w["child_ranges"] == o["child_ranges"], (name, pf, pkw)
-                for wc, oc in zip(w["children"], o["children"]):
-                    assert wc["mean_q"] == oc["mean_q"] and wc["window_q"] == oc["window_q"] and wc["passed"] == oc["passed"], (name, pf, pkw)
+            want = [_oracle.score_read(seq, q, p, orc, cap=65536) for _, seq, q in reads]
+            for env, form, locus in forms:
+                with monkeypatch.context() as mp:
+                    for k, v in env.items():
+                        mp.setenv(k, v)
+                    got = be.score(reads, pkw, ks)
+                assert (ctx.last_kmer_cover(), ctx.last_kmer_locus()) == (form, locus), (env, pf)
+                for (name, seq, q), w, o in zip(reads, want, got):
+                    assert w["mean_q"] == o["mean_q"] and w["window_q"] == o["window_q"], (name, pf, pkw, env, w["mean_q"], o["mean_q"])
+                    assert (w["first"], w["last"], w["passed"]) == (o["first"], o["last"], o["passed"]), (name, pf, pkw, env)
+                    assert w["child_ranges"] == o["child_ranges"], (name, pf, pkw, env)
+                    for wc, oc in zip(w["children"], o["children"]):
+                        assert wc["mean_q"] == oc["mean_q"] and wc["window_q"] == oc["window_q"] and wc["passed"] == oc["passed"], (name, pf, pkw, env)
 
 
 def _text_codes(contigs):

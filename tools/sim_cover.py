@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Host-side model of the wave-level cover kernel's lookups (csrc/score_kmer.hip, k_kmer_cover_w) on the synthetic C3 reads:
+"""Host-side model of the wave-level cover kernel's lookups (csrc/cover_wave.hip, k_kmer_cover_w) on the synthetic C3 reads:
 how many far requests (exact-membership lookups) and rounds a lane needs when ONE request answers G consecutive positions
 (G = 1: a bit per 16-mer; 2: the exact15 pair table; 4 / 5: wider groups), with groups at fixed alignment or floating (the
 request is placed so that its range ends at the asked position); "+ locus": the members along the read's own locus in the assembly

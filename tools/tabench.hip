@@ -1,5 +1,5 @@
 // tabench.hip — what a random table lookup costs on MI355X by WHERE the table lives and HOW the lanes of one instruction
-// spread over cache lines.  Input for the k-mer cover kernel (csrc/score_kmer.hip): its two request classes are 4-byte
+// spread over cache lines.  Input for the k-mer cover kernel (csrc/cover_wave.hip, csrc/cover_queue.hip): its two request classes are 4-byte
 // lookups into an L2-resident 2 MiB table (12-mer prefilter) and into a 512 MiB bitmap (one fabric request each).
 //   (1) plain / nt / sc1 loads, table 16 KiB .. 2 MiB .. 512 MiB, every lane its own random line
 //   (2) G lanes of an instruction share one 128-byte line (G = 1 .. 64), 2 MiB table: is the price per LANE or per LINE?
