@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "flx_kmerset_add_short_reads", "flx_kmerset_finalize", "flx_kmerset_size", "flx_kmerset_contains",
     "flx_last_phred_kernel", "flx_last_kmer_locus", "flx_last_kmer_fold_grid", "flx_last_kmer_cover", "flx_last_kmer_handed_over", "flx_synth_qual_dev", "flx_synth_qual_profile_dev", "flx_synth_seq_dev", "flx_synth_seq_profile_dev",
     "flx_bgzf_bound", "flx_bgzf_compress_dev", "flx_bgzf_create", "flx_bgzf_compress", "flx_bgzf_destroy",
+    "flx_summary_q_edges", "flx_summary_dev", "flx_summary",
 ]
 
 
@@ -69,6 +70,22 @@ class CutReport(C.Structure):
         ("exact_fallback", C.c_int32),
         ("mean_quality", C.c_double), ("stdev_quality", C.c_double), ("min_z", C.c_double), ("max_z", C.c_double),
         ("audited", C.c_uint64),
+    ]
+
+
+SUMMARY_LEN_BINS, SUMMARY_Q_BINS = 32, 52
+
+
+class Summary(C.Structure):
+    """struct flx_summary"""
+    _fields_ = [
+        ("n", C.c_uint64), ("bases", C.c_uint64),
+        ("min_length", C.c_int32), ("max_length", C.c_int32),
+        ("median_length", C.c_int32), ("_pad0", C.c_int32),
+        ("nx", C.c_int32 * 9), ("_pad1", C.c_int32),
+        ("len_count", C.c_uint64 * SUMMARY_LEN_BINS), ("len_bases", C.c_uint64 * SUMMARY_LEN_BINS),
+        ("mean_q_count", C.c_uint64 * SUMMARY_Q_BINS), ("mean_q_bases", C.c_uint64 * SUMMARY_Q_BINS),
+        ("window_q_count", C.c_uint64 * SUMMARY_Q_BINS), ("window_q_bases", C.c_uint64 * SUMMARY_Q_BINS),
     ]
 
 
@@ -173,5 +190,8 @@ def load():
     L.flx_bgzf_compress.argtypes = [vp, vp, u64, i32, vp, u64, C.POINTER(u64)]
     L.flx_bgzf_destroy.argtypes = [vp]
     L.flx_bgzf_destroy.restype = None
+    L.flx_summary_q_edges.argtypes = [vp]
+    L.flx_summary_dev.argtypes = [vp, u64, vp, vp, vp, vp, i32, C.POINTER(Summary)]
+    L.flx_summary.argtypes = [vp, u64, vp, vp, vp, vp, i32, C.POINTER(Summary)]
     _lib = L
     return L

@@ -391,6 +391,53 @@ class Context:
         self._check(self.L.flx_bgzf_compress_dev(self.h, d_in, int(n), BGZF_EOF if eof else 0, d_out, int(out_cap), C.byref(got)))
         return got.value
 
+    # ---- read summary (include/filtlong_hip.h, flx_summary*) ------------------------------------------------------
+    def summary(self, lengths, mean_q=None, window_q=None, mask=None, global_=False):
+        """flx_summary over host arrays: the struct's fields as a dictionary (integers and lists of integers).  `mask`:
+        entries with a non-zero byte count (None: all).  global_: collective over the context's communicator."""
+        ln = np.ascontiguousarray(lengths, dtype=np.int32)
+        n = len(ln)
+        mq = None if mean_q is None else np.ascontiguousarray(mean_q, dtype=np.float64)
+        wq = None if window_q is None else np.ascontiguousarray(window_q, dtype=np.float64)
+        mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        for a in (mq, wq, mk):
+            if a is not None and len(a) != n:
+                raise ValueError("summary: arrays of different lengths")
+        out = _lib.Summary()
+        self._check(self.L.flx_summary(self.h, n, ln.ctypes.data, None if mq is None else mq.ctypes.data,
+                                       None if wq is None else wq.ctypes.data, None if mk is None else mk.ctypes.data,
+                                       1 if global_ else 0, C.byref(out)))
+        return summary_dict(out)
+
+    def summary_dev(self, n, d_length, d_mean_q=None, d_window_q=None, d_mask=None, global_=False):
+        """flx_summary_dev: the same over device pointers (int32 lengths, float64 qualities, uint8 mask)."""
+        out = _lib.Summary()
+        self._check(self.L.flx_summary_dev(self.h, int(n), d_length, d_mean_q, d_window_q, d_mask, 1 if global_ else 0,
+                                           C.byref(out)))
+        return summary_dict(out)
+
+
+SUMMARY_FIELDS = ("n", "bases", "min_length", "max_length", "median_length", "nx", "len_count", "len_bases",
+                  "mean_q_count", "mean_q_bases", "window_q_count", "window_q_bases")
+
+
+def summary_dict(s):
+    """struct flx_summary -> {field: int or list of ints} (padding left out)."""
+    d = {}
+    for name in SUMMARY_FIELDS:
+        v = getattr(s, name)
+        d[name] = int(v) if isinstance(v, int) else [int(x) for x in v]
+    return d
+
+
+def summary_q_edges():
+    """The 51 quality-bin edges of flx_summary, edges[k] = 100 (1 - 10^(-k/10)): the very doubles the kernel bins with."""
+    e = np.zeros(51, dtype=np.float64)
+    rc = _lib.load().flx_summary_q_edges(e.ctypes.data)
+    if rc:
+        raise FlxError(rc, "flx_summary_q_edges")
+    return e
+
 
 BGZF_EOF = 1  # FLX_BGZF_EOF
 

@@ -2,6 +2,7 @@
 // (src/arguments.cpp:28-393, src/args.h for the generic readers).
 #pragma once
 #include <sys/ioctl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 #include <climits>
 #include <cmath>
@@ -34,6 +35,7 @@ struct Args {
     bool verbose = false;
     int gpus = 1;  // not a reference flag: --gpus N scores on N GPUs of this node (one process per GPU)
     bool gzip = false;  // not a reference flag: --gzip writes stdout as BGZF, compressed on the GPU
+    bool report_set = false; std::string report;  // not a reference flag: --report FILE receives a JSON summary of the reads before and after
 };
 enum ParsingResult { GOOD, BAD, HELP, VERSION };
 
@@ -105,7 +107,7 @@ static long long read_ll(const std::string &name, const std::string &value, long
 // terminal on STDOUT (TIOCGWINSZ; indent 1 / 2 / 3 / 4 for widths up to 60 / 80 / 120 / beyond).  When stdout is no terminal the
 // reference reads the width out of an untouched `struct winsize` — 0 in practice: the description comes out one word per line and,
 // the other widths being unsigned differences that wrap around, nothing else is wrapped at all.  Both cases are restated here.
-// (--gpus and --gzip, this binary's flags of its own, are documented in README.md: the menu is the reference's.)
+// (--gpus, --gzip and --report, this binary's flags of its own, are documented in README.md: the menu is the reference's.)
 static std::vector<std::string> help_wrap(const std::string &in, size_t width, size_t first = 0) {  // src/args.h:94-149
     std::vector<std::string> out;
     size_t cur = first ? first : width, linesize = 0;
@@ -268,6 +270,7 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
             else if (flag == "window_size") a.window_size = read_ll("int", need("window_size"), a.window_size);
             else if (flag == "gpus") a.gpus = (int)read_ll("int", need("gpus"), a.gpus);
             else if (flag == "gzip") a.gzip = true;
+            else if (flag == "report") { a.report = need("report"); a.report_set = true; }
             else throw ParseError("Error: flag could not be matched: " + flag);
         }
     } catch (const ParseError &e) {
@@ -313,4 +316,27 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     if (a.window_size <= 0) { std::cerr << "Error: the value for --window_size must be a positive integer\n"; return BAD; }
     if (a.gpus < 1 || a.gpus > 64) { std::cerr << "Error: the value for --gpus must be between 1 and 64\n"; return BAD; }
     return GOOD;
+}
+
+// --report FILE: behind every check of the reference and of the environment (messages and their order stay what they were) and
+// before any work, FILE is created or emptied; it stays empty unless the run succeeds (report.h).  A FILE that is one of the
+// run's own inputs is refused: emptying it would destroy the input before it is read.
+static bool open_report_file(const Args &a) {
+    if (!a.report_set) return true;
+    struct stat rs;
+    if (stat(a.report.c_str(), &rs) == 0) {
+        std::vector<std::string> inputs = a.short_reads;
+        inputs.push_back(a.input_reads);
+        if (a.assembly_set) inputs.push_back(a.assembly);
+        for (const auto &f : inputs) {
+            struct stat is;
+            if (stat(f.c_str(), &is) == 0 && is.st_dev == rs.st_dev && is.st_ino == rs.st_ino) {
+                std::cerr << "Error: report file is one of the input files: " << a.report << "\n";
+                return false;
+            }
+        }
+    }
+    std::ofstream f(a.report, std::ios::out | std::ios::trunc);
+    if (!f.good()) { std::cerr << "Error: cannot write report file: " << a.report << "\n"; return false; }
+    return true;
 }

@@ -28,6 +28,7 @@
 #include "pass1.h"
 #include "ranks.h"
 #include "reference.h"
+#include "report.h"
 #include "run.h"
 #include "verbose.h"
 
@@ -115,7 +116,7 @@ static void print_cut_report(const Run &run, const flx_cut_report &rep) {
 // The output is complete.  Unpinning the staging buffers, shutting the HIP runtime down and unmapping the input is work the
 // kernel does faster when the process simply ends (0.5-0.9 s of 1.3-2.7 s on 2-10 GB inputs): flush and leave, unless a
 // clean teardown is asked for (FLX_CLI_CLEAN_EXIT=1, the timing report, or ranks to reap).
-static int leave(Run &run, Scorer &scorer) {
+static int leave(Run &run, Scorer &scorer, const Report &report) {
     const bool clean_exit = getenv("FLX_CLI_CLEAN_EXIT") != nullptr || run.timing;
     if (clean_exit) {
         scorer.destroy();
@@ -127,7 +128,8 @@ static int leave(Run &run, Scorer &scorer) {
     if (!g_job.finish()) { std::cerr << "Error: a rank failed\n"; return 1; }
     run.print_wall_clock("returns");
     if (run.rank == 0) std::cerr << "\n";
-    const bool flushed = fflush(stdout) == 0 && !ferror(stdout);
+    bool flushed = fflush(stdout) == 0 && !ferror(stdout);
+    if (flushed) flushed = write_report(run, report);  // (--report: only a run that succeeded leaves more than an empty file)
     fflush(stderr);
     if (!clean_exit) _exit(flushed ? 0 : 1);
     return flushed ? 0 : 1;
@@ -164,6 +166,7 @@ int main(int argc, char **argv) {
     if (pr == VERSION) { std::cout << "Filtlong v" << PROGRAM_VERSION << "\n"; return 0; }
     if (const int bad_env = check_cli_environment()) return bad_env;
     if (const char *po = getenv("FLX_CLI_PARSE_ONLY")) return parse_only(args.input_reads, po);
+    if (!open_report_file(args)) return 1;  // --report: created or emptied here, before any work
 
     // ---- ranks: one process per GPU (north_star / SURVEY §8e; ranks.h) — under a launcher, or forked here by --gpus N ----
     Run run(args);
@@ -225,6 +228,9 @@ int main(int argc, char **argv) {
     if (const int rc = print_verbose_table(run, r2, rep); rc != kGoOn) return rc;
     print_cut_report(run, rep);
     run.stage("rank and cut");
+    Report report;  // --report: summarised here, in front of the output pass (collectives with several ranks), written on the way out
+    if (const int rc = summarise_for_report(run, p, res, r2, report); rc != kGoOn) return rc;
+    if (args.report_set) run.stage("report");
 
     // ---- output in input order (src/main.cpp:263-313) -----------------------------------------------------
     Output out;
@@ -234,5 +240,5 @@ int main(int argc, char **argv) {
     if (const int rc = finish_output(run, out, em); rc != kGoOn) return rc;
     run.stage("output");
 
-    return leave(run, scorer);
+    return leave(run, scorer, report);
 }

@@ -40,7 +40,8 @@ extern "C" {
  * memory beside the 512 MiB bitmap, 1 GiB pair table and 2 + 2 MiB prefilters); when that memory cannot be had the set works without */
 /* 3 (round 5): + flx_last_kmer_fold_grid */
 /* 4 (round 6): + flx_last_kmer_cover, flx_last_kmer_handed_over, flx_synth_seq_profile_dev; added under version 4: the BGZF
- * compressor (flx_bgzf_bound, flx_bgzf_compress_dev, flx_bgzf_create / _compress / _destroy) */
+ * compressor (flx_bgzf_bound, flx_bgzf_compress_dev, flx_bgzf_create / _compress / _destroy) and the read summary
+ * (flx_summary_q_edges, flx_summary_dev, flx_summary) */
 #define FLX_ABI_VERSION 4
 
 enum flx_status {
@@ -340,6 +341,50 @@ typedef struct flx_bgzf flx_bgzf;
 int flx_bgzf_create(flx_ctx *ctx, uint64_t slot_bytes, unsigned slots, flx_bgzf **out);
 int flx_bgzf_compress(flx_bgzf *z, const void *in, uint64_t n, int flags, void *out, uint64_t out_cap, uint64_t *out_len);
 void flx_bgzf_destroy(flx_bgzf *z);
+
+/* ------------------------------------------------------------------------------------------
+ * read summary (added under version 4): what a set of reads looks like — entries, bases, shortest, longest, median, N10..N90
+ * and the histograms of length, mean quality and window quality — from the per-read arrays of seam 2 / the reads2 gather and
+ * the pass flags of seam 3.  The reference has no counterpart: its users run a statistics tool over the input and again over
+ * the output.  Every field is an integer and every definition is exact, so N ranks give the bits of one rank.
+ *   which entries count   all when mask is NULL, else those with mask[i] != 0; lengths must not be negative (FLX_ERR_INVALID)
+ *   length bins           bin 0 holds lengths 0 and 1, bin b holds 2^b <= L < 2^(b+1)
+ *   quality bins          on the Phred scale: edges[k] = 100 (1 - 10^(-k/10)), k = 0..50, computed once with the host's pow
+ *                         (flx_summary_q_edges returns the very doubles the kernel bins with); bin k in 0..49 holds
+ *                         edges[k] <= q < edges[k+1], bin 50 q >= edges[50] (100.0 included), bin 51 NaN and q < 0.  A NULL
+ *                         quality array leaves its two histograms zero.  *_count = entries, *_bases = sum of their lengths.
+ *   Nx                    order the counted entries by descending length; Nx is the length of the first entry at which
+ *                         100 * cum >= x * bases, cum = the sum of the lengths up to and including that entry (the product
+ *                         is carried in 128 bits); 0 when bases == 0.  nx[0] = N10 ... nx[4] = N50 ... nx[8] = N90.
+ *   median_length         entry (n - 1) / 2 of the ascending order (the lower median)
+ *   global                != 0 on a context with a communicator (flx_comm_init): the call is COLLECTIVE — every rank calls it
+ *                         (a rank with n == 0 too), every count and histogram is summed over the ranks (the exchange of
+ *                         flx_comm_sum_u64) and every rank returns the same struct, that of all entries of all ranks.
+ *                         Without a communicator `global` is ignored.
+ * One streaming pass over the arrays for the histograms and four over length and mask for the ten order statistics (radix
+ * selection, 8 bits per pass); five small device-to-host copies (<= 40 KiB) per call.  The timing bracket "flx_summary" spans the
+ * whole call on the stream: kernels, copies, the host's work between the passes and, when collective, the exchanges.
+ * In C the struct is named with its tag, `struct flx_summary`: the plain name is the function's.
+ * ---------------------------------------------------------------------------------------- */
+#define FLX_SUMMARY_LEN_BINS 32
+#define FLX_SUMMARY_Q_BINS 52
+struct flx_summary {
+    uint64_t n, bases;               /* entries counted, sum of their lengths              */
+    int32_t min_length, max_length;  /* 0, 0 when n == 0                                   */
+    int32_t median_length, _pad0;    /* 0 when n == 0                                      */
+    int32_t nx[9];                   /* N10, N20, ... N90                                  */
+    int32_t _pad1;
+    uint64_t len_count[FLX_SUMMARY_LEN_BINS], len_bases[FLX_SUMMARY_LEN_BINS];
+    uint64_t mean_q_count[FLX_SUMMARY_Q_BINS], mean_q_bases[FLX_SUMMARY_Q_BINS];
+    uint64_t window_q_count[FLX_SUMMARY_Q_BINS], window_q_bases[FLX_SUMMARY_Q_BINS];
+};
+int flx_summary_q_edges(double edges[51]);
+int flx_summary_dev(flx_ctx *ctx, uint64_t n, const void *d_length /* int32 */, const void *d_mean_q /* f64 or NULL */,
+                    const void *d_window_q /* f64 or NULL */, const void *d_mask /* u8, or NULL = all */, int global,
+                    struct flx_summary *out /* host */);
+/* host arrays, staged through the device like flx_rank_and_cut */
+int flx_summary(flx_ctx *ctx, uint64_t n, const int32_t *length, const double *mean_q, const double *window_q,
+                const uint8_t *mask, int global, struct flx_summary *out);
 
 /* ------------------------------------------------------------------------------------------
  * bench / test support: deterministic synthetic Phred planes generated directly in HBM
