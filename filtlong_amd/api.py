@@ -391,6 +391,13 @@ class Context:
         self._check(self.L.flx_bgzf_compress_dev(self.h, d_in, int(n), BGZF_EOF if eof else 0, d_out, int(out_cap), C.byref(got)))
         return got.value
 
+    def bgzf_inflate_dev(self, d_in, d_in_off, d_out_off, n_members, d_out, d_status):
+        """flx_bgzf_inflate_dev: member k = bytes [d_in_off[k], d_in_off[k+1]) of d_in to [d_out_off[k], d_out_off[k+1]) of d_out
+        (device pointers; offsets uint64, n_members + 1 each; d_status uint32) -> the lowest member that is not ok, or n_members."""
+        first_bad = C.c_uint64()
+        self._check(self.L.flx_bgzf_inflate_dev(self.h, d_in, d_in_off, d_out_off, int(n_members), d_out, d_status, C.byref(first_bad)))
+        return first_bad.value
+
     # ---- read summary (include/filtlong_hip.h, flx_summary*) ------------------------------------------------------
     def summary(self, lengths, mean_q=None, window_q=None, mask=None, global_=False):
         """flx_summary over host arrays: the struct's fields as a dictionary (integers and lists of integers).  `mask`:
@@ -451,6 +458,21 @@ def bgzf_bound(n, eof=True):
     return b.value
 
 
+def bgzf_index(data, max_members=None):
+    """flx_bgzf_index (host only): the well-formed BGZF members at the front of `data` -> (in_off, out_off), two uint64 arrays of
+    members + 1 prefix sums: member k is data[in_off[k]:in_off[k+1]] and holds out_off[k+1] - out_off[k] bytes."""
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    cap = len(src) // 26 + 1 if max_members is None else int(max_members)
+    in_off = np.zeros(cap + 1, dtype=np.uint64)
+    out_off = np.zeros(cap + 1, dtype=np.uint64)
+    m = C.c_uint64()
+    rc = _lib.load().flx_bgzf_index(src.ctypes.data if len(src) else None, len(src), cap, in_off.ctypes.data, out_off.ctypes.data,
+                                    C.byref(m))
+    if rc:
+        raise FlxError(rc, "flx_bgzf_index")
+    return in_off[:m.value + 1].copy(), out_off[:m.value + 1].copy()
+
+
 class Bgzf:
     """Host-to-host BGZF compressor (flx_bgzf) with `slots` pinned slots of `slot_bytes`; compress() may be called from
     several threads at once (ctypes releases the GIL for the call)."""
@@ -472,6 +494,20 @@ class Bgzf:
         if rc:
             raise FlxError(rc, "flx_bgzf_compress")
         return out[:got.value].tobytes()
+
+    def inflate(self, data):
+        """flx_bgzf_inflate of the BGZF members at the front of `data` (those bgzf_index finds) -> (bytes, first_bad): the bytes
+        of the members in front of the first bad one, and its index (the number of members when all are ok)."""
+        src = np.frombuffer(bytes(data), dtype=np.uint8)
+        in_off, out_off = bgzf_index(src)
+        n = len(in_off) - 1
+        out = np.empty(max(int(out_off[n]), 1), dtype=np.uint8)
+        first_bad = C.c_uint64()
+        rc = self.ctx.L.flx_bgzf_inflate(self.h, src.ctypes.data if len(src) else None, in_off.ctypes.data, out_off.ctypes.data, n,
+                                         out.ctypes.data, C.byref(first_bad))
+        if rc:
+            raise FlxError(rc, "flx_bgzf_inflate")
+        return out[:int(out_off[first_bad.value])].tobytes(), first_bad.value
 
     def close(self):
         if self.h:

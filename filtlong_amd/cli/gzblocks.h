@@ -4,6 +4,9 @@
 #include "fastx.h"
 #include "inflate_stream.h"
 #include "pinflate.h"
+#include <atomic>
+#include <functional>
+#include <mutex>
 
 // ---- block-wise parse of a compressed input -----------------------------------------------------------------------------
 // A gzip file cannot be mapped, and inflating all of it costs its uncompressed size in memory (the reference never holds
@@ -33,6 +36,36 @@ struct MappedFile {  // read-only mapping of a regular file (the compressed inpu
     }
     bool gz() const { return n >= 2 && p[0] == 0x1f && p[1] == 0x8b; }
 };
+
+// FLX_CLI_GPU_INFLATE=1: the process's device inflater of BGZF members.  run.h sets `make`; the object is created when the first
+// BGZF input large enough for the parallel reader is opened, so a plain or plain-gzip input costs nothing.  A failed creation (want
+// of memory) leaves it null for good: zlib on the host threads, as with the switch at 0.
+struct GpuInflater {
+    std::function<flx_bgzf *()> make;
+    bool output_pass = false;  // FLX_CLI_GPU_INFLATE_OUTPUT=1: inflate_range goes through it too
+    std::atomic<uint64_t> out_device{0}, out_zlib{0};  // units of the output pass: through the device / through zlib
+    flx_bgzf *get() {
+        std::lock_guard<std::mutex> g(mu_);
+        if (!tried_ && make) z_ = make();
+        tried_ = true;
+        return z_;
+    }
+    flx_bgzf *for_output() {  // (never the first use: an input that went through it has created it)
+        std::lock_guard<std::mutex> g(mu_);
+        return output_pass ? z_ : nullptr;
+    }
+    void destroy() {
+        std::lock_guard<std::mutex> g(mu_);
+        flx_bgzf_destroy(z_);
+        z_ = nullptr;
+    }
+
+private:
+    std::mutex mu_;
+    bool tried_ = false;
+    flx_bgzf *z_ = nullptr;
+};
+static GpuInflater g_gpu_inflater;
 
 struct BlockReader {
     static constexpr size_t kHistory = 32768;  // output kept in front of the write position: the window of an access point
@@ -65,7 +98,9 @@ struct BlockReader {
         return (uint64_t)32 << 20;
     }
     bool open(const std::string &path, bool want_points) {
-        if (!file.open(path) || !z.open(file.p, file.n, file.gz(), ParallelInflate::default_threads(host_threads()))) return false;
+        if (!file.open(path)) return false;
+        z.set_device(starts_with_bgzf() ? g_gpu_inflater.get() : nullptr);
+        if (!z.open(file.p, file.n, file.gz(), ParallelInflate::default_threads(host_threads()))) return false;
         holdback = file.gz() ? kHoldback : 0;
         buf.resize(block_bytes() + kHistory + holdback);
         span = want_points ? point_span() : 0;
@@ -138,6 +173,11 @@ struct BlockReader {
     }
 
 private:
+    bool starts_with_bgzf() const {  // ... and is large enough for ParallelInflate to leave the serial stream
+        uint64_t io[2], oo[2], m = 0;
+        return g_gpu_inflater.make && file.gz() && file.n >= ParallelInflate::min_bytes() &&
+               flx_bgzf_index(file.p, file.n, 1, io, oo, &m) == FLX_OK && m == 1;
+    }
     uint64_t dropped_ = 0;  // bytes of a plain file's mapping given back so far (a multiple of 2 MiB)
     size_t holdback = 0;
     Input view;  // non-owning window on buf
@@ -163,10 +203,49 @@ struct UnitIndex {
     size_t units() const { return start.empty() ? 0 : start.size() - 1; }
 };
 
+// inflate_range through the device: the point is a BGZF member start.  The members that hold bytes of [from, to) are found with
+// flx_bgzf_index and inflated in one call; false (a member that is not BGZF, or one the device does not call ok): zlib's.
+static bool inflate_range_device(flx_bgzf *z, const MappedFile &file, const GzPoint &pt, uint64_t from, uint64_t to, std::vector<char> &text) {
+    constexpr uint64_t kBatch = 1024;
+    std::vector<uint64_t> io(kBatch + 1), oo(kBatch + 1), in_off, out_off;
+    uint64_t at = pt.in, out = pt.out, in0 = 0, out0 = 0;
+    while (out < to) {
+        uint64_t m = 0;
+        if (at >= file.n || flx_bgzf_index(file.p + at, file.n - at, kBatch, io.data(), oo.data(), &m) != FLX_OK || m == 0) return false;
+        for (uint64_t k = 0; k < m && out < to; ++k) {
+            const uint64_t size = io[k + 1] - io[k], isize = oo[k + 1] - oo[k];
+            if (out + isize > from) {
+                if (in_off.empty()) {
+                    in0 = at;
+                    out0 = out;
+                    in_off.push_back(0);
+                    out_off.push_back(0);
+                }
+                in_off.push_back(at + size - in0);
+                out_off.push_back(out + isize - out0);
+            }
+            at += size;
+            out += isize;
+        }
+    }
+    const uint64_t n = in_off.size() - 1;
+    uint64_t first_bad = 0;
+    text.resize((size_t)out_off.back());
+    if (flx_bgzf_inflate(z, file.p + in0, in_off.data(), out_off.data(), n, text.data(), &first_bad) != FLX_OK || first_bad < n) return false;
+    text.erase(text.begin(), text.begin() + (size_t)(from - out0));
+    text.resize((size_t)(to - from));
+    return true;
+}
+
 // bytes [from, to) of the uncompressed stream, inflated from an access point at or before `from`
 static bool inflate_range(const MappedFile &file, const GzPoint &pt, uint64_t from, uint64_t to, std::vector<char> &text) {
+    if (pt.out > from) return false;
+    if (flx_bgzf *dev = (!pt.raw && file.gz() && from < to) ? g_gpu_inflater.for_output() : nullptr) {
+        if (inflate_range_device(dev, file, pt, from, to, text)) { ++g_gpu_inflater.out_device; return true; }
+        ++g_gpu_inflater.out_zlib;
+    }
     InflateStream z;
-    if (pt.out > from || !z.open_at(file.p, file.n, file.gz(), pt)) return false;
+    if (!z.open_at(file.p, file.n, file.gz(), pt)) return false;
     std::vector<char> skip(std::min<uint64_t>(from - pt.out, 1u << 20));
     for (uint64_t left = from - pt.out; left > 0;) {
         const size_t got = z.read(skip.data(), (size_t)std::min<uint64_t>(left, skip.size()));

@@ -393,6 +393,9 @@ static int write_output_streamed(const Run &run, const ReadsInput &in, const Pas
         }
         return gz_piece(out.gz, buf);
     }, out.sink, nullptr);
+    if (g_gpu_inflater.output_pass && getenv("FLX_CLI_PINFLATE_TIMING"))
+        fprintf(stderr, "[pinflate] device: output pass: %llu units inflated on the device, %llu by zlib\n",
+                (unsigned long long)g_gpu_inflater.out_device.load(), (unsigned long long)g_gpu_inflater.out_zlib.load());
     if (!ok && run.world == 1) { std::cerr << "Error: " << run.args.input_reads << " could not be read a second time (did it change?)\n"; return 1; }
     out.pieces_ok = ok;  // (several ranks: to the exchange of finish_output, like a failed write)
     return kGoOn;

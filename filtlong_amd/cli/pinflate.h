@@ -34,6 +34,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/filtlong_hip.h"
 #include "inflate_stream.h"
 
 namespace pinflate {
@@ -435,6 +436,11 @@ public:
     ParallelInflate &operator=(const ParallelInflate &) = delete;
     ~ParallelInflate() { shutdown(); }
 
+    // BGZF members go through this device inflater instead of the zlib workers (null, the default: nothing changes).  Set before
+    // open().  What the device does not call ok goes to zlib, member by member, exactly as a failing run of the workers does.
+    void set_device(flx_bgzf *z) { gpu_ = z; }
+    uint64_t device_members() const { return gpu_members_; }
+
     bool open(const unsigned char *data, size_t size, bool gz, unsigned threads) {
         shutdown();
         data_ = data; size_ = size; threads_ = std::max(1u, threads);
@@ -444,6 +450,7 @@ public:
         stage_q_.clear(); stage_pts_.clear(); p_finished_ = false; p_error_ = false; p_handover_set_ = false; p_deliverable_ = 0;
         stream_out_ = 0; member_base_ = 0; bgzf_mode_ = false; bgzf_at_ = 0;
         parallel_bytes_ = 0; zlib_tail_bytes_ = 0; rounds_ = 0; dropped_chunks_ = 0;
+        gpu_members_ = 0; gpu_handed_ = 0; gpu_ns_ = 0;
         const char *off = getenv("FLX_CLI_PINFLATE");  // 0: zlib only; "nozlib": every chunk to its end with the marker decoder (tests)
         zlib_tails_ = !(off && strcmp(off, "nozlib") == 0);
         if (const char *e = getenv("FLX_CLI_PINFLATE_AHEAD_MB")) max_ahead_ = (size_t)std::max(1, atoi(e)) << 20;
@@ -452,7 +459,7 @@ public:
             last_point_out_ = 0;
             begin_member(0);
             if (p_error_) { error_ = true; return false; }
-            if (p_handover_set_) return take_over();  // nothing for the parallel paths: zlib from the first byte
+            if (p_handover_set_) { device_line(); return take_over(); }  // nothing for the parallel paths: zlib from the first byte
             serial_mode_ = false;
             producer_ = std::thread([this] { produce(); });  // decodes ahead of read(), at most max_ahead_ bytes
             return true;
@@ -614,6 +621,7 @@ private:
                 return;
             }
             if (size_ - at >= min_bytes() || at == 0) {
+                if (gpu_ && at > 0) ++gpu_handed_;  // a plain member behind BGZF ones: the host decoders', like every hand-over
                 chain_bit_ = (uint64_t)hdr * 8;
                 member_base_ = stream_out_;
                 member_out_ = 0;
@@ -634,6 +642,13 @@ private:
         p_handover_ = pt;
         p_handover_set_ = true;
         p_finished_ = true;
+        if (gpu_) ++gpu_handed_;  // (the member at pt.in)
+    }
+    // FLX_CLI_PINFLATE_TIMING with a device inflater: what it did, once, when the producer has finished
+    void device_line() const {
+        if (!gpu_ || !getenv("FLX_CLI_PINFLATE_TIMING")) return;
+        fprintf(stderr, "[pinflate] device: %llu members inflated on the device, %llu handed to zlib, %.3f ms in flx_bgzf_inflate\n",
+                (unsigned long long)gpu_members_.load(), (unsigned long long)gpu_handed_.load(), gpu_ns_.load() * 1e-6);
     }
     // reader: the serial stream takes over where the producer stopped
     bool take_over() {
@@ -682,7 +697,7 @@ private:
             for (GzPoint &pt : stage_pts_) shared_pts_.push_back(std::move(pt));
             stage_q_.clear();
             stage_pts_.clear();
-            if (p_finished_ || stop_) { finished_ = true; lk.unlock(); cv_.notify_all(); return; }
+            if (p_finished_ || stop_) { finished_ = true; lk.unlock(); cv_.notify_all(); device_line(); return; }
             cv_.notify_all();
             cv_.wait(lk, [&] { return queued_bytes_ <= max_ahead_ || stop_; });
             if (stop_) { finished_ = true; lk.unlock(); cv_.notify_all(); return; }
@@ -731,6 +746,8 @@ private:
         std::vector<Piece> pieces(runs);
         std::vector<int> ok(runs, 1);
         std::vector<size_t> first(runs + 1);
+        std::vector<size_t> good(runs, 0);  // device: the members of a run in front of its first bad one
+        std::vector<int> api_error(runs, 0);
         for (size_t r = 0; r <= runs; ++r) first[r] = mem.size() * r / runs;
         const bool all_ran = pinflate::run_parallel(runs, threads_, [&](size_t r) {
             size_t total = 0;
@@ -738,6 +755,25 @@ private:
             Piece &pc = pieces[r];
             pc.bytes = take_buffer();
             if (pc.bytes.size() < total) pc.bytes.resize(total);
+            if (gpu_) {  // the run's members through the device; the first it does not call ok ends the run
+                const size_t m = first[r + 1] - first[r];
+                std::vector<uint64_t> in_off(m + 1), out_off(m + 1);
+                in_off[0] = 0;
+                out_off[0] = 0;
+                for (size_t k = 0; k < m; ++k) {
+                    in_off[k + 1] = in_off[k] + mem[first[r] + k].size;
+                    out_off[k + 1] = out_off[k] + mem[first[r] + k].isize;
+                }
+                uint64_t fb = 0;
+                const auto t0 = std::chrono::steady_clock::now();
+                const int rc = flx_bgzf_inflate(gpu_, data_ + mem[first[r]].at, in_off.data(), out_off.data(), m, pc.bytes.data(), &fb);
+                gpu_ns_ += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+                if (rc != FLX_OK) { api_error[r] = 1; return; }
+                good[r] = (size_t)fb;
+                if (fb < m) ok[r] = 0;
+                pc.n = (size_t)out_off[fb];
+                return;
+            }
             size_t have = 0;
             z_stream z;
             memset(&z, 0, sizeof z);
@@ -753,12 +789,32 @@ private:
             inflateEnd(&z);
             pc.n = total;
         });
-        if (!all_ran) ok.assign(runs, 0);  // a worker could not get its memory: zlib reads on alone from the first run
+        bool failed = !all_ran;  // a worker could not get its memory: zlib reads on alone from the first run
+        for (size_t r = 0; r < runs; ++r) failed = failed || api_error[r];  // (or the device inflater could not run: the same)
+        if (failed) {
+            ok.assign(runs, 0);
+            good.assign(runs, 0);
+            for (Piece &pc : pieces) pc.n = 0;
+        }
         ++rounds_;
         for (size_t r = 0; r < runs; ++r) {
-            if (!ok[r]) {  // zlib reads this run again, alone, and says what is wrong with it
+            if (!ok[r] && good[r] > 0) {  // device: the members in front of the bad one are a piece like any other
+                if (stream_out_ > 0) {
+                    GzPoint pt;
+                    pt.in = mem[first[r]].at;
+                    pt.out = stream_out_;
+                    pt.raw = false;
+                    stage_pts_.push_back(std::move(pt));
+                }
+                stream_out_ += pieces[r].n;
+                parallel_bytes_ += pieces[r].n;
+                gpu_members_ += good[r];
+                if (pieces[r].n > 0) stage_q_.push_back(std::move(pieces[r]));
+            }
+            if (!ok[r]) {  // zlib reads this run (device: from its first bad member) again, alone, and says what is wrong with it
+                if (gpu_) gpu_handed_ += mem.size() - (first[r] + good[r]) - 1;  // (hand_over counts the bad member itself)
                 GzPoint pt;
-                pt.in = mem[first[r]].at;
+                pt.in = mem[first[r] + good[r]].at;
                 pt.out = stream_out_;
                 pt.raw = false;
                 bgzf_mode_ = false;
@@ -774,6 +830,7 @@ private:
             }
             stream_out_ += pieces[r].n;
             parallel_bytes_ += pieces[r].n;
+            if (gpu_) gpu_members_ += first[r + 1] - first[r];
             if (pieces[r].n > 0) stage_q_.push_back(std::move(pieces[r]));
         }
         bgzf_at_ = at;
@@ -1075,4 +1132,6 @@ private:
     std::vector<pinflate::Decoder> decoders_;
     std::atomic<uint64_t> parallel_bytes_{0}, zlib_tail_bytes_{0};
     std::atomic<unsigned> rounds_{0}, dropped_chunks_{0};
+    flx_bgzf *gpu_ = nullptr;  // the device inflater of BGZF members (null: the zlib workers)
+    std::atomic<uint64_t> gpu_members_{0}, gpu_handed_{0}, gpu_ns_{0};
 };

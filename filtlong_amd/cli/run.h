@@ -101,6 +101,23 @@ struct Run {
         }
         return ctx != nullptr;
     }
+    // FLX_CLI_GPU_INFLATE=1: BGZF input (the reads, the count pass, the -a / -1 / -2 references) is inflated on the device, by one
+    // object per process.  It is created when the first BGZF input is opened (gzblocks.h), behind the context, which that input then
+    // waits for; nothing else does.  A context or an object that cannot be had is no error here: the input is zlib's, as with the
+    // switch at 0, and whoever needs the context next reports it.  0, the default: zlib on the host threads.
+    // FLX_CLI_GPU_INFLATE_OUTPUT=1 sends the output pass's re-inflation (inflate_range) through the same object.
+    static bool switch_on(const char *e) { return e && e[0] == '1'; }
+    void arm_inflater() {
+        if (!switch_on(getenv("FLX_CLI_GPU_INFLATE"))) return;
+        g_gpu_inflater.output_pass = switch_on(getenv("FLX_CLI_GPU_INFLATE_OUTPUT"));
+        g_gpu_inflater.make = [this]() -> flx_bgzf * {
+            if (ctx_thread.joinable()) ctx_thread.join();
+            flx_bgzf *z = nullptr;
+            if (ctx_rc != FLX_OK || !ctx) return nullptr;
+            if (flx_bgzf_create(ctx, 16u << 20, (unsigned)std::min<size_t>(host_threads(), 16), &z) != FLX_OK) return nullptr;
+            return z;
+        };
+    }
     // a rank's file in the job's private directory: its "part" of the output, its "vblocks" and "vtable" of --verbose
     std::string part_path(const char *kind, int r) const { return part_prefix + "." + kind + std::to_string(r); }
 };

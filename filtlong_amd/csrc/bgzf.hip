@@ -196,8 +196,15 @@ struct flx_bgzf_slot {
     uint8_t *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
     void *work = nullptr;
     uint64_t *h_state = nullptr;
+    uint64_t *d_tab = nullptr, *h_tab = nullptr;  // inflate: the piece's offsets, its first bad member, its status words
     bool busy = false;
 };
+
+// inflate runs a call in pieces of at most kInflatePiece members whose compressed bytes fit d_in and whose bytes fit d_out: both
+// are kSlotSlack larger than compression needs, so that a single member of 64 KiB (either way) always fits
+constexpr uint64_t kInflatePiece = 4096;
+constexpr uint64_t kSlotSlack = 256;
+constexpr size_t kTabBytes = (2 * (kInflatePiece + 1) + 1) * 8 + kInflatePiece * 4;
 
 struct flx_bgzf {
     flx_ctx *ctx = nullptr;
@@ -216,6 +223,8 @@ static void free_slot(flx_bgzf_slot &s) {
     if (s.h_in) (void)hipHostFree(s.h_in);
     if (s.h_out) (void)hipHostFree(s.h_out);
     if (s.h_state) (void)hipHostFree(s.h_state);
+    if (s.d_tab) (void)hipFree(s.d_tab);
+    if (s.h_tab) (void)hipHostFree(s.h_tab);
     s = flx_bgzf_slot();
 }
 
@@ -244,12 +253,14 @@ extern "C" int flx_bgzf_create(flx_ctx *ctx, uint64_t slot_bytes, unsigned slots
     const uint64_t ob = bound_of(sb, FLX_BGZF_EOF);
     for (auto &s : z->slots) {
         hipError_t e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMalloc(&s.d_in, sb);
-        if (e == hipSuccess) e = hipMalloc(&s.d_out, ob);
+        if (e == hipSuccess) e = hipMalloc(&s.d_in, sb + kSlotSlack);
+        if (e == hipSuccess) e = hipMalloc(&s.d_out, ob + kSlotSlack);
         if (e == hipSuccess) e = hipMalloc(&s.work, work_bytes(sb));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_in, sb, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_out, ob, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_in, sb + kSlotSlack, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_out, ob + kSlotSlack, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_state, 16, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void **)&s.d_tab, kTabBytes);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_tab, kTabBytes, hipHostMallocDefault);
         if (e != hipSuccess) {
             flx_bgzf_destroy(z);
             return flx_fail(ctx, FLX_ERR_NOMEM, "flx_bgzf_create: %s", hipGetErrorString(e));
@@ -259,22 +270,89 @@ extern "C" int flx_bgzf_create(flx_ctx *ctx, uint64_t slot_bytes, unsigned slots
     return FLX_OK;
 }
 
+static flx_bgzf_slot *take_slot(flx_bgzf *z) {
+    flx_bgzf_slot *s = nullptr;
+    std::unique_lock<std::mutex> lk(z->mu);
+    for (;;) {
+        for (auto &c : z->slots)
+            if (!c.busy) { s = &c; break; }
+        if (s) break;
+        z->cv.wait(lk);
+    }
+    s->busy = true;
+    return s;
+}
+static void give_slot(flx_bgzf *z, flx_bgzf_slot *s) {
+    {
+        std::lock_guard<std::mutex> lk(z->mu);
+        s->busy = false;
+    }
+    z->cv.notify_one();
+}
+
+// Thread-safe like flx_bgzf_compress.  Members [k, k + c) of a piece: compressed bytes in, offsets in, bytes and the first bad
+// member out; the call stops behind the first piece that holds a bad member.
+extern "C" int flx_bgzf_inflate(flx_bgzf *z, const void *in, const uint64_t *in_off, const uint64_t *out_off, uint64_t n_members,
+                                void *out, uint64_t *first_bad) {
+    if (!z || !first_bad) return FLX_ERR_INVALID;
+    *first_bad = n_members;
+    if (n_members == 0) return FLX_OK;
+    if (!in || !in_off || !out_off || (!out && out_off[n_members] > out_off[0])) return FLX_ERR_INVALID;
+    for (uint64_t k = 0; k < n_members; ++k)
+        if (in_off[k + 1] < in_off[k] || out_off[k + 1] < out_off[k]) return FLX_ERR_INVALID;
+    const uint64_t in_cap = z->slot_bytes + kSlotSlack, out_cap = bound_of(z->slot_bytes, FLX_BGZF_EOF) + kSlotSlack;
+    flx_bgzf_slot *s = take_slot(z);
+    hipError_t e = hipSetDevice(z->device);
+    uint64_t k = 0, bad = n_members;
+    while (e == hipSuccess && k < n_members) {
+        uint64_t c = 0;
+        while (k + c < n_members && c < kInflatePiece && in_off[k + c + 1] - in_off[k] <= in_cap &&
+               out_off[k + c + 1] - out_off[k] <= out_cap)
+            ++c;
+        if (c == 0) {  // a member beyond 64 KiB is no BGZF member
+            bad = k;
+            break;
+        }
+        const uint64_t nin = in_off[k + c] - in_off[k], nout = out_off[k + c] - out_off[k];
+        uint64_t *h_in_off = s->h_tab, *h_out_off = s->h_tab + c + 1;
+        for (uint64_t j = 0; j <= c; ++j) {
+            h_in_off[j] = in_off[k + j] - in_off[k];
+            h_out_off[j] = out_off[k + j] - out_off[k];
+        }
+        uint64_t *d_first = s->d_tab + 2 * (kInflatePiece + 1);
+        uint32_t *d_status = (uint32_t *)(d_first + 1);
+        memcpy(s->h_in, (const uint8_t *)in + in_off[k], nin);
+        e = hipMemcpyAsync(s->d_in, s->h_in, nin, hipMemcpyHostToDevice, s->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->d_tab, s->h_tab, (2 * c + 2) * 8, hipMemcpyHostToDevice, s->stream);
+        if (e == hipSuccess)
+            e = flx_bgzf_inflate_launch(s->stream, s->d_in, s->d_tab, s->d_tab + c + 1, c, s->d_out, d_status, d_first);
+        if (e == hipSuccess && nout) e = hipMemcpyAsync(s->h_out, s->d_out, nout, hipMemcpyDeviceToHost, s->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->h_state, d_first, 8, hipMemcpyDeviceToHost, s->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+        if (e != hipSuccess) {  // what was enqueued in front of the failure may still read or write the slot's buffers
+            (void)hipStreamSynchronize(s->stream);
+            break;
+        }
+        const uint64_t fb = s->h_state[0] < c ? s->h_state[0] : c;
+        memcpy((uint8_t *)out + out_off[k], s->h_out, (size_t)(h_out_off[fb]));
+        if (fb < c) {
+            bad = k + fb;
+            break;
+        }
+        k += c;
+    }
+    give_slot(z, s);
+    if (e != hipSuccess) return FLX_ERR_HIP;
+    *first_bad = bad;
+    return FLX_OK;
+}
+
 // Thread-safe: a call takes a free slot (or waits for one) and runs its chunks on that slot's stream.
 extern "C" int flx_bgzf_compress(flx_bgzf *z, const void *in, uint64_t n, int flags, void *out, uint64_t out_cap,
                                  uint64_t *out_len) {
     if (!z || (!in && n) || !out_len || (flags & ~FLX_BGZF_EOF) || (!out && out_cap)) return FLX_ERR_INVALID;
     *out_len = 0;
-    flx_bgzf_slot *s = nullptr;
-    {
-        std::unique_lock<std::mutex> lk(z->mu);
-        for (;;) {
-            for (auto &c : z->slots)
-                if (!c.busy) { s = &c; break; }
-            if (s) break;
-            z->cv.wait(lk);
-        }
-        s->busy = true;
-    }
+    flx_bgzf_slot *s = take_slot(z);
     int rc = FLX_OK;
     hipError_t e = hipSetDevice(z->device);
     uint64_t done = 0, len = 0;
@@ -301,11 +379,7 @@ extern "C" int flx_bgzf_compress(flx_bgzf *z, const void *in, uint64_t n, int fl
         done += c;
     } while (done < n);
     if (e != hipSuccess) rc = FLX_ERR_HIP;
-    {
-        std::lock_guard<std::mutex> lk(z->mu);
-        s->busy = false;
-    }
-    z->cv.notify_one();
+    give_slot(z, s);
     if (rc == FLX_OK) *out_len = len;
     return rc;
 }

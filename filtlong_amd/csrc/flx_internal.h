@@ -96,6 +96,10 @@ struct flx_time_scope {
     ~flx_time_scope() { end(); }
 };
 
+// bgzf_inflate.hip: the launches of one inflate call on `st` (for flx_bgzf's slots in bgzf.hip); *d_first: the lowest bad member
+hipError_t flx_bgzf_inflate_launch(hipStream_t st, const void *d_in, const uint64_t *d_in_off, const uint64_t *d_out_off,
+                                   uint64_t n_members, void *d_out, uint32_t *d_status, uint64_t *d_first);
+
 // grow-only scratch on the device
 int flx_scratch(flx_ctx *ctx, size_t bytes, void **out);
 // grow-only pinned host buffer; valid until the next call that asks for more

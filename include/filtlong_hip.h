@@ -40,8 +40,9 @@ extern "C" {
  * memory beside the 512 MiB bitmap, 1 GiB pair table and 2 + 2 MiB prefilters); when that memory cannot be had the set works without */
 /* 3 (round 5): + flx_last_kmer_fold_grid */
 /* 4 (round 6): + flx_last_kmer_cover, flx_last_kmer_handed_over, flx_synth_seq_profile_dev; added under version 4: the BGZF
- * compressor (flx_bgzf_bound, flx_bgzf_compress_dev, flx_bgzf_create / _compress / _destroy) and the read summary
- * (flx_summary_q_edges, flx_summary_dev, flx_summary) */
+ * compressor (flx_bgzf_bound, flx_bgzf_compress_dev, flx_bgzf_create / _compress / _destroy), the read summary
+ * (flx_summary_q_edges, flx_summary_dev, flx_summary) and the BGZF inflater (flx_bgzf_index, flx_bgzf_inflate_dev,
+ * flx_bgzf_inflate) */
 #define FLX_ABI_VERSION 4
 
 enum flx_status {
@@ -341,6 +342,32 @@ typedef struct flx_bgzf flx_bgzf;
 int flx_bgzf_create(flx_ctx *ctx, uint64_t slot_bytes, unsigned slots, flx_bgzf **out);
 int flx_bgzf_compress(flx_bgzf *z, const void *in, uint64_t n, int flags, void *out, uint64_t out_cap, uint64_t *out_len);
 void flx_bgzf_destroy(flx_bgzf *z);
+
+/* BGZF members inflated on the device (added under version 4): the read side of the compressor.  A member holds at most 64 KiB,
+ * carries its size and depends on no other, so members are decoded side by side, one wave each.  The decoder is a complete RFC 1951
+ * decoder (stored, fixed and dynamic blocks, any number per member); a member is ok (status word 0) only when its deflate data is
+ * valid, ends in the last byte in front of the trailer, gives exactly ISIZE bytes and their CRC-32 is the trailer's.  In doubt it
+ * rejects: a caller hands the first bad member to zlib, which has the last word on damaged data.  The bytes of a member that is not
+ * ok are unspecified (and inside its own range).
+ *   flx_bgzf_index        host only, no device: walks the well-formed BGZF members from byte 0 (magic, CM 8, FEXTRA with a `BC`
+ *                         subfield of length 2, BSIZE + 1 within n and no smaller than header + 8, ISIZE <= 65536) up to the
+ *                         first that is not, or max_members.  in_off[0..m] and out_off[0..m] are the prefix sums of the members'
+ *                         sizes and of their ISIZEs (m + 1 entries each, so room for max_members + 1); *n_members = m.
+ *   flx_bgzf_inflate_dev  device to device on the context's stream (timed as "flx_bgzf_inflate"): member k is the bytes
+ *                         [d_in_off[k], d_in_off[k+1]) of d_in and its output goes to [d_out_off[k], d_out_off[k+1]) of d_out;
+ *                         d_status[k] = 0 for an ok member.  *first_bad = the lowest k with a status other than 0, or n_members;
+ *                         it comes back with the call's one small copy.  FLX_OK whenever the call ran: a damaged member is
+ *                         data, not an error.  n_members == 0 is a no-op.
+ *   flx_bgzf_inflate      host to host through the pinned slots and streams of a flx_bgzf; may be called from several threads at
+ *                         once like flx_bgzf_compress.  Offsets as above, relative to `in` and `out`.  Runs in pieces that fit a
+ *                         slot both ways and stops behind the piece of the first bad member: the bytes of the members in front
+ *                         of *first_bad are in `out`, nothing behind them is promised.
+ * ---------------------------------------------------------------------------------------- */
+int flx_bgzf_index(const void *in, uint64_t n, uint64_t max_members, uint64_t *in_off, uint64_t *out_off, uint64_t *n_members);
+int flx_bgzf_inflate_dev(flx_ctx *ctx, const void *d_in, const uint64_t *d_in_off, const uint64_t *d_out_off, uint64_t n_members,
+                         void *d_out, uint32_t *d_status, uint64_t *first_bad);
+int flx_bgzf_inflate(flx_bgzf *z, const void *in, const uint64_t *in_off, const uint64_t *out_off, uint64_t n_members, void *out,
+                     uint64_t *first_bad);
 
 /* ------------------------------------------------------------------------------------------
  * read summary (added under version 4): what a set of reads looks like — entries, bases, shortest, longest, median, N10..N90
