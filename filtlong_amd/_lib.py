@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "flx_last_phred_kernel", "flx_last_kmer_locus", "flx_last_kmer_fold_grid", "flx_last_kmer_cover", "flx_last_kmer_handed_over", "flx_synth_qual_dev", "flx_synth_qual_profile_dev", "flx_synth_seq_dev", "flx_synth_seq_profile_dev",
     "flx_bgzf_bound", "flx_bgzf_compress_dev", "flx_bgzf_create", "flx_bgzf_compress", "flx_bgzf_destroy",
     "flx_bgzf_index", "flx_bgzf_inflate_dev", "flx_bgzf_inflate",
+    "flx_bam_index", "flx_bam_to_fastq_dev", "flx_bam_to_fastq",
     "flx_summary_q_edges", "flx_summary_dev", "flx_summary",
 ]
 
@@ -194,6 +195,9 @@ def load():
     L.flx_bgzf_index.argtypes = [vp, u64, u64, vp, vp, C.POINTER(u64)]
     L.flx_bgzf_inflate_dev.argtypes = [vp, vp, vp, vp, u64, vp, vp, C.POINTER(u64)]
     L.flx_bgzf_inflate.argtypes = [vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
+    L.flx_bam_index.argtypes = [vp, u64, u64, vp, C.POINTER(u64), C.POINTER(C.c_int)]
+    L.flx_bam_to_fastq_dev.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.flx_bam_to_fastq.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.flx_summary_q_edges.argtypes = [vp]
     L.flx_summary_dev.argtypes = [vp, u64, vp, vp, vp, vp, i32, C.POINTER(Summary)]
     L.flx_summary.argtypes = [vp, u64, vp, vp, vp, vp, i32, C.POINTER(Summary)]

@@ -398,6 +398,19 @@ class Context:
         self._check(self.L.flx_bgzf_inflate_dev(self.h, d_in, d_in_off, d_out_off, int(n_members), d_out, d_status, C.byref(first_bad)))
         return first_bad.value
 
+    def bam_to_fastq_dev(self, d_bam, n, d_rec_off, n_records, d_out, out_cap, d_out_off):
+        """flx_bam_to_fastq_dev: records [d_rec_off[k], d_rec_off[k+1]) of the n device bytes at d_bam as FASTQ text into d_out
+        (device, out_cap bytes); d_out_off (device, uint64, n_records + 1) gets the text offsets -> (out_len, n_skipped, first_bad).
+        FLX_ERR_CAPACITY raises FlxError with the length needed in its `needed`."""
+        out_len, skipped, first_bad = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = self.L.flx_bam_to_fastq_dev(self.h, d_bam, int(n), d_rec_off, int(n_records), d_out, int(out_cap), d_out_off,
+                                         C.byref(out_len), C.byref(skipped), C.byref(first_bad))
+        if rc:
+            e = FlxError(rc, self.L.flx_last_error(self.h).decode())
+            e.needed = out_len.value
+            raise e
+        return out_len.value, skipped.value, first_bad.value
+
     # ---- read summary (include/filtlong_hip.h, flx_summary*) ------------------------------------------------------
     def summary(self, lengths, mean_q=None, window_q=None, mask=None, global_=False):
         """flx_summary over host arrays: the struct's fields as a dictionary (integers and lists of integers).  `mask`:
@@ -471,6 +484,47 @@ def bgzf_index(data, max_members=None):
     if rc:
         raise FlxError(rc, "flx_bgzf_index")
     return in_off[:m.value + 1].copy(), out_off[:m.value + 1].copy()
+
+
+BAM_END, BAM_TRUNCATED, BAM_MALFORMED, BAM_HEADER, BAM_MORE = range(5)  # FLX_BAM_*: why flx_bam_index stopped
+
+
+def bam_index(data, max_records=None):
+    """flx_bam_index (host only) over inflated BAM bytes -> (rec_off, end_state): record k is data[rec_off[k]:rec_off[k+1]]
+    (rec_off[0] is the end of the header) and end_state one of the BAM_* values above."""
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    cap = len(src) // 36 + 1 if max_records is None else int(max_records)
+    rec_off = np.zeros(cap + 1, dtype=np.uint64)
+    m, end = C.c_uint64(), C.c_int()
+    rc = _lib.load().flx_bam_index(src.ctypes.data if len(src) else None, len(src), cap, rec_off.ctypes.data, C.byref(m), C.byref(end))
+    if rc:
+        raise FlxError(rc, "flx_bam_index")
+    return rec_off[:m.value + 1].copy(), end.value
+
+
+def bam_to_fastq(ctx, data, piece_bytes=0, out_cap=None, with_offsets=False):
+    """flx_bam_to_fastq: inflated BAM bytes in, FASTQ bytes out (the records bam_index finds; a truncated or malformed file raises
+    ValueError).  with_offsets: -> (bytes, text offsets of the records, skipped records)."""
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    rec_off, end = bam_index(src)
+    if end != BAM_END:
+        raise ValueError("bam_to_fastq: %s at record %d" % ({BAM_TRUNCATED: "truncated", BAM_MALFORMED: "malformed", BAM_HEADER: "bad header"}.get(end, end),
+                                                            len(rec_off) - 1))
+    n = len(rec_off) - 1
+    cap = 2 * int(rec_off[n] - rec_off[0]) if out_cap is None else int(out_cap)
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    out_off = np.zeros(n + 1, dtype=np.uint64)
+    out_len, skipped, first_bad = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rc = ctx.L.flx_bam_to_fastq(ctx.h, src.ctypes.data if len(src) else None, len(src), rec_off.ctypes.data, n, int(piece_bytes),
+                                out.ctypes.data, cap, out_off.ctypes.data, C.byref(out_len), C.byref(skipped), C.byref(first_bad))
+    if rc:
+        e = FlxError(rc, ctx.L.flx_last_error(ctx.h).decode())
+        e.needed = out_len.value
+        raise e
+    if first_bad.value != n:
+        raise ValueError("bam_to_fastq: record %d is malformed" % first_bad.value)
+    text = out[:out_len.value].tobytes()
+    return (text, out_off, skipped.value) if with_offsets else text
 
 
 class Bgzf:

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <deque>
 #include <iostream>
+#include <memory>
 #include <string>
 #include <string_view>
 #include <thread>
@@ -59,8 +60,16 @@ static void parallel_for(size_t n_parts, F &&body) {  // body(part) for part in 
     for (auto &x : th) x.join();
 }
 
+// What an Input needs to take unaligned BAM (bam.h: kBamHooks): whether a mapped file is BAM, and the inflated file as FASTQ text
+// (false: `reason` says what is wrong with it).  This header knows nothing else about BAM.
+struct BamHooks {
+    bool (*detect)(const unsigned char *file, size_t n);
+    bool (*to_text)(const char *data, size_t n, std::unique_ptr<char[]> &text, size_t &text_len, std::string &reason);
+};
+
 // The whole input, addressable.  Plain files are mapped (no copy; pages are faulted in by several threads); gzip and
-// pipes are inflated / read into memory through zlib, as the reference's kseq does (src/kseq.h:87-110).
+// pipes are inflated / read into memory through zlib, as the reference's kseq does (src/kseq.h:87-110).  Unaligned BAM (only where
+// `bam` is set: the long reads) is inflated like gzip and then replaced by its FASTQ text.
 struct Input {
     const char *p = nullptr;
     size_t n = 0;
@@ -71,6 +80,9 @@ struct Input {
     // (src/kseq.h:47,71-76,105-108: every further read returns -3) — not at the end of the file.  The Parser below turns that into
     // what kseq_read returns from there (a truncated stream is simply shorter: gzread delivers what it could decode, then EOF).
     bool stream_error = false;
+    const BamHooks *bam = nullptr;       // set by the caller before open(): this input may be unaligned BAM
+    std::unique_ptr<char[]> bam_text;    // a BAM input: the text its records were turned into (p points here)
+    std::string bam_error;               // open() returned false because the input is BAM and truncated or malformed: the reason
     Input() = default;
     Input(const Input &) = delete;
     Input &operator=(const Input &) = delete;
@@ -108,6 +120,7 @@ struct Input {
             void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
             if (m != MAP_FAILED) {
                 bool ok = false;
+                const bool is_bam = bam && bam->detect((const unsigned char *)m, (size_t)st.st_size);
                 {
                     ParallelInflate z;
                     if (z.open((const unsigned char *)m, (size_t)st.st_size, true, ParallelInflate::default_threads(host_threads()))) {
@@ -126,6 +139,15 @@ struct Input {
                     }
                 }
                 munmap(m, (size_t)st.st_size);
+                if (is_bam) {  // (a missing BGZF end-of-file block is nothing: the records end where the data ends, or they do not)
+                    ::close(fd);
+                    if (!ok) bam_error = "the BGZF members could not be read";
+                    else if (stream_error) bam_error = "a BGZF member does not inflate";
+                    else if (bam->to_text(owned.data(), owned.size(), bam_text, n, bam_error)) p = bam_text.get();
+                    stream_error = false;
+                    std::string().swap(owned);
+                    return p != nullptr;
+                }
                 if (ok) {
                     ::close(fd);
                     p = owned.data(); n = owned.size();

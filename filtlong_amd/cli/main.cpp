@@ -140,8 +140,8 @@ static int leave(Run &run, Scorer &scorer, const Report &report) {
 // error — a mistyped switch must not be ignored silently.  (The library checks the rest of the FLX_* names: flx_ctx_create.)
 static int check_cli_environment() {
     static const char *const known[] = {
-        "FLX_CLI_BLOCK_BYTES", "FLX_CLI_BLOCK_MB", "FLX_CLI_CHUNK_BYTES", "FLX_CLI_CHUNK_MB", "FLX_CLI_CLEAN_EXIT", "FLX_CLI_FORCE_STREAM",
-        "FLX_CLI_FAIL_WRITE_RANK", "FLX_CLI_GPU_INFLATE", "FLX_CLI_GPU_INFLATE_OUTPUT", "FLX_CLI_INFLATE_THREADS", "FLX_CLI_NO_STREAM", "FLX_CLI_ORDERED_OUTPUT", "FLX_CLI_PARALLEL_PARSE_MIN", "FLX_CLI_PARSE_ONLY",
+        "FLX_CLI_BAM_TIMING", "FLX_CLI_BLOCK_BYTES", "FLX_CLI_BLOCK_MB", "FLX_CLI_CHUNK_BYTES", "FLX_CLI_CHUNK_MB", "FLX_CLI_CLEAN_EXIT", "FLX_CLI_FORCE_STREAM",
+        "FLX_CLI_FAIL_WRITE_RANK", "FLX_CLI_GPU_BAM", "FLX_CLI_GPU_INFLATE", "FLX_CLI_GPU_INFLATE_OUTPUT", "FLX_CLI_INFLATE_THREADS", "FLX_CLI_NO_STREAM", "FLX_CLI_ORDERED_OUTPUT", "FLX_CLI_PARALLEL_PARSE_MIN", "FLX_CLI_PARSE_ONLY",
         "FLX_CLI_PINFLATE", "FLX_CLI_PINFLATE_AHEAD_MB", "FLX_CLI_PINFLATE_CHUNK", "FLX_CLI_PINFLATE_MIN", "FLX_CLI_PINFLATE_TIMING",
         "FLX_CLI_RANK_RANGES", "FLX_CLI_RANK_STREAM", "FLX_CLI_REF_BATCH_BYTES", "FLX_CLI_SPAN_BYTES", "FLX_CLI_THREADS", "FLX_CLI_TIMING",
     };
@@ -156,7 +156,7 @@ static int check_cli_environment() {
             return 1;
         }
     }
-    for (const char *name : {"FLX_CLI_GPU_INFLATE", "FLX_CLI_GPU_INFLATE_OUTPUT"})
+    for (const char *name : {"FLX_CLI_GPU_BAM", "FLX_CLI_GPU_INFLATE", "FLX_CLI_GPU_INFLATE_OUTPUT"})
         if (const char *e = getenv(name))
             if (strcmp(e, "0") != 0 && strcmp(e, "1") != 0) {
                 std::cerr << "Error: " << name << " must be 0 or 1\n";
@@ -196,6 +196,7 @@ int main(int argc, char **argv) {
     if (run.world > 1)
         if (const int rc = exchange_communicator_id(run, id_file, id_pipe); rc != kGoOn) return rc;
     run.arm_inflater();
+    run.arm_bam();
     run.stage("context");
 
     // ---- reference 16-mers (src/main.cpp:51-59, src/kmers.cpp:50-72) --------------------------------------

@@ -1,6 +1,7 @@
 // parse_only.h — the parsers without a GPU: a digest of every field of the input (the CPU tests compare the sequential parser, the
 // concurrent one, the block-wise reader and the ranks' shares on generated odd files).  Included by main.cpp only.
 #pragma once
+#include "bam.h"
 #include "fastx.h"
 #include "gzblocks.h"
 
@@ -58,7 +59,12 @@ static int parse_only(const std::string &path, const char *mode) {
         return 0;
     }
     Input data;
-    if (!data.open(path)) { std::cerr << "Error reading " << path << "\n"; return 1; }
+    data.bam = &kBamHooks;
+    if (!data.open(path)) {
+        if (!data.bam_error.empty()) std::cerr << "Error: could not read BAM input " << path << ": " << data.bam_error << "\n";
+        else std::cerr << "Error reading " << path << "\n";
+        return 1;
+    }
     if (strncmp(mode, "ranks:", 6) == 0) {
         // ranks:W — every rank's share of the file (parse_rank_range), one after the other; accepted only if EVERY rank accepts its
         // share, as the command line decides it from a sum over the ranks — else the whole file, as every rank would parse it then

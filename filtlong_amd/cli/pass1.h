@@ -45,8 +45,17 @@ static int open_reads_input(Run &run, ReadsInput &in) {
         const char *rs_env = getenv("FLX_CLI_RANK_STREAM");
         const bool rank_stream = !args.verbose && (rs_env ? rs_env[0] != '0' : (gz && st.st_size >= ((off_t)1 << 30)));
         in.streamed = regular && (run.world == 1 || rank_stream) && !getenv("FLX_CLI_NO_STREAM") && (gz || getenv("FLX_CLI_FORCE_STREAM"));
+        if (gz) {  // unaligned BAM (bam.h) is always taken into memory: Input::open turns it into FASTQ text, on every rank
+            MappedFile file;
+            if (file.open(args.input_reads) && bam_detect(file.p, file.n)) in.streamed = false;
+        }
+        in.data.bam = &kBamHooks;
     }
-    if (in.streamed ? !in.blocks.open(args.input_reads, true) : !in.data.open(args.input_reads)) { std::cerr << "Error reading " << args.input_reads << "\n"; return 1; }
+    if (in.streamed ? !in.blocks.open(args.input_reads, true) : !in.data.open(args.input_reads)) {
+        if (!in.streamed && !in.data.bam_error.empty()) std::cerr << "Error: could not read BAM input " << args.input_reads << ": " << in.data.bam_error << "\n";
+        else std::cerr << "Error reading " << args.input_reads << "\n";
+        return 1;
+    }
     run.stage("read input file");
     return kGoOn;
 }

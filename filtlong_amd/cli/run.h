@@ -18,6 +18,7 @@
 #include "../../include/filtlong_hip.h"
 
 #include "args.h"
+#include "bam.h"
 #include "fastx.h"
 #include "gzblocks.h"
 
@@ -116,6 +117,13 @@ struct Run {
             if (ctx_rc != FLX_OK || !ctx) return nullptr;
             if (flx_bgzf_create(ctx, 16u << 20, (unsigned)std::min<size_t>(host_threads(), 16), &z) != FLX_OK) return nullptr;
             return z;
+        };
+    }
+    // FLX_CLI_GPU_BAM=1: a BAM input is turned into text on the device (bam.h), which then waits for the context like the inflater
+    void arm_bam() {
+        g_bam.ctx = [this]() -> flx_ctx * {
+            if (ctx_thread.joinable()) ctx_thread.join();
+            return ctx_rc == FLX_OK ? ctx : nullptr;
         };
     }
     // a rank's file in the job's private directory: its "part" of the output, its "vblocks" and "vtable" of --verbose

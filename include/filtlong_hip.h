@@ -370,6 +370,43 @@ int flx_bgzf_inflate(flx_bgzf *z, const void *in, const uint64_t *in_off, const 
                      uint64_t *first_bad);
 
 /* ------------------------------------------------------------------------------------------
+ * unaligned BAM to FASTQ text (added under version 4): the layer inside the BGZF container.  Input is INFLATED BAM (SAM/BAM
+ * specification 4.2): the header, then records that each start with their block_size.  A record is valid when block_size >= 32,
+ * l_read_name >= 1 with a NUL as the name's last byte, l_seq >= 0, 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq <=
+ * block_size (in 64 bits) and it lies inside the buffer; CIGAR and tags are skipped, never interpreted.  Its text is
+ *   '@' name '\n' SEQ '\n' '+' '\n' QUAL '\n'      (l_read_name + 2 l_seq + 5 bytes; at most twice the record's block_size + 4)
+ * with SEQ from "=ACMGRSVTWYHKDBN", QUAL = min(q, 93) + 33, or '"' (quality 1) at every position when the first quality byte is 0xFF
+ * (no qualities stored); flag 0x10 gives the reverse complement (IUPAC; '=' and 'N' stay) and the reversed qualities; flags 0x40 /
+ * 0x80 do not change the name.  A record with flag 0x100 or 0x800 (secondary, supplementary) or with l_seq == 0 has no text: it is
+ * skipped and counted.
+ *   flx_bam_index         host only, no device: checks the header and walks the records from the first to the last whole, valid one
+ *                         within n bytes, or to max_records.  rec_off[0..m] are the records' offsets (rec_off[0]: the end of the
+ *                         header; m + 1 entries, so room for max_records + 1; NULL: count only), *n_records = m and *end_state
+ *                         tells why the walk ended (FLX_BAM_*): a rule that the bytes present already break is MALFORMED
+ *                         (HEADER inside the header), a buffer that ends before a rule can be checked is TRUNCATED.
+ *   flx_bam_to_fastq_dev  device to device on the context's stream (timed as "flx_bam"): record k is the bytes [d_rec_off[k],
+ *                         d_rec_off[k+1]) of d_bam[0, n).  d_out_off[0..n_records] (device, u64) gets the text offsets: a skipped
+ *                         record has d_out_off[k+1] == d_out_off[k]; *out_len the text length, *n_skipped the skipped records.
+ *                         FLX_ERR_CAPACITY when out_cap is below the text length (*out_len = the length needed; nothing is
+ *                         written).  A record the device finds invalid is data, not an error: *first_bad = the lowest such k (else
+ *                         n_records), it counts as no text, and the text is then no result.  n_records == 0 is a no-op.
+ *   flx_bam_to_fastq      host to host through two pinned staging slots with a stream each, in pieces of whole records of at most
+ *                         piece_bytes of BAM (0: 32 MiB; the staging grows to the largest record): copy-in, kernels and copy-out
+ *                         of consecutive pieces overlap.  out_off (host, n_records + 1 entries) may be NULL.  Stops in front of
+ *                         *first_bad: the text of the records before it is in out.  FLX_ERR_CAPACITY as above.
+ * ---------------------------------------------------------------------------------------- */
+#define FLX_BAM_END 0       /* the last record ends where the data ends                         */
+#define FLX_BAM_TRUNCATED 1 /* the data ends inside the header or inside record *n_records      */
+#define FLX_BAM_MALFORMED 2 /* record *n_records breaks a rule                                  */
+#define FLX_BAM_HEADER 3    /* the header does: no magic, a negative length                     */
+#define FLX_BAM_MORE 4      /* max_records were taken and data is left                          */
+int flx_bam_index(const void *bam, uint64_t n, uint64_t max_records, uint64_t *rec_off, uint64_t *n_records, int *end_state);
+int flx_bam_to_fastq_dev(flx_ctx *ctx, const void *d_bam, uint64_t n, const uint64_t *d_rec_off, uint64_t n_records, void *d_out,
+                         uint64_t out_cap, uint64_t *d_out_off, uint64_t *out_len, uint64_t *n_skipped, uint64_t *first_bad);
+int flx_bam_to_fastq(flx_ctx *ctx, const void *bam, uint64_t n, const uint64_t *rec_off, uint64_t n_records, uint64_t piece_bytes,
+                     void *out, uint64_t out_cap, uint64_t *out_off, uint64_t *out_len, uint64_t *n_skipped, uint64_t *first_bad);
+
+/* ------------------------------------------------------------------------------------------
  * read summary (added under version 4): what a set of reads looks like — entries, bases, shortest, longest, median, N10..N90
  * and the histograms of length, mean quality and window quality — from the per-read arrays of seam 2 / the reads2 gather and
  * the pass flags of seam 3.  The reference has no counterpart: its users run a statistics tool over the input and again over
