@@ -15,61 +15,46 @@
 #include "kmerset.h"
 #include "cover_common.h"
 #include "rank_internal.h"
-#include "score_kmer_common.h"
+#include "fold_common.h"
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------------
 // serial fold over the coverage bits
 // ---------------------------------------------------------------------------------------------------
-#ifndef FLX_FOLD_FMA
-#define FLX_FOLD_FMA 1
-#endif
-// (the grid table, the folds' arguments and the shared result code: fold_grid_tab.h, score_kmer_common.h)
-// MODE 0: parent only (no --trim/--split).  MODE 1: parent + count children, bit by bit.  MODE 2: emit children.
-// MODE 4: emit children with the zero-run events found at word level and a branch-light bit loop (same condition as 3).
-// MODE 3: parent + count children at WORD level — a zero run can only be a bad range if it starts at position 0, reaches
-// the end of the read, or is at least --split long; with --split >= 32 (or unset) every such run crosses a 32-bit word
-// boundary, so the runs that lie inside one word never matter and the parent keeps MODE 0's branch-free steady state.
-// MODE 5: the word-level events of MODE 3 once more, without any floating point: writes every child's (start, end) and its
-// read's index at the child's place in the CSR.  MODE 6: ONE LANE PER CHILD, children in descending order of length — a child
-// is a read of its own (src/read.cpp:131-137: Read(child name, seq + start, ...)), so its lane runs MODE 0's branch-free
-// recurrence on the parent's coverage bits [start, end) (the row words funnel-shifted by start mod 32) and writes the child's
-// mean / window / pass flag.  5 + 6 replace MODE 4, whose 32 predicated positions per word carry the event machinery through
-// every bit (67 of the 98 ms per 10^11 positions of C4's folds).
-#ifndef FLX_FOLD_WALK_COPIES
-#define FLX_FOLD_WALK_COPIES 1  // copies of the integer-grid fold's walk table in LDS (a power of two; 1, 8, 16 measured: no difference — the gathers are not what bounds the kernel)
-#endif
-#ifdef FLX_FOLD_WAVES_PER_EU  // (A/B builds: the register budget of the fold kernels)
-#define FLX_FOLD_OCC __attribute__((amdgpu_waves_per_eu(FLX_FOLD_WAVES_PER_EU)))
-#else
-#define FLX_FOLD_OCC
-#endif
+// (the modes, the row as a lane sees it, the zero-run rule and the steps of one word: fold_common.h; the grid table and the start of
+// a regime: fold_grid_tab.h; the folds' arguments and the shared result code: score_kmer_common.h)
+// One lane per slot — a read, or in the mode whose slots are children a child — and per word of 32 positions four phases:
+// the zero-run events of the word, the head shortcut, the steady state, the positions one by one.  What a mode does in each is
+// kFoldModes' to say.  The register budget was A/B-built with amdgpu_waves_per_eu and left to the compiler: no setting won.
 template <int MODE, bool RING, bool GRID = false>
-__global__ void __launch_bounds__(256) FLX_FOLD_OCC k_kmer_fold(const FoldArgs a) {
+__global__ void __launch_bounds__(256) k_kmer_fold(const FoldArgs a) {
+    constexpr FoldMode M = kFoldModes[MODE];
+    constexpr bool kChild = M.child;
     const uint64_t slot = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    bool live = slot < (MODE == 6 ? a.n_children : a.n_reads);
-    uint32_t rid = 0;  // MODE 6: the child's index
+    bool live = slot < (kChild ? a.n_children : a.n_reads);
+    uint32_t rid = 0;  // the read's index, or the child's
     int L = 0;
-    const uint32_t *row = a.cov;
-    int row_words_left = 0;       // MODE 6: words of the parent's row from `row` on
-    uint32_t bit_off = 0;         // MODE 6: the child starts at bit `bit_off` (0..127) of row[0]
-    if (live && MODE != 6) {
+    FoldRow row;
+    row.row = a.cov;
+    row.bit_off = 0;
+    int row_words_left = 0;  // a child: words of the parent's row from row.row on
+    if (live && !kChild) {
         rid = a.order ? a.order[slot] : (uint32_t)slot;
         L = a.lengths[rid];
-        row = a.cov + (a.cov_off[rid] >> 2);
+        row.row = a.cov + (a.cov_off[rid] >> 2);
     }
-    if (live && MODE == 6) {
+    if (live && kChild) {
         rid = a.child_order[slot];
         const uint32_t parent = a.child_parent[rid];
         const int start = a.child_ranges[2 * (size_t)rid], end = a.child_ranges[2 * (size_t)rid + 1];
         L = end - start;
         const int base_word = (start >> 7) << 2;  // 16-byte aligned piece of the row the child starts in
-        row = a.cov + (a.cov_off[parent] >> 2) + base_word;
+        row.row = a.cov + (a.cov_off[parent] >> 2) + base_word;
         row_words_left = ((a.lengths[parent] + 31) >> 5) - base_word;
-        bit_off = (uint32_t)(start - 32 * base_word);
+        row.bit_off = (uint32_t)(start - 32 * base_word);
     }
-    if ((MODE == 0 || MODE == 3 || MODE == 5 || MODE == 6) && a.long_min > 0 && L >= a.long_min) {
+    if (M.leaves_long && a.long_min > 0 && L >= a.long_min) {
         // a long read or child: the cooperative path's (score_kmer_long.hip) — this lane folds nothing and writes nothing
         live = false;
         L = 0;
@@ -77,497 +62,72 @@ __global__ void __launch_bounds__(256) FLX_FOLD_OCC k_kmer_fold(const FoldArgs a
     int Lmax = L;
     for (int o = 32; o > 0; o >>= 1) Lmax = max(Lmax, __shfl_xor(Lmax, o, 64));
     const int ws = a.ws;
-    const double delta = a.delta;
 
     Win P = {0, 0.0, 0.0};
-    // child machinery
-    Win C = {0, 0.0, 0.0};
-    Win S = {0, 0.0, 0.0};  // snapshot of C at the start of the current zero run
-    int cs = 0;             // start of the current child candidate
-    int zs = -1;            // start of the current zero run (-1: none)
-    bool any_bad = false;
-    uint32_t nchild = 0;
-    const uint64_t cbase = ((MODE == 2 || MODE == 4 || MODE == 5) && live) ? a.child_offsets[rid] : 0;
-    const bool split_set = a.p.split_set != 0;
-    const bool trim = a.p.trim != 0;
-    const int split = a.p.split;
+    Children K;
+    const uint64_t cbase = ((M.out & kOutRanges) && live) ? a.child_offsets[rid] : 0;
+    const ZeroRunRule rule(a.p);
 
-    auto emit_child = [&](int start, int end, const Win &st) {
-        if (end <= start) return;
-        if (MODE == 5) {
-            const uint64_t at = cbase + nchild;
-            a.child_ranges[2 * at] = start;
-            a.child_ranges[2 * at + 1] = end;
-            a.child_parent[at] = rid;
-        }
-        if (MODE == 3 && a.inline_ranges && nchild < (uint32_t)kInlineChildren) {
-            int32_t *slot = a.inline_ranges + ((size_t)rid * kInlineChildren + nchild) * 2;
-            slot[0] = start;
-            slot[1] = end;
-        }
-        if (MODE == 2 || MODE == 4) {
-            const int len = end - start;
-            const double mean = 100.0 * (double)st.cnt / (double)len;
-            const double window = window_result(a, len, st.cnt, st.mn);
-            const uint64_t at = cbase + nchild;
-            a.child_ranges[2 * at] = start;
-            a.child_ranges[2 * at + 1] = end;
-            a.child_mean_q[at] = mean;
-            a.child_window_q[at] = window;
-            a.child_passed[at] = cutoffs(a.p, len, mean, window);
-        }
-        ++nchild;
-    };
-
-    // Two word streams over the read's coverage row — the leading edge (position j) and the trailing edge (position
-    // j - ws).  Each lane walks its own row: 64 lanes = 64 distinct lines per load instruction, and the rows of all resident
-    // lanes do not fit L1 / L2 together, so a line is gone again before the lane comes back to it — every load of a new piece
-    // is a far request (55 G/s, profiles/r03_microbench.txt).
-    //   RING (default): the row is read ONCE, 64 bytes per lane at a time (four 16-byte loads issued back to back to one
-    //   half line, a block ahead of their use), and parked in a per-lane ring of words in LDS (word k of lane l at
-    //   ((k mod R) * 64 + l): every access of a wave is conflict free and touches only the lane's own words, so no barrier).
-    //   Both edges then come out of the ring with ds_read_b32: one far request per 512 positions instead of two per 128,
-    //   which had made the folds request bound (round 2: 28 of the 36 ms per 10^11 positions).
-    //   !RING: both streams straight from global memory in 16-byte blocks (windows too long for the ring).
-    const int n_words = MODE == 6 ? row_words_left : (L + 31) >> 5;  // words of the row that exist behind `row`
-    const int o5 = (int)(bit_off >> 5);                                // MODE 6: the child's word k = row words k + o5, k + o5 + 1 ...
-    const unsigned o = bit_off & 31u;                                  // ... shifted right by o bits
-    auto ldq = [&](int b) -> uint4 {
-        return (b * 4 < n_words) ? *reinterpret_cast<const uint4 *>(row + 4 * (size_t)b) : make_uint4(0u, 0u, 0u, 0u);
-    };
-    struct WStream { uint4 cur, nxt; int blk; };
-    auto advance = [&](WStream &st, int b) {  // streams only move forward, one block at a time
-        if (b != st.blk) {
-            st.cur = st.nxt;
-            st.blk = b;
-            st.nxt = ldq(b + 1);
-        }
-    };
-    auto word = [&](const WStream &st, int wi) -> uint32_t {  // wi inside block st.blk or st.blk + 1
-        // (selects, no reference to one of the two blocks: a reference makes the compiler keep the stream in scratch memory)
-        const bool cur = (wi >> 2) == st.blk;
-        const int c = wi & 3;
-        const uint32_t x = cur ? st.cur.x : st.nxt.x, y = cur ? st.cur.y : st.nxt.y, z = cur ? st.cur.z : st.nxt.z, w = cur ? st.cur.w : st.nxt.w;
-        const uint32_t v = c == 0 ? x : c == 1 ? y : c == 2 ? z : w;
-        return wi < n_words ? v : 0u;  // the padding of the last block is not coverage
-    };
-    WStream lead = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u), 0};
-    if (!RING) lead = {ldq(0), ldq(1), 0};
-    WStream trail = lead;
-    extern __shared__ uint32_t fold_ring[];
-    const int R = a.ring_words;  // power of two >= 16 + ceil(ws / 32) + 2
-    // GRID: in front of the rings the table of the +-1 walk of four positions, indexed by (new nibble << 4 | old nibble): two dwords,
-    // {lowest prefix, -(highest prefix)} and {total, -total} as pairs of 16-bit integers (packed adds and minima carry both at once)
-    // ... and behind it the grid table itself (GridTab: d* and the lower bound per binade, 4 dwords per entry): a regime begins in
-    // the middle of the steady state, and a load from the kernel's arguments there costs the whole wave a trip to memory
-    // (kWalkCopies copies of the walk table, entry idx of copy c at (idx * copies + c): a lane reads copy lane % copies, so that
-    // lanes with different nibble pairs rarely meet in one bank — with one copy the 64 lanes of a gather share 32 bank pairs)
-    constexpr int kWalkCopies = FLX_FOLD_WALK_COPIES;
-    constexpr int kGridTabAt = 512 * kWalkCopies;  // dword index of the grid table
-    constexpr int kWalkWords = GRID ? kGridTabAt + 8 * 32 : 0;
-    if (GRID) {
-        for (int i = threadIdx.x; i < GridTab::kMax; i += blockDim.x) {
-            fold_ring[kGridTabAt + 8 * i + 0] = (uint32_t)__double2loint(a.gt.dstar[i]);
-            fold_ring[kGridTabAt + 8 * i + 1] = (uint32_t)__double2hiint(a.gt.dstar[i]);
-            fold_ring[kGridTabAt + 8 * i + 2] = (uint32_t)__double2loint(a.gt.lv[i]);
-            fold_ring[kGridTabAt + 8 * i + 3] = (uint32_t)__double2hiint(a.gt.lv[i]);
-            fold_ring[kGridTabAt + 8 * i + 4] = (uint32_t)a.gt.top[i];
-        }
-        for (int idx = threadIdx.x; idx < 256; idx += blockDim.x) {
-            int t = 0, mp = 0, xp = 0;
-            for (int i = 0; i < 4; ++i) {
-                t += ((idx >> (4 + i)) & 1) - ((idx >> i) & 1);
-                mp = min(mp, t);
-                xp = max(xp, t);
-            }
-            for (int c = 0; c < kWalkCopies; ++c) {
-                fold_ring[2 * (idx * kWalkCopies + c)] = ((uint32_t)mp & 0xffffu) | ((uint32_t)(-xp) << 16);
-                fold_ring[2 * (idx * kWalkCopies + c) + 1] = ((uint32_t)t & 0xffffu) | ((uint32_t)(-t) << 16);
-            }
-        }
-        __syncthreads();
-    }
-    uint32_t *ring = fold_ring + kWalkWords + (size_t)(threadIdx.x >> 6) * (size_t)R * 64 + (threadIdx.x & 63);
-    uint4 nq[4];       // the block after the newest one in the ring
-    int have_blk = -1;  // newest block in the ring (wave-uniform: every lane is at the same position)
-    if (RING) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) nq[q] = ldq(q);
-    }
-    auto ring_fill = [&](int wi) {  // word wi (and everything up to the end of its block) into the ring; wi only moves forward
-        const int b = wi >> 4;
-        if (b > have_blk) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int k = (b * 16 + 4 * q) & (R - 1);
-                ring[(k + 0) * 64] = nq[q].x; ring[(k + 1) * 64] = nq[q].y; ring[(k + 2) * 64] = nq[q].z; ring[(k + 3) * 64] = nq[q].w;
-            }
-            have_blk = b;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) nq[q] = ldq((b + 1) * 4 + q);
-        }
-    };
-    auto ring_word = [&](int wi) -> uint32_t { return wi < n_words ? ring[(wi & (R - 1)) * 64] : 0u; };
-    // MODE 6: bit p of the child is bit p + bit_off of the row, so 32 child positions from position p on are row words
-    // (p + bit_off) / 32 and the next one, funnel-shifted by (p + bit_off) mod 32
-    auto lead_bits = [&](int p) -> uint32_t {  // p a multiple of 32, moving forward
-        const int w = (p >> 5) + o5;
-        uint32_t lo, hi;
-        if (RING) { ring_fill(w + 1); lo = ring_word(w); hi = ring_word(w + 1); }
-        else { advance(lead, w >> 2); lo = word(lead, w); hi = word(lead, w + 1); }
-        return __builtin_amdgcn_alignbit(hi, lo, o);
-    };
-    auto trail_bits = [&](int p) -> uint32_t {  // any p >= 0 behind the leading edge, moving forward
-        const int t = p + (int)bit_off, w = t >> 5;
-        uint32_t lo, hi;
-        if (RING) { lo = ring_word(w); hi = ring_word(w + 1); }
-        else { advance(trail, w >> 2); lo = word(trail, w); hi = word(trail, w + 1); }
-        return __builtin_amdgcn_alignbit(hi, lo, (unsigned)(t & 31));
-    };
-    auto lead_word = [&](int wi) -> uint32_t {  // the word holding the leading edge
-        if (MODE == 6) return lead_bits(wi << 5);
-        if (RING) { ring_fill(wi); return ring_word(wi); }
-        advance(lead, wi >> 2);
-        return word(lead, wi);
-    };
-    auto trail_word = [&](int wi) -> uint32_t {  // words of the trailing edge: never ahead of the leading one
-        if (MODE == 6) return trail_bits(wi << 5);
-        if (RING) return ring_word(wi);
-        advance(trail, wi >> 2);
-        return word(trail, wi);
-    };
-    uint32_t lead_w = 0, trail_w = 0;
+    row.n_words = kChild ? row_words_left : (L + 31) >> 5;
+    extern __shared__ uint32_t fold_lds[];  // GRID: the walk table and the grid table (kGridLdsWords dwords); then the rings
+    if (GRID) grid_lds_fill(fold_lds, a.gt);
+    row.R = a.ring_words;
+    row.ring = fold_lds + (GRID ? kGridLdsWords : 0) + (size_t)(threadIdx.x >> 6) * (size_t)row.R * 64 + (threadIdx.x & 63);
+    row.begin<RING>();
     int Lmin = live ? L : 0x7fffffff;
     for (int o = 32; o > 0; o >>= 1) Lmin = min(Lmin, __shfl_xor(Lmin, o, 64));
-    const unsigned int d_lo = (unsigned int)(__double_as_longlong(delta) & 0xffffffffll);
-    const unsigned int d_hi = (unsigned int)(__double_as_longlong(delta) >> 32);
-    // GRID: the regime of this lane's parent window (w = g_wb + g_c * g_ds while it holds; lowest c so far in g_cmin)
-    double g_wb = 0.0, g_ds = 0.0;
-    int g_c = 0, g_cmin = 0, g_lo = 0x7fffffff, g_hi = (int)0x80000000;
-    bool grid_on = false;  // wave-uniform: the steady state has begun (and not ended)
-    auto grid_flush = [&]() {  // the regime's state as the recurrence's: exact, every operand is a multiple of the regime's grid
-        P.mn = fmin(P.mn, fma((double)g_cmin, g_ds, g_wb));
-        P.w = fma((double)g_c, g_ds, g_wb);
-    };
-    auto grid_begin = [&]() {  // a regime from P.w on (tools/sim_fold_grid.cpp: begin_regime — the same arithmetic)
-        g_wb = P.w;
-        g_ds = 0.0;
-        g_c = 0;
-        g_cmin = 0;
-        g_lo = 0x7fffffff;
-        g_hi = (int)0x80000000;
-        const int eb = (__double2hiint(P.w) >> 20) & 0x7ff;
-        const int idx = eb - a.gt.e0;
-        if (P.w > 0.0 && idx >= 0 && idx < a.gt.n) {
-            const uint4 e = *reinterpret_cast<const uint4 *>(fold_ring + kGridTabAt + 8 * idx);
-            const double ds = __hiloint2double((int)e.y, (int)e.x), lv = __hiloint2double((int)e.w, (int)e.z);
-            if (ds > 0.0) {
-                // The top: w must not reach a binade on whose grid w_b does NOT lie (its low bits would be rounded away there).  w_b
-                // lies on the grid of binade eb + z, z = the trailing zero bits of its mantissa — a window that has once been full
-                // (w = 1.0) stays on the grid of [1, 2) whatever is subtracted, d* is a multiple of it — up to the top of the group.
-                const uint32_t m_lo = (uint32_t)__double2loint(P.w), m_hi = ((uint32_t)__double2hiint(P.w) & 0xfffffu) | 0x100000u;
-                const int z = m_lo ? __ffs((int)m_lo) - 1 : 32 + (__ffs((int)m_hi) - 1);
-                const int gb = min(eb + z, (int)fold_ring[kGridTabAt + 8 * idx + 4]);
-                const double uv = __hiloint2double((gb + 1) << 20, 0);
-                // smallest c with w + c d* > lv: the estimate's floor is the answer or up to two below it; the values decide
-                int k0 = (int)floor((lv - P.w) * a.ws_d);
-                if (fma((double)k0, ds, P.w) <= lv) ++k0;
-                if (fma((double)k0, ds, P.w) <= lv) ++k0;
-                // largest c with w + c d* < uv
-                int k1 = (int)ceil((uv - P.w) * a.ws_d);
-                if (fma((double)k1, ds, P.w) >= uv) --k1;
-                if (fma((double)k1, ds, P.w) >= uv) --k1;
-                g_ds = ds;
-                g_lo = k0;
-                g_hi = k1;
-            }
-        }
-    };
+    GridLane g;
+    uint32_t trail_w = 0;  // the trailing edge's word of the per-position phase
     for (int j0 = 0; j0 < Lmax; j0 += 32) {
-      lead_w = lead_word(j0 >> 5);
-      if (MODE == 4) {
-          // ---- children only: events per word, then 32 predicated positions ----
-          int ev_end = -1, ev_zs = 0, snap = -1;
-          if (j0 < L) {
-              const int v = min(32, L - j0);
-              const uint32_t w = v < 32 ? (lead_w & ((1u << v) - 1u)) : lead_w;
-              if (j0 == 0 && !(w & 1u)) zs = 0;  // S is still the initial (empty) state
-              if (w != 0) {
-                  if (zs >= 0) {
-                      const int f = __ffs(w) - 1;
-                      const bool bad = (split_set && j0 + f - zs >= split) || (trim && zs == 0);
-                      if (bad) { ev_end = f; ev_zs = zs; }
-                      zs = -1;
-                  }
-                  const int top = 32 - __clz(w);
-                  if (top < v) { zs = j0 + top; snap = top; }
-              } else if (zs < 0) {
-                  zs = j0;
-                  snap = 0;
-              }
-          }
-          // trailing window of the 32 positions (positions before the read count as uncovered; they are never used,
-          // a child's trailing edge lies inside the child)
-          const int tj0 = j0 - ws;
-          uint32_t tw = 0;
-          if (tj0 > -32) {
-              const int twi = tj0 >> 5, sh = tj0 & 31;  // twi == -1 for the word that straddles position 0
-              const uint32_t lo = twi >= 0 ? trail_word(twi) : 0u;
-              tw = sh ? __builtin_amdgcn_alignbit(trail_word(twi + 1), lo, (unsigned)sh) : lo;
-          }
-#pragma unroll
-          for (int i = 0; i < 32; ++i) {
-              const int j = j0 + i;
-              if (i == ev_end) {  // a bad range ended here: the child [cs, ev_zs) is complete, a new one starts at j
-                  any_bad = true;
-                  emit_child(cs, ev_zs, S);
-                  cs = j;
-                  C.cnt = 0;
-                  C.w = 0.0;
-                  C.mn = 0.0;
-              }
-              if (i == snap) {  // state of the current child at the start of a zero run that may turn out bad
-                  S.cnt = C.cnt;
-                  S.mn = C.mn;
-              }
-              const bool act = j < L;
-              const int k = j - cs;
-              const int ml = __builtin_amdgcn_sbfe((int)lead_w, i, 1);  // 0 or -1 (bits beyond L are 0)
-              const int mt = __builtin_amdgcn_sbfe((int)tw, i, 1);
-              C.cnt -= ml;
-              if (act && k == ws - 1) {
-                  C.w = (double)C.cnt / a.ws_d;
-                  C.mn = C.w;
-              }
-              const bool steady = act && k >= ws;
-              const int ms = steady ? -1 : 0;
-              const double dl = __hiloint2double((int)(d_hi & (unsigned)(ml & ms)), (int)(d_lo & (unsigned)(ml & ms)));
-              const double dt = __hiloint2double((int)(d_hi & (unsigned)(mt & ms)), (int)(d_lo & (unsigned)(mt & ms)));
-              C.w -= dt;  // exact no-ops outside the steady state
-              C.w += dl;
-              const double m2 = fmin(C.mn, C.w);
-              C.mn = steady ? m2 : C.mn;
-          }
-          continue;
-      }
-      if ((MODE == 3 || MODE == 5) && j0 < L) {
-          const int v = min(32, L - j0);  // valid bits of this word
-          const uint32_t w = v < 32 ? (lead_w & ((1u << v) - 1u)) : lead_w;
-          if (j0 == 0 && !(w & 1u)) zs = 0;  // the read starts inside a zero run
-          if (w != 0) {
-              if (zs >= 0) {  // the run [zs, j) that reached this word ends at its first covered base
-                  const int j = j0 + __ffs(w) - 1;
-                  const bool bad = (split_set && j - zs >= split) || (trim && zs == 0);
-                  if (bad) {
-                      any_bad = true;
-                      emit_child(cs, zs, S);  // (counts it; MODE 5 also writes its range)
-                      cs = j;
-                  }
-                  zs = -1;
-              }
-              const int top = 32 - __clz(w);  // one past the last covered base of the word
-              if (top < v) zs = j0 + top;     // the word ends inside a new zero run
-          } else if (zs < 0) {
-              zs = j0;
-          }
-      }
-      if (MODE == 5) continue;
-      if ((MODE == 0 || MODE == 3 || MODE == 6) && j0 + 32 <= ws - 1 && j0 + 32 <= Lmin) {
-          // ---- the head, a word at a time: every position of the word lies in front of the first full window (j < ws - 1) and inside
-          // every read of the wave — the recurrence has not begun, only the covered bases are counted (src/read.cpp:221-225).  (The
-          // per-bit loop below spent ~20 instructions on each of these positions: a fifth of a 10 kbp read's fold once the steady state
-          // ran on the integer grid.)
-          P.cnt += __popc(lead_w);
-          continue;
-      }
-      if ((MODE == 0 || MODE == 3 || MODE == 6) && j0 >= ws && j0 + 32 <= Lmin) {
-          // ---- steady state, one window per lane: 32 positions, every lane active, no per-bit control flow ----
-          uint32_t tw;
-          if (MODE == 6) {
-              tw = trail_bits(j0 - ws);
-          } else {
-              const int tj0 = j0 - ws, sh = tj0 & 31, twi = tj0 >> 5;
-              const uint32_t t0 = trail_word(twi);
-              tw = sh ? __builtin_amdgcn_alignbit(trail_word(twi + 1), t0, (unsigned)sh) : t0;
-          }
-          P.cnt += __popc(lead_w);
-          if (GRID) {
-              if (!grid_on) {
-                  grid_begin();
-                  grid_on = true;
-              }
-              typedef short s16x2 __attribute__((ext_vector_type(2)));
-              // the (new, old) nibble pairs of the word: byte k of `even` = nibbles 2k, of `odd` = nibbles 2k + 1
-              const uint32_t odd = (lead_w & 0xF0F0F0F0u) | ((tw >> 4) & 0x0F0F0F0Fu);
-              const uint32_t even = ((lead_w << 4) & 0xF0F0F0F0u) | (tw & 0x0F0F0F0Fu);
-              const uint2 *walk = reinterpret_cast<const uint2 *>(fold_ring) + (threadIdx.x & (kWalkCopies - 1));
-              s16x2 run = {0, 0}, ext = {0, 0};  // {prefix, -prefix} so far; {lowest prefix, -(highest prefix)}
-#pragma unroll
-              for (int k = 0; k < 8; ++k) {
-                  const uint32_t idx = ((k & 1 ? odd : even) >> (8 * (k >> 1))) & 0xffu;
-                  const uint2 e = walk[idx * kWalkCopies];
-                  ext = __builtin_elementwise_min(ext, run + __builtin_bit_cast(s16x2, e.x));
-                  run = run + __builtin_bit_cast(s16x2, e.y);
-              }
-              const int mp = ext.x, xp = -(int)ext.y, t = run.x;
-              // not a no-op (a word of zeros on both edges changes nothing in any regime) and outside the regime: this lane's word in FP
-#ifdef FLX_FOLD_GRID_NOSLOW  // (timing experiment only: wrong results)
-              const bool slow = false;
-#else
-              const bool slow = (lead_w | tw) != 0u && !(g_c + mp >= g_lo && g_c + xp <= g_hi);
-#endif
-              if (!__any(slow)) {
-                  g_cmin = min(g_cmin, g_c + mp);
-                  g_c += t;
-                  continue;
-              }
-              if (!slow) {
-                  g_cmin = min(g_cmin, g_c + mp);
-                  g_c += t;
-                  lead_w = tw = 0;  // (32 exact no-ops below)
-              } else {
-                  grid_flush();
-              }
-              // (four rounds of eight steps, not 32 unrolled: unrolled, the compiler converts all 64 bits to doubles ahead of the chain
-              // and the kernel needs 122 registers, or spills)
-#pragma unroll 1
-              for (int i0 = 0; i0 < 32; i0 += 8) {
-#pragma unroll
-                  for (int i = 0; i < 8; ++i) {
-                      const double lb = (double)__builtin_amdgcn_ubfe(lead_w, i0 + i, 1);
-                      const double tb = (double)__builtin_amdgcn_ubfe(tw, i0 + i, 1);
-                      P.w = fma(tb, -delta, P.w);
-                      P.w = fma(lb, delta, P.w);
-                      P.mn = fmin(P.mn, P.w);
-                  }
-              }
-              if (slow) grid_begin();
-              continue;
-          }
-          if (a.events) {
-              // Round-3 review, item 5: only the positions where the two edges DIFFER change w for certain (one exact step each);
-              // where both are 0 nothing happens, and where both are 1 the step is fl(fl(w - d) + d), which is w itself unless the
-              // subtraction leaves w's binade — checked once per stretch of such positions, with the 32-step loop below as the
-              // fallback for a word where it fails.  Lanes diverge (a wave runs as many rounds as its busiest lane has events).
-              const double w0 = P.w, mn0 = P.mn;
-              const uint32_t both = lead_w & tw;
-              uint32_t ev = lead_w ^ tw, handled = 0;
-              bool slow = false;
-              for (;;) {
-                  const int i = ev ? __ffs(ev) - 1 : 32;
-                  const uint32_t upto = i == 32 ? 0xffffffffu : ((1u << i) - 1u);
-                  if (both & upto & ~handled) {
-                      double t = P.w - delta;
-                      t = t + delta;
-                      if (t != P.w) { slow = true; break; }
-                  }
-                  if (i == 32) break;
-                  if ((lead_w >> i) & 1u) {
-                      P.w = P.w + delta;
-                  } else {
-                      P.w = P.w - delta;
-                      P.mn = fmin(P.mn, P.w);
-                  }
-                  handled = upto | (1u << i);
-                  ev &= ev - 1;
-              }
-              if (!__any(slow)) continue;
-              if (!slow) {
-                  lead_w = tw = 0;  // (this lane is done with the word: 32 exact no-ops below)
-              } else {
-                  P.w = w0;
-                  P.mn = mn0;
-              }
-          }
-#pragma unroll
-          for (int i = 0; i < 32; ++i) {
-#if FLX_FOLD_FMA
-              // w - q[j-ws]/ws and + q[j]/ws with q in {0.0, 1.0} (src/read.cpp:228-229) as fma(bit, -+delta, w): the product is exact
-              // (0 or delta), so the one rounding of the fma is the rounding of the reference's subtraction / addition, and
-              // adding a zero product leaves w as it is.  7 VALU instructions per position instead of 9 — the folds are VALU bound.
-              const double lb = (double)__builtin_amdgcn_ubfe(lead_w, i, 1);
-              const double tb = (double)__builtin_amdgcn_ubfe(tw, i, 1);
-              P.w = fma(tb, -delta, P.w);
-              P.w = fma(lb, delta, P.w);
-#else
-              const int ml = __builtin_amdgcn_sbfe((int)lead_w, i, 1);  // 0 or -1
-              const int mt = __builtin_amdgcn_sbfe((int)tw, i, 1);
-              const double dl = __hiloint2double((int)(d_hi & (unsigned)ml), (int)(d_lo & (unsigned)ml));
-              const double dt = __hiloint2double((int)(d_hi & (unsigned)mt), (int)(d_lo & (unsigned)mt));
-              P.w -= dt;
-              P.w += dl;
-#endif
-              P.mn = fmin(P.mn, P.w);
-          }
-          continue;
-      }
-      if (GRID && grid_on) {  // the steady state is over (the shortest read of the wave ends inside this word): back to the recurrence's own state
-          grid_flush();
-          grid_on = false;
-          g_ds = 0.0;
-          g_c = g_cmin = 0;
-          g_wb = P.w;
-      }
-      for (int jj = 0; jj < 32; ++jj) {
-        const int j = j0 + jj;
-        if (j >= Lmax) break;
-        const int tj = j - ws;
-        if (tj >= 0 && ((tj & 31) == 0 || jj == 0)) {
-            trail_w = trail_word(tj >> 5);
-        }
-        const bool act = j < L;
-        const uint32_t b = act ? ((lead_w >> (j & 31)) & 1u) : 0u;
-        const uint32_t tb = (act && tj >= 0) ? ((trail_w >> (tj & 31)) & 1u) : 0u;
-        const double dl = b ? delta : 0.0;
-        const double dt = tb ? delta : 0.0;
-
-        if (act) {
-            // ---- parent window (src/read.cpp:216-236) ----
-            P.cnt += (int)b;
-            if (j == ws - 1) {
-                P.w = (double)P.cnt / a.ws_d;
-                P.mn = P.w;
-            } else if (j >= ws) {
-                P.w -= dt;
-                P.w += dl;
-                if (P.w < P.mn) P.mn = P.w;
+        uint32_t lead_w = row.lead_word<RING, kChild>(j0 >> 5);
+        // ---- 1. events: the zero runs that end or begin in this word ----
+        if (M.events == kEvWord) {
+            const ZeroRunWord z = zero_run_word(rule, lead_w, j0, L, K.zs);
+            if (M.window == kWinChildWords) {  // the children's own recurrence, in this lane
+                child_word_positions<RING, M.out>(a, row, j0, L, lead_w, z, K, rid, cbase);
+                continue;
             }
-            if (MODE == 1 || MODE == 2) {
-                // ---- zero runs -> bad ranges -> children (src/read.cpp:89-141) ----
-                if (b == 0 && zs < 0) {
-                    zs = j;
-                    S = C;
-                }
-                if (b == 1 && zs >= 0) {  // the run [zs, j) has ended
-                    const bool bad = (split_set && j - zs >= split) || (trim && zs == 0);
-                    if (bad) {
-                        any_bad = true;
-                        emit_child(cs, zs, S);
-                        cs = j;
-                        C.cnt = 0;
-                        C.w = 0.0;
-                        C.mn = 0.0;
-                    }
-                    zs = -1;
-                }
-                const int k = j - cs;  // position inside the current child
-                C.cnt += (int)b;
-                if (k == ws - 1) {
-                    C.w = (double)C.cnt / a.ws_d;
-                    C.mn = C.w;
-                } else if (k >= ws) {
-                    C.w -= dt;
-                    C.w += dl;
-                    if (C.w < C.mn) C.mn = C.w;
-                }
+            if (z.ev_end >= 0) {
+                K.any_bad = true;
+                emit_child<M.out>(a, rid, cbase, K.n, K.cs, z.ev_zs, K.S);  // (counts it, and writes what the mode writes)
+                K.cs = j0 + z.ev_end;
             }
+            if (M.window == kWinNone) continue;
         }
-      }
+        // ---- 2. the head, a word at a time: every position of the word lies in front of the first full window (j < ws - 1) and inside
+        // every read of the wave — the recurrence has not begun, only the covered bases are counted (src/read.cpp:221-225).  (The
+        // per-position loop spent ~20 instructions on each of these positions: a fifth of a 10 kbp read's fold once the steady state
+        // ran on the integer grid.)
+        if (M.window == kWinWords && j0 + 32 <= ws - 1 && j0 + 32 <= Lmin) {
+            P.cnt += __popc(lead_w);
+            continue;
+        }
+        // ---- 3. steady state, one window per lane: the word's 32 positions at once (fold_word_*) ----
+        if (M.window == kWinWords && j0 >= ws && j0 + 32 <= Lmin) {
+            uint32_t tw = row.trail32<RING, kChild>(j0 - ws);
+            P.cnt += __popc(lead_w);
+            if (GRID) {
+                fold_word_grid(g, P, lead_w, tw, fold_lds, a);
+                continue;
+            }
+            if (a.events && fold_word_events(P, lead_w, tw, a.delta)) continue;
+            fold_word_fp<false>(P.w, P.mn, lead_w, tw, a.delta);
+            continue;
+        }
+        // ---- 4. per position (the shortest read of the wave ends inside this word, or the mode has no steady state) ----
+        if (GRID && g.on) {  // the steady state is over: back to the recurrence's own state
+            grid_flush(g, P);
+            g.on = false;
+            g.r.ds = 0.0;
+            g.c = g.cmin = 0;
+            g.r.wb = P.w;
+        }
+        fold_positions<RING, kChild, M.events, M.out>(a, row, j0, L, Lmax, lead_w, trail_w, P, rule, K, rid, cbase);
     }
-    if (GRID && grid_on) grid_flush();
+    if (GRID && g.on) grid_flush(g, P);
     if (!live) return;
 
-    if (MODE == 6) {  // the child's own scores (src/read.cpp:131-137 -> the Read constructor's folds on the child's slice)
+    if (M.out & kOutOwnScores) {  // the child's own scores (src/read.cpp:131-137 -> the Read constructor's folds on the child's slice)
         const double mean = 100.0 * (double)P.cnt / (double)L;
         const double window = window_result(a, L, P.cnt, P.mn);
         a.child_mean_q[rid] = mean;
@@ -575,21 +135,18 @@ __global__ void __launch_bounds__(256) FLX_FOLD_OCC k_kmer_fold(const FoldArgs a
         a.child_passed[rid] = cutoffs(a.p, L, mean, window);
         return;
     }
-    if (MODE != 0) {
+    if (M.events != kEvNone) {
         int end = L;
-        if (zs >= 0) {  // the read ends inside a zero run [zs, L)
-            const bool bad = (split_set && L - zs >= split) || (trim && zs > 0);
-            if (bad) {
-                any_bad = true;
-                end = zs;
-                C = S;
-            }
+        if (K.zs >= 0 && rule.bad_run_at_end(K.zs, L)) {  // the read ends inside a bad zero run [zs, L)
+            K.any_bad = true;
+            end = K.zs;
+            K.C = K.S;
         }
-        if (any_bad) emit_child(cs, end, C);
-        else nchild = 0;
+        if (K.any_bad) emit_child<M.out>(a, rid, cbase, K.n, K.cs, end, K.C);
+        else K.n = 0;
     }
-    if (MODE == 1 || MODE == 3) a.n_child[rid] = nchild;
-    if (MODE != 2 && MODE != 4 && MODE != 5) {
+    if (M.out & kOutCount) a.n_child[rid] = K.n;
+    if (M.out & kOutRead) {
         const double mean = 100.0 * (double)a.count[rid] / (double)L;  // exact: the qualities are 0.0 / 1.0
         const double window = window_result(a, L, P.cnt, P.mn);
         a.mean_q[rid] = mean;
@@ -682,7 +239,7 @@ static int launch_fold(flx_ctx *ctx, FoldArgs &a) {
     if (grid) {
         constexpr int M = (MODE == 0 || MODE == 3 || MODE == 6) ? MODE : 0;
         ctx->last_kmer_fold_grid = true;
-        const size_t lds = (size_t)(threads / 64) * (size_t)R * 256 + 2048 * FLX_FOLD_WALK_COPIES + 1024;
+        const size_t lds = (size_t)(threads / 64) * (size_t)R * 256 + kGridLdsWords * 4;
         FLX_HIP(ctx, hipFuncSetAttribute((const void *)k_kmer_fold<M, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         flx_time_scope tf(ctx, kFoldTimingNames[MODE][path][1]);
         hipLaunchKernelGGL((k_kmer_fold<M, true, true>), dim3(nb), dim3(threads), lds, ctx->stream, a);
@@ -697,6 +254,32 @@ static int launch_fold(flx_ctx *ctx, FoldArgs &a) {
     }
     FLX_HIP(ctx, hipGetLastError());  // (a launch that fails must not pass for a kernel that wrote nothing)
     return FLX_OK;
+}
+
+// How a call folds, decided once from the parameters and the environment.  The switches select second implementations that the
+// tests hold against the default ones; an unknown value of FLX_KMER_FOLD is a variant like the others (no inline ranges, no
+// cooperative path) that then takes the default launches.
+struct FoldPlan {
+    bool bit_level;        // zero runs per bit (MODE 1 + 2): --split < 32, where a run inside one word can be a bad range, or FLX_KMER_FOLD=bits
+    bool per_child;        // one lane per child (MODE 3, 5, 6); else FLX_KMER_FOLD=words: the children inside their read's lane (MODE 3 + 4)
+    bool inline_children;  // MODE 3 leaves every read's first ranges beside it (FoldArgs::inline_ranges)
+    bool grid;             // the steady state on the integer grid; FLX_KMER_FOLD_GRID=0 and windows whose table does not pay: in floating point
+    bool events;           // FLX_KMER_FOLD_EVENTS=1
+    // The cooperative path for ultra-long reads and children (score_kmer_long.hip) applies where the one-lane kernels would fold on
+    // the integer grid: a window size whose grid table pays, none of the test-only fold variants, --split absent or >= 32.
+    bool cooperative;
+};
+static FoldPlan fold_plan(const flx_params *params, bool want_children, bool grid_pays) {
+    const char *fold_env = getenv("FLX_KMER_FOLD"), *ev_env = getenv("FLX_KMER_FOLD_EVENTS"), *grid_env = getenv("FLX_KMER_FOLD_GRID");
+    const bool short_split = params->split_set && params->split < 32;
+    FoldPlan p;
+    p.bit_level = short_split || (fold_env && strcmp(fold_env, "bits") == 0);
+    p.per_child = !p.bit_level && !(fold_env && strcmp(fold_env, "words") == 0);
+    p.inline_children = want_children && !short_split && !fold_env;
+    p.grid = grid_pays && !(grid_env && grid_env[0] == '0');
+    p.events = ev_env && ev_env[0] == '1';
+    p.cooperative = p.grid && !p.events && !fold_env && !short_split;
+    return p;
 }
 
 int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_plane, uint64_t plane_bytes,
@@ -718,27 +301,16 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
     // batch once they have reached their size.
     const size_t scan_ws = flx_radix_sort_workspace(n_reads + 1);
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const char *fold_env0 = getenv("FLX_KMER_FOLD");
-    const bool inline_children = want_children && !(params->split_set && params->split < 32) && !fold_env0;  // (the one-lane-per-child path)
-    // The cooperative path for ultra-long reads and children (score_kmer_long.hip) applies where the one-lane kernels would fold on
-    // the integer grid: a window size whose grid table pays, none of the test-only fold variants, --split absent or >= 32.
     GridTab gt;
-    const bool grid_pays = build_grid_table(params->window_size, gt);
-    bool grid_on, events_on;
-    {
-        const char *ev_env = getenv("FLX_KMER_FOLD_EVENTS");
-        events_on = ev_env && ev_env[0] == '1';
-        const char *grid_env = getenv("FLX_KMER_FOLD_GRID");  // "0": the floating-point steady state (the second implementation; tests, A/B)
-        grid_on = grid_pays && !(grid_env && grid_env[0] == '0');
-    }
+    const FoldPlan plan = fold_plan(params, want_children, build_grid_table(params->window_size, gt));
     KmerLong kl;
-    FLX_CHECK(flx_kmer_long_threshold(ctx, plane_bytes, grid_on && !events_on && !fold_env0 && !(params->split_set && params->split < 32), &kl));
+    FLX_CHECK(flx_kmer_long_threshold(ctx, plane_bytes, plan.cooperative, &kl));
     // The cooperative path of the coverage stage (cover_long.hip): long reads are covered as segments, one wave each, by the
     // wave-level kernels — whatever the window size, --split and the fold variant; the workgroup-per-read form keeps them in its own launch
     CoverLong cvl;
     FLX_CHECK(flx_cover_long_threshold(ctx, plane_bytes, !flx_kmer_cover_is_v2(set), &cvl));
     const size_t small_bytes = 2 * up((n_reads + 1) * 8) + 3 * up(n_reads * 4) + up((n_reads + 1) * 4) + up(scan_ws) + up(n_reads) +
-                               (inline_children ? up(n_reads * (size_t)kInlineChildren * 8) + up(64) : 0) + up(64);
+                               (plan.inline_children ? up(n_reads * (size_t)kInlineChildren * 8) + up(64) : 0) + up(64);
     void *small = nullptr;
     FLX_CHECK(flx_workspace(ctx, 0, small_bytes, &small));
     char *wp = (char *)small;
@@ -751,8 +323,8 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
     uint32_t *d_nchild = (uint32_t *)carve((n_reads + 1) * 4);
     void *d_scanws = carve(scan_ws);
     uint8_t *d_redo = (uint8_t *)carve(n_reads);  // cover_queue.hip: marks of the reads handed to the kernel with a diagonal per lane
-    int32_t *d_inline = inline_children ? (int32_t *)carve(n_reads * (size_t)kInlineChildren * 8) : nullptr;
-    unsigned int *d_overflow = inline_children ? (unsigned int *)carve(64) : nullptr;
+    int32_t *d_inline = plan.inline_children ? (int32_t *)carve(n_reads * (size_t)kInlineChildren * 8) : nullptr;
+    unsigned int *d_overflow = plan.inline_children ? (unsigned int *)carve(64) : nullptr;
     int32_t *first = out->first ? out->first : d_first_tmp, *last = out->last ? out->last : d_last_tmp;
     // the counters of the cooperative paths, 64 bytes: the long reads' and (at + 1) the long children's counts for the folds, then
     // the coverage stage's long reads and segments — zeroed by one memset, read back by one copy with the wait below
@@ -791,7 +363,7 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
                                    d_redo, cvl, &d_counters->cover, d_cover_long, cover_long_room));
 
     // ---- stage 2: serial fold ----
-    FoldArgs a;
+    FoldArgs a;  // (what a launch does not use stays null / 0: the struct's defaults)
     a.cov = (uint32_t *)d_cov;
     a.cov_off = (const uint64_t *)d_covoff;
     a.lengths = d_lengths;
@@ -809,19 +381,14 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
     }
     a.p = *params;
     a.gt = gt;
-    a.events = events_on;
-    a.grid = grid_on;
+    a.events = plan.events;
+    a.grid = plan.grid;
     a.long_min = kl.on ? kl.thr : 0;
     ctx->last_kmer_fold_grid = false;  // (launch_fold says so when a grid kernel really runs)
     a.mean_q = out->mean_q;
     a.window_q = out->window_q;
     a.passed = out->passed;
-    a.n_child = nullptr;
     a.inline_ranges = d_inline;
-    a.child_parent = nullptr;
-    a.child_order = nullptr;
-    a.n_children = 0;
-    a.child_offsets = nullptr;
     a.child_ranges = out->child_ranges;
     a.child_mean_q = out->child_mean_q;
     a.child_window_q = out->child_window_q;
@@ -840,10 +407,7 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
 
     FLX_HIP(ctx, hipMemsetAsync(d_nchild, 0, (n_reads + 1) * 4, st));
     a.n_child = d_nchild;
-    // FLX_KMER_FOLD=bits forces the bit-level passes (tests compare the two implementations on every read)
-    const char *fold_env = getenv("FLX_KMER_FOLD");
-    const bool bit_level = (params->split_set && params->split < 32) || (fold_env && strcmp(fold_env, "bits") == 0);
-    if (bit_level)
+    if (plan.bit_level)
         FLX_CHECK(launch_fold<1>(ctx, a));  // runs inside one word can be bad ranges
     else
         FLX_CHECK(launch_fold<3>(ctx, a));
@@ -863,11 +427,9 @@ int flx_score_kmer_dev(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *d_pl
                         (long long)total_children, (unsigned long long)out->child_capacity);
     if (total_children > 0) {
         a.child_offsets = out->child_offsets;
-        // FLX_KMER_FOLD=words: the children inside their read's lane (MODE 4, second implementation of the word-level path)
-        const bool per_child = !bit_level && !(fold_env && strcmp(fold_env, "words") == 0);
-        if (bit_level) {
+        if (plan.bit_level) {
             FLX_CHECK(launch_fold<2>(ctx, a));
-        } else if (!per_child) {
+        } else if (!plan.per_child) {
             FLX_CHECK(launch_fold<4>(ctx, a));
         } else {
             // ranges (word-level events only) -> children by descending length -> one lane per child

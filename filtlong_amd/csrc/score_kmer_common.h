@@ -33,14 +33,14 @@ struct FoldArgs {
     // MODE 3 leaves the first kInlineChildren ranges of every read here ([n_reads][kInlineChildren][2], or NULL): they are moved to
     // their places in the CSR once the counts have been scanned, and the ranges pass (MODE 5) only runs for a batch in which some
     // read has more (round 5: MODE 5 walked every row again for ~1 child per read — 7.7 of C4's 33 ms of folds)
-    int32_t *inline_ranges;
+    int32_t *inline_ranges = nullptr;
     // MODE 5 / 6: one lane per child
-    uint32_t *child_parent;         // [n_children] read index of every child (written by MODE 5, read by MODE 6)
-    const uint32_t *child_order;    // [n_children] children by descending length (MODE 6)
-    uint64_t n_children;
+    uint32_t *child_parent = nullptr;         // [n_children] read index of every child (written by MODE 5, read by MODE 6)
+    const uint32_t *child_order = nullptr;    // [n_children] children by descending length (MODE 6)
+    uint64_t n_children = 0;
     // children
-    uint32_t *n_child;              // [n] (count pass)
-    const uint64_t *child_offsets;  // [n+1] (emit pass)
+    uint32_t *n_child = nullptr;              // [n] (count pass)
+    const uint64_t *child_offsets = nullptr;  // [n+1] (emit pass)
     int32_t *child_ranges;
     double *child_mean_q;
     double *child_window_q;

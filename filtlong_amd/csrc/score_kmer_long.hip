@@ -17,7 +17,7 @@
 //      the count (before the offsets' scan), once to write child_ranges / child_parent in order (after it).  Children of at least the
 //      threshold are segments of their own and go through 1. and 2.; the shorter ones stay with MODE 6.
 // tools/sim_fold_long.cpp is the walk of 2. on the host against the plain recurrence, bit for bit.
-#include "score_kmer_common.h"
+#include "fold_common.h"
 
 #include <cerrno>
 #include <chrono>
@@ -167,41 +167,20 @@ __global__ void __launch_bounds__(64) k_kmer_long_walk(const LongArgs g) {
     if (len > ws) {
         w = (double)c0 / g.a.ws_d;  // src/read.cpp:221-226
         mn = w;
-        // the regime (all wave-uniform): w = wb + c * ds while g_lo <= c <= g_hi; lmin = lowest c this LANE's words reached
-        double wb = w, ds = 0.0;
-        int c = 0, g_lo = 0x7fffffff, g_hi = (int)0x80000000, lmin = 0x7fffffff;
-        auto begin = [&]() {  // k_kmer_fold: grid_begin — the same arithmetic
-            wb = w;
-            ds = 0.0;
+        // the regime (all wave-uniform): w = r.wb + c * r.ds while r.lo <= c <= r.hi; lmin = lowest c this LANE's words reached
+        GridRegime r;
+        int c = 0, lmin = 0x7fffffff;
+        auto begin = [&]() {  // fold_grid_tab.h: the table's entry of w's binade from LDS
+            const int idx = grid_binade(w) - g.a.gt.e0;
+            const bool has = w > 0.0 && idx >= 0 && idx < g.a.gt.n;
+            r = grid_regime_begin(w, has ? sh_ds[idx] : 0.0, has ? sh_lv[idx] : 0.0, has ? sh_top[idx] : 0, g.a.ws_d);
             c = 0;
             lmin = 0x7fffffff;
-            g_lo = 0x7fffffff;
-            g_hi = (int)0x80000000;
-            const int eb = (__double2hiint(w) >> 20) & 0x7ff;
-            const int idx = eb - g.a.gt.e0;
-            if (w > 0.0 && idx >= 0 && idx < g.a.gt.n) {
-                const double d2 = sh_ds[idx], lv = sh_lv[idx];
-                if (d2 > 0.0) {
-                    const uint32_t m_lo = (uint32_t)__double2loint(w), m_hi = ((uint32_t)__double2hiint(w) & 0xfffffu) | 0x100000u;
-                    const int z = m_lo ? __ffs((int)m_lo) - 1 : 32 + (__ffs((int)m_hi) - 1);
-                    const int gb = min(eb + z, sh_top[idx]);
-                    const double uv = __hiloint2double((gb + 1) << 20, 0);
-                    int k0 = (int)floor((lv - w) * g.a.ws_d);
-                    if (fma((double)k0, d2, w) <= lv) ++k0;
-                    if (fma((double)k0, d2, w) <= lv) ++k0;
-                    int k1 = (int)ceil((uv - w) * g.a.ws_d);
-                    if (fma((double)k1, d2, w) >= uv) --k1;
-                    if (fma((double)k1, d2, w) >= uv) --k1;
-                    ds = d2;
-                    g_lo = k0;
-                    g_hi = k1;
-                }
-            }
         };
-        auto flush = [&]() {  // the regime's state as the recurrence's: exact (k_kmer_fold: grid_flush)
+        auto flush = [&]() {  // the regime's state as the recurrence's: exact
             const int cmin = wave_min(lmin);
-            if (cmin != 0x7fffffff) mn = fmin(mn, fma((double)cmin, ds, wb));
-            w = fma((double)c, ds, wb);
+            if (cmin != 0x7fffffff) mn = fmin(mn, grid_value(r, cmin));
+            w = grid_value(r, c);
         };
         begin();
         const int nw = (int)flx_kmer_long_words(len, ws);
@@ -227,7 +206,7 @@ __global__ void __launch_bounds__(64) k_kmer_long_walk(const LongArgs g) {
             int from = 0, pre_from = 0;
             for (;;) {
                 const int ci = c + (pre - pre_from);
-                const bool ok = !(sv & kNonZero) || (!(sv & kPartial) && ci + mp >= g_lo && ci + xp <= g_hi);
+                const bool ok = !(sv & kNonZero) || (!(sv & kPartial) && ci + mp >= r.lo && ci + xp <= r.hi);
                 const unsigned long long failed = __ballot(lane >= from && !ok);
                 const int fail = failed ? __ffsll(failed) - 1 : 64;
                 if (lane >= from && lane < fail) lmin = min(lmin, ci + mp);
@@ -237,19 +216,9 @@ __global__ void __launch_bounds__(64) k_kmer_long_walk(const LongArgs g) {
                 }
                 c += uniform_lane(pre, fail) - pre_from;
                 flush();
-                // that word by the reference's own steps (k_kmer_fold: the same 32 fma pairs)
+                // that word by the reference's own steps
                 const uint32_t rl = (uint32_t)uniform_lane((int)lead, fail), rt = (uint32_t)uniform_lane((int)trail, fail);
-#pragma unroll 1
-                for (int i0 = 0; i0 < 32; i0 += 8) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const double lb = (double)__builtin_amdgcn_ubfe(rl, i0 + i, 1);
-                        const double tb = (double)__builtin_amdgcn_ubfe(rt, i0 + i, 1);
-                        w = fma(tb, -delta, w);
-                        w = fma(lb, delta, w);
-                        mn = fmin(mn, w);
-                    }
-                }
+                fold_word_fp<true>(w, mn, rl, rt, delta);
                 ++replays;
                 begin();
                 pre_from = uniform_lane(incl, fail);
@@ -292,8 +261,8 @@ __global__ void __launch_bounds__(64) k_kmer_long_children(const LongArgs g, Kme
     const int L = g.a.lengths[rid];
     const uint32_t *row = g.a.cov + (g.a.cov_off[rid] >> 2);
     const int nw = (L + 31) >> 5;
-    const bool split_set = g.a.p.split_set != 0, trim = g.a.p.trim != 0;
-    const int split = g.a.p.split, thr = g.a.long_min, ws = g.a.ws;
+    const ZeroRunRule rule(g.a.p);
+    const int thr = g.a.long_min, ws = g.a.ws;
     const uint64_t cbase = EMIT ? g.a.child_offsets[rid] : 0;
     const unsigned long long below = (1ull << lane) - 1ull;
     // wave-uniform: one past the last covered base so far (0: none yet), start of the current child candidate, children so far
@@ -332,7 +301,7 @@ __global__ void __launch_bounds__(64) k_kmer_long_children(const LongArgs g, Kme
         const int p = nz_below ? 63 - __clzll((long long)nz_below) : -1;
         const int tp_left = __shfl(tp, p < 0 ? 0 : p, 64);
         const int zs = p >= 0 ? tp_left : prev_tp;  // the zero run [zs, f) ends at this word's first covered base
-        const bool bad = wd != 0u && f > zs && ((split_set && f - zs >= split) || (trim && zs == 0));
+        const bool bad = wd != 0u && f > zs && rule.bad_run(zs, f);
         const unsigned long long badm = __ballot(bad);
         if (badm) {
             const unsigned long long bad_below = badm & below;
@@ -349,11 +318,9 @@ __global__ void __launch_bounds__(64) k_kmer_long_children(const LongArgs g, Kme
         prev_tp = __shfl(tp, 63 - __clzll((long long)nzm), 64);
     }
     int end = L;
-    if (prev_tp < L) {  // the read ends inside the zero run [prev_tp, L)
-        if ((split_set && L - prev_tp >= split) || (trim && prev_tp > 0)) {
-            any_bad = true;
-            end = prev_tp;
-        }
+    if (prev_tp < L && rule.bad_run_at_end(prev_tp, L)) {  // the read ends inside the bad zero run [prev_tp, L)
+        any_bad = true;
+        end = prev_tp;
     }
     if (any_bad && end > cs) {
         if (lane == 0) child(nchild, cs, end);

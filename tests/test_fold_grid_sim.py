@@ -1,5 +1,6 @@
-"""The integer-grid window fold (filtlong_amd/csrc/score_kmer.hip: GridTab, k_kmer_fold<.., GRID>) restated on the host —
-tools/sim_fold_grid.cpp, the same regime logic the kernel runs — against the plain floating-point recurrence of the reference
+"""The integer-grid window fold (k_kmer_fold<.., GRID>) on the host — tools/sim_fold_grid.cpp: the grid table and the start of a
+regime are the kernels' own functions (filtlong_amd/csrc/fold_grid_tab.h: build_grid_table, grid_regime_begin), compiled by g++; the
+walk over the words is restated — against the plain floating-point recurrence of the reference
 (src/read.cpp:216-236 with qualities 0.0 / 1.0), bit for bit.  No GPU: this is the exhaustion argument behind the kernel (DESIGN.md
 §4.3); the kernel itself is held against the oracle and against the floating-point kernel in tests/test_gpu_kmer.py and
 tests/test_gpu_fullsize.py."""

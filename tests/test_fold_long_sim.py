@@ -1,5 +1,5 @@
 """The cooperative window fold of ultra-long reads in k-mer mode (filtlong_amd/csrc/score_kmer_long.hip) restated on the host —
-tools/sim_fold_long.cpp: word summaries, 64 at a time, the first word that leaves the regime replayed in floating point, the rest
+tools/sim_fold_long.cpp, with the kernel's own grid table and start of a regime (filtlong_amd/csrc/fold_grid_tab.h): word summaries, 64 at a time, the first word that leaves the regime replayed in floating point, the rest
 tested again — against the plain recurrence of the reference (src/read.cpp:216-236 with qualities 0.0 / 1.0), bit for bit in w and
 mn.  Random and engineered bit streams (the clean / junk periods of tests/test_gpu_kmer.py::test_integer_grid_folds_vs_oracle,
 all-zero and all-one streams, lengths ws-1 .. ws+1, 1023 .. 1025, 2047 .. 2049), as a read of its own and as a child at a bit offset

@@ -1,4 +1,5 @@
-// sim_fold_grid.cpp — the integer-grid window fold, on the host, before it was built for the GPU.
+// sim_fold_grid.cpp — the integer-grid window fold, on the host: the grid table and the start of a regime are the
+// kernels' own code (filtlong_amd/csrc/fold_grid_tab.h), the walk over the words is restated here.
 //
 // Reference semantics: src/read.cpp:216-236 with qualities 0.0 / 1.0:  w0 = cnt / ws;  per step  w -= q[j-ws]/ws; w += q[j]/ws;
 // mn = min(mn, w).  Claim: while w stays inside a GROUP of binades in which fl(1/ws) rounds to the same real number d* on every
@@ -16,92 +17,14 @@
 #include <random>
 #include <vector>
 
-struct Binade { double dstar; bool tie; int group; };  // per unbiased exponent E of w: the step on that binade's grid
-struct Table {
-    int e_min, e_max;  // exponents covered: e_min .. e_max
-    std::vector<Binade> b;
-    std::vector<int> glo, ghi;  // per group: lowest / highest exponent
-    double delta;
-};
+#include "../filtlong_amd/csrc/fold_grid_tab.h"
 
-static Table make_table(int ws) {
-    Table t;
-    volatile double one = 1.0, wsd = (double)ws;
-    t.delta = one / wsd;
-    uint64_t bits;
-    memcpy(&bits, &t.delta, 8);
-    const int e_d = (int)((bits >> 52) & 0x7ff) - 1023;
-    const uint64_t M = (bits & ((1ull << 52) - 1)) | (1ull << 52);  // delta = M * 2^(e_d - 52)
-    t.e_min = e_d - 2;
-    t.e_max = 1;
-    for (int E = t.e_min; E <= t.e_max; ++E) {
-        Binade x;
-        const int shift = E - e_d;  // grid of binade E = 2^(E-52) = 2^shift units of delta's ulp
-        x.tie = false;
-        if (shift <= 0) x.dstar = t.delta;
-        else if (shift >= 53) { x.dstar = 0; x.tie = true; }  // (not reached: w <= 2)
-        else {
-            const uint64_t rem = M & ((1ull << shift) - 1), half = 1ull << (shift - 1);
-            x.tie = rem == half;
-            const uint64_t q = (M >> shift) + (rem > half ? 1 : 0);
-            x.dstar = ldexp((double)q, shift + e_d - 52);  // q < 2^54: exact
-        }
-        x.group = -1;
-        t.b.push_back(x);
-    }
-    for (size_t i = 0; i < t.b.size(); ++i) {
-        if (t.b[i].tie) continue;
-        if (i > 0 && !t.b[i - 1].tie && t.b[i - 1].dstar == t.b[i].dstar) { t.b[i].group = t.b[i - 1].group; t.ghi[t.b[i].group] = t.e_min + (int)i; }
-        else { t.b[i].group = (int)t.glo.size(); t.glo.push_back(t.e_min + (int)i); t.ghi.push_back(t.e_min + (int)i); }
-    }
-    return t;
-}
-
-// what the kernel does when a regime begins (score_kmer.hip: begin_regime) — same arithmetic, same corrections
-struct Regime { bool valid; double wb, dstar; long lo_c, hi_c; };
+// The table (build_grid_table) and the start of a regime (grid_regime_begin) are the kernels' own: fold_grid_tab.h.  A window size
+// without a table (ws < 8) has no regime anywhere and folds in plain floating point, as the kernel does.
 static long g_reason[4];  // slow words by reason: 0 no regime, 1 below, 2 above
 static int g_nibble = 0;    // 1: a slow word is replayed from its first nibble that leaves the regime (costed in round 6, NOT built: below); 0: whole, what the kernel does
 static long g_fp_steps = 0; // positions replayed in floating point
-static int g_ctz_rule = 1;  // the top of a regime: the highest binade on whose grid w_b already lies (0: the binade w_b is in)
-static Regime begin_regime(const Table &t, double w, int ws) {
-    Regime r{false, w, 0, 1, -1};
-    if (!(w > 0)) return r;
-    int E;
-    frexp(w, &E);
-    E -= 1;  // w in [2^E, 2^(E+1))
-    if (E < t.e_min || E > t.e_max) return r;
-    const Binade &b = t.b[(size_t)(E - t.e_min)];
-    if (b.group < 0) return r;
-    // the bottom of the group, and never closer to 0 than 4 delta: a (1,1) step dips by delta and must stay within ONE binade of w
-    // the top: w must not reach a binade on whose grid w_b does NOT lie (there its low bits would be rounded away).  w_b lies on the
-    // grid of binade E + z, z = trailing zero bits of its mantissa (a window that has been full, w = 1.0, stays on the grid of [1, 2)
-    // whatever is subtracted: d* is a multiple of that grid) — up to the top of the group
-    int G = E;
-    if (g_ctz_rule) {
-        uint64_t bits;
-        memcpy(&bits, &w, 8);
-        const uint64_t m = (bits & ((1ull << 52) - 1)) | (1ull << 52);
-        G = std::min(E + (int)__builtin_ctzll(m), t.ghi[(size_t)b.group]);
-    }
-    const double Lv = std::max(ldexp(1.0, t.glo[(size_t)b.group]), 4.0 * t.delta), Uv = ldexp(1.0, G + 1);
-    const double ds = b.dstar, wsd = (double)ws;
-    // smallest k with w + k d* > Lv: the estimate (Lv - w) * ws is within 1e-9 of (Lv - w) / d*, so its floor is the answer or
-    // one or two below it; the values themselves decide (w + k d* is exact: a multiple of w's grid)
-    // (strictly above Lv: a step that lands exactly ON the bottom of the group's lowest binade has its true value, w - delta, a
-    // hair below it when delta > d* — in the binade underneath, which rounds on its own, finer grid)
-    long k0 = (long)floor((Lv - w) * wsd);
-    if (fma((double)k0, ds, w) <= Lv) ++k0;
-    if (fma((double)k0, ds, w) <= Lv) ++k0;
-    // largest k with w + k d* < Uv: the ceiling of the estimate is the answer or one or two above it
-    long k1 = (long)ceil((Uv - w) * wsd);
-    if (fma((double)k1, ds, w) >= Uv) --k1;
-    if (fma((double)k1, ds, w) >= Uv) --k1;
-    r.valid = true;
-    r.dstar = ds;
-    r.lo_c = k0;
-    r.hi_c = k1;
-    return r;
-}
+static int g_ctz_rule = 1;  // the top of a regime: the highest binade on whose grid w_b already lies (0: the binade w_b is in, passed as `top`)
 
 struct Fold { double w, mn; };
 // plain FP fold of positions [ws, L) given bits
@@ -121,7 +44,7 @@ static Fold fold_fp(const std::vector<uint8_t> &q, int ws) {
 }
 
 // regime fold; `slow` gets the word indices that took the FP path
-static Fold fold_grid(const std::vector<uint8_t> &q, int ws, const Table &t, std::vector<int> *slow) {
+static Fold fold_grid(const std::vector<uint8_t> &q, int ws, const GridTab &t, std::vector<int> *slow) {
     const int L = (int)q.size();
     volatile double one = 1.0, wsd = (double)ws;
     const double d = one / wsd;
@@ -135,12 +58,12 @@ static Fold fold_grid(const std::vector<uint8_t> &q, int ws, const Table &t, std
         w += q[j] ? d : 0.0;
         if (w < mn) mn = w;
     }
-    Regime r = begin_regime(t, w, ws);
-    long c = 0, cmin = 0;
+    GridRegime r = grid_regime_begin(t, w, (double)ws, !g_ctz_rule);
+    int c = 0, cmin = 0;
     auto flush = [&]() {
-        if (r.valid) {
-            const double wn = fma((double)c, r.dstar, r.wb);
-            const double m2 = fma((double)cmin, r.dstar, r.wb);
+        if (r.ds > 0.0) {
+            const double wn = grid_value(r, c);
+            const double m2 = grid_value(r, cmin);
             if (m2 < mn) mn = m2;
             w = wn;
         }
@@ -156,7 +79,7 @@ static Fold fold_grid(const std::vector<uint8_t> &q, int ws, const Table &t, std
             xp = std::max(xp, tt);
         }
         if (!any) continue;  // (0,0) steps change nothing in any regime
-        if (r.valid && c + mp >= r.lo_c && c + xp <= r.hi_c) {
+        if (r.ds > 0.0 && c + mp >= r.lo && c + xp <= r.hi) {
             cmin = std::min(cmin, c + mp);
             c += tt;
             continue;
@@ -167,7 +90,7 @@ static Fold fold_grid(const std::vector<uint8_t> &q, int ws, const Table &t, std
         // C3-like reads (half the slow words have no regime at all — w in the tie binade or at 0 — and start at position 0), and finding the
         // nibble costs the kernel a second walk through the table: a loss.
         int first = 0;  // first position replayed in floating point
-        if (g_nibble && r.valid) {
+        if (g_nibble && r.ds > 0.0) {
             int pre = 0, lo = 0, hi = 0;  // the walk through the nibbles that stay inside
             for (int k = 0; k < 8; ++k) {
                 int p2 = pre, lo2 = lo, hi2 = hi;
@@ -176,7 +99,7 @@ static Fold fold_grid(const std::vector<uint8_t> &q, int ws, const Table &t, std
                     lo2 = std::min(lo2, p2);
                     hi2 = std::max(hi2, p2);
                 }
-                if (!(c + lo2 >= r.lo_c && c + hi2 <= r.hi_c)) break;
+                if (!(c + lo2 >= r.lo && c + hi2 <= r.hi)) break;
                 pre = p2; lo = lo2; hi = hi2;
                 first = 4 * k + 4;
             }
@@ -186,18 +109,17 @@ static Fold fold_grid(const std::vector<uint8_t> &q, int ws, const Table &t, std
         g_fp_steps += 32 - first;
         flush();
         if (slow) slow->push_back(j >> 5);
-        ++g_reason[!r.valid ? 0 : (c + mp < r.lo_c ? 1 : 2)];
+        ++g_reason[!(r.ds > 0.0) ? 0 : (c + mp < r.lo ? 1 : 2)];
         for (int i = first; i < 32; ++i) {
             w -= q[j + i - ws] ? d : 0.0;
             w += q[j + i] ? d : 0.0;
             if (w < mn) mn = w;
         }
-        r = begin_regime(t, w, ws);
+        r = grid_regime_begin(t, w, (double)ws, !g_ctz_rule);
         c = 0;
         cmin = 0;
     }
     flush();
-    r.valid = false;
     for (; j < L; ++j) {
         w -= q[j - ws] ? d : 0.0;
         w += q[j] ? d : 0.0;
@@ -228,7 +150,8 @@ int main(int argc, char **argv) {
     const int n_ws = argc > 1 ? atoi(argv[1]) : 400;
     for (int k = 0; k < n_ws; ++k) {
         const int ws = k < 40 ? (int[]){250, 100, 1, 2, 3, 5, 7, 16, 32, 33, 64, 127, 128, 129, 255, 256, 257, 500, 512, 1000, 1024, 2047, 2048, 4096, 9999, 10000, 31, 63, 65, 96, 97, 200, 300, 333, 400, 600, 750, 800, 900, 1500}[k] : 1 + (int)(g() % 3000);
-        const Table t = make_table(ws);
+        GridTab t;
+        build_grid_table(ws, t);
         for (int rep = 0; rep < 30; ++rep) {
             const int L = ws + 64 + (int)(g() % 20000);
             std::vector<uint8_t> q((size_t)L);
@@ -254,11 +177,13 @@ int main(int argc, char **argv) {
     printf("exactness: %ld cases, %ld mismatches\n", cases, bad);
     // the groups of the default window
     for (int ws : {250, 100, 1000, 500}) {
-        const Table t = make_table(ws);
-        printf("ws %d: groups", ws);
-        for (size_t i = 0; i < t.glo.size(); ++i) printf(" [2^%d, 2^%d)", t.glo[i], t.ghi[i] + 1);
+        GridTab t;
+        build_grid_table(ws, t);
+        printf("ws %d: groups", ws);  // a group begins behind a tie (d* = 0) or where top[] changes, and reaches up to its top[]
+        for (int i = 0; i < t.n; ++i)
+            if (t.dstar[i] != 0.0 && (i == 0 || t.dstar[i - 1] == 0.0 || t.top[i - 1] != t.top[i])) printf(" [2^%d, 2^%d)", t.e0 - 1023 + i, t.top[i] - 1023 + 1);
         printf("   ties at:");
-        for (size_t i = 0; i < t.b.size(); ++i) if (t.b[i].tie) printf(" 2^%d", t.e_min + (int)i);
+        for (int i = 0; i < t.n; ++i) if (t.dstar[i] == 0.0) printf(" 2^%d", t.e0 - 1023 + i);
         printf("\n");
     }
     g_reason[0] = g_reason[1] = g_reason[2] = 0;
@@ -269,7 +194,8 @@ int main(int argc, char **argv) {
     for (int ws : {250, 100, 500}) {
         g_ctz_rule = rule;
         printf("top of a regime %s: ", rule ? "by the grid w_b lies on" : "the binade w_b is in");
-        const Table t = make_table(ws);
+        GridTab t;
+        build_grid_table(ws, t);
         const int n = 64 * 60;
         std::vector<int> len((size_t)n);
         std::gamma_distribution<double> gd(4.0, 2500.0);

@@ -7,8 +7,8 @@
 //     highest prefix of the +-1 walk, a flag for "not all zero", a flag for the partial last word);
 //   * the head is (double)popcount(first ws bits) / ws;
 //   * 64 summaries at a time: prefix of the totals, every word tested against the regime's bounds (same grid table and the same
-//     begin-of-regime arithmetic as the one-lane kernel: filtlong_amd/csrc/fold_grid_tab.h), the first failing word replayed by the
-//     32 fma pairs, a new regime, the rest of the 64 tested again without recomputing them.
+//     begin of a regime as both kernels — their own code: filtlong_amd/csrc/fold_grid_tab.h), the first failing word replayed in
+//     floating point (the 32 fma pairs), a new regime, the rest of the 64 tested again without recomputing them.
 // Reference semantics: src/read.cpp:216-236 with qualities 0.0 / 1.0.
 //
 // usage: sim_fold_long [random streams per window size]     (exit status 1 on a mismatch)
@@ -106,35 +106,17 @@ static Fold fold_long(const Seg &s, int ws, const GridTab &gt) {
         c0 += __builtin_popcount(v);
     }
     double w = (double)c0 / ws_d, mn = w;
-    // the regime
-    double wb = w, ds = 0.0;
-    int c = 0, g_lo = 0x7fffffff, g_hi = (int)0x80000000, cmin = 0x7fffffff;
+    // the regime (fold_grid_tab.h: the kernel's own start of a regime, the table held as GridTab)
+    GridRegime r;
+    int c = 0, cmin = 0x7fffffff;
     auto begin = [&]() {
-        wb = w; ds = 0.0; c = 0; cmin = 0x7fffffff; g_lo = 0x7fffffff; g_hi = (int)0x80000000;
-        uint64_t bits;
-        memcpy(&bits, &w, 8);
-        const int eb = (int)((bits >> 52) & 0x7ff);
-        const int idx = eb - gt.e0;
-        if (w > 0.0 && idx >= 0 && idx < gt.n) {
-            const double d2 = gt.dstar[idx], lv = gt.lv[idx];
-            if (d2 > 0.0) {
-                const uint64_t m = (bits & ((1ull << 52) - 1)) | (1ull << 52);
-                const int z = __builtin_ctzll(m);
-                const int gb = std::min(eb + z, gt.top[idx]);
-                const double uv = ldexp(1.0, gb + 1 - 1023);
-                int k0 = (int)floor((lv - w) * ws_d);
-                if (fma((double)k0, d2, w) <= lv) ++k0;
-                if (fma((double)k0, d2, w) <= lv) ++k0;
-                int k1 = (int)ceil((uv - w) * ws_d);
-                if (fma((double)k1, d2, w) >= uv) --k1;
-                if (fma((double)k1, d2, w) >= uv) --k1;
-                ds = d2; g_lo = k0; g_hi = k1;
-            }
-        }
+        r = grid_regime_begin(gt, w, ws_d);
+        c = 0;
+        cmin = 0x7fffffff;
     };
     auto flush = [&]() {
-        if (cmin != 0x7fffffff) mn = fmin(mn, fma((double)cmin, ds, wb));
-        w = fma((double)c, ds, wb);
+        if (cmin != 0x7fffffff) mn = fmin(mn, grid_value(r, cmin));
+        w = grid_value(r, c);
     };
     begin();
     g_words += nw;
@@ -157,7 +139,7 @@ static Fold fold_long(const Seg &s, int ws, const GridTab &gt) {
             int fail = 64;
             for (int l = from; l < 64; ++l) {
                 const int ci = c + (pre[l] - pre_from);
-                const bool ok = !(sv[l] & kNonZero) || (!(sv[l] & kPartial) && ci + mp[l] >= g_lo && ci + xp[l] <= g_hi);
+                const bool ok = !(sv[l] & kNonZero) || (!(sv[l] & kPartial) && ci + mp[l] >= r.lo && ci + xp[l] <= r.hi);
                 if (!ok) { fail = l; break; }
             }
             for (int l = from; l < fail; ++l) cmin = std::min(cmin, c + (pre[l] - pre_from) + mp[l]);
@@ -165,7 +147,7 @@ static Fold fold_long(const Seg &s, int ws, const GridTab &gt) {
             c += pre[fail] - pre_from;
             flush();
             const uint32_t rl = lw[(size_t)(k0 + fail)], rt = tw[(size_t)(k0 + fail)];
-            for (int i = 0; i < 32; ++i) {
+            for (int i = 0; i < 32; ++i) {  // (fold_common.h: fold_word_fp — a device function, so its fma pairs are restated here)
                 const double lb = (double)((rl >> i) & 1u), tb = (double)((rt >> i) & 1u);
                 w = fma(tb, -delta, w);
                 w = fma(lb, delta, w);
