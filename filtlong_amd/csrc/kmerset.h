@@ -89,6 +89,40 @@ struct flx_locus {
 };
 __host__ __device__ inline uint32_t flx_locus_hash(uint32_t kmer, int shift) { return (kmer * 0x9E3779B1u) >> shift; }
 #if defined(__HIPCC__)
+// ---- device helpers of the code that builds the set and its text (kmerset.hip, pathtext.hip) ----
+// src/kmers.cpp:176-196 / 199-219: anything that is not ACGTacgt encodes as 0 on BOTH strands
+__device__ __forceinline__ uint32_t flx_base_fwd(uint8_t c) {
+    switch (c) {
+        case 'C': case 'c': return 1u;
+        case 'G': case 'g': return 2u;
+        case 'T': case 't': return 3u;
+        default: return 0u;
+    }
+}
+__device__ __forceinline__ uint32_t flx_base_rev_code(uint8_t c) {  // the 2-bit value the reverse encoder puts on top
+    switch (c) {
+        case 'G': case 'g': return 1u;
+        case 'C': case 'c': return 2u;
+        case 'A': case 'a': return 3u;
+        default: return 0u;
+    }
+}
+__device__ __forceinline__ bool flx_test_bit(const uint32_t *bm, uint32_t k) { return (bm[k >> 5] >> (k & 31)) & 1u; }
+__device__ __forceinline__ bool flx_set_bit(uint32_t *bm, uint32_t k) {  // returns the previous value
+    const uint32_t m = 1u << (k & 31);
+    return (atomicOr(&bm[k >> 5], m) & m) != 0;
+}
+// The sequence of flat position g of a batch: the largest s with pos_base[s] + stride * s <= g.  stride 0: g counts 16-mer start
+// positions (len - 15 per sequence); stride 15: g counts bases.
+__device__ __forceinline__ uint64_t flx_seq_of(const uint64_t *pos_base, uint64_t n_seqs, uint64_t g, uint64_t stride) {
+    uint64_t lo = 0, hi = n_seqs;
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (pos_base[mid] + stride * mid <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
 // the 16 codes of the text from position t on (t + 16 <= n_text is the caller's business: padding follows the data)
 __device__ __forceinline__ uint32_t flx_locus_kmer_at(const uint2 *text, uint32_t t) {
     const uint32_t w = (t >> 4) + kLocusPad, s = t & 15u;
@@ -96,13 +130,29 @@ __device__ __forceinline__ uint32_t flx_locus_kmer_at(const uint2 *text, uint32_
     if (s == 0) return a;
     return __builtin_amdgcn_alignbit(a, text[w + 1].x, 32 - 2 * s);
 }
+// no piece starts at t + 1 .. t + len - 1 and the window of `len` bases from t on ends inside the text (len <= 16)
+__device__ __forceinline__ bool flx_locus_in_piece(const uint2 *text, uint64_t n_text, uint64_t t, int len) {
+    if (t + len > n_text) return false;
+    const uint64_t t1 = t + 1;
+    const uint64_t w = (t1 >> 4) + kLocusPad;
+    const uint32_t s = (uint32_t)(t1 & 15);
+    const uint32_t b = ((text[w].y & 0xffffu) >> s) | ((text[w + 1].y & 0xffffu) << (16 - s));
+    return (b & ((1u << (len - 1)) - 1u)) == 0;
+}
 #endif
-// pathtext.hip: the same for a set without an assembly (its de Bruijn graph cut into paths)
+
+// ---- who builds it: pathtext.hip makes the text, its U13 bits and the seed table, in three forms with one finish; kmerset.hip
+// (finalize) chooses the form and adds S1 from the finished text and the exact bitmap ----
 struct flx_seq_batch {  // sequences on the device as k_add_reference indexes them (those of at least 16 bases)
     const uint8_t *bases;
-    const uint64_t *offsets, *pos_base;
+    const uint64_t *offsets, *pos_base;  // pos_base[s]: 16-mer start positions of the sequences before s
     uint64_t n_seqs, n_pos;
 };
+// All three: on success the caller owns *text_out / *seed_out (hipFree) and `loc` describes them (safe1 is the caller's); FLX_OK
+// with *text_out == nullptr when the text is too large or the device memory for it is not there (the scoring path works without).
+// the assembly form: both strands of every sequence, one after the other (at most 2^28 text positions, at least one 16-mer)
+int flx_build_assembly_text(flx_ctx *ctx, const flx_seq_batch *batches, size_t n_batches, uint32_t **text_out, uint32_t **seed_out, flx_locus *loc);
+// the path forms, for a set with short reads in it (its de Bruijn graph cut into paths): order 24, else order 16
 int flx_build_path_text(flx_ctx *ctx, const uint32_t *present, const uint8_t *exact15, uint64_t n_members, const flx_seq_batch *batches,
                         size_t n_batches, uint32_t **text_out, uint32_t **seed_out, flx_locus *loc);
 const flx_locus *flx_kmerset_locus(const flx_kmerset *set);  // NULL: no assembly, too large, or switched off at build time

@@ -40,30 +40,6 @@ __device__ __forceinline__ uint32_t bloom_index(uint32_t kmer, int i) {
     return h % (uint32_t)kBloomBits;        // compute_indices (bloom_filter.h:461-465)
 }
 
-// src/kmers.cpp:176-196 / 199-219: anything that is not ACGTacgt encodes as 0 on BOTH strands
-__device__ __forceinline__ uint32_t base_fwd(uint8_t c) {
-    switch (c) {
-        case 'C': case 'c': return 1u;
-        case 'G': case 'g': return 2u;
-        case 'T': case 't': return 3u;
-        default: return 0u;
-    }
-}
-__device__ __forceinline__ uint32_t base_rev_code(uint8_t c) {  // the 2-bit value placed in the top bits
-    switch (c) {
-        case 'G': case 'g': return 1u;
-        case 'C': case 'c': return 2u;
-        case 'A': case 'a': return 3u;
-        default: return 0u;
-    }
-}
-
-__device__ __forceinline__ bool test_bit(const uint32_t *bm, uint32_t k) { return (bm[k >> 5] >> (k & 31)) & 1u; }
-__device__ __forceinline__ bool set_bit(uint32_t *bm, uint32_t k) {  // returns the previous value
-    const uint32_t m = 1u << (k & 31);
-    return (atomicOr(&bm[k >> 5], m) & m) != 0;
-}
-
 // One thread per 16-mer START position of the packed reference sequences.  `pos_base[s]` is the number of
 // start positions of sequences before s (exclusive scan of max(len-15,0)), so the grid is flat.
 template <bool MULTI>
@@ -73,21 +49,15 @@ __global__ void __launch_bounds__(256) k_add_reference(const uint8_t *bases, con
                                                        uint32_t *seen1, uint32_t *seen2, uint32_t *seen3) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_pos) return;
-    // find the sequence: largest s with pos_base[s] <= g
-    uint64_t lo = 0, hi = n_seqs;
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (pos_base[mid] <= g) lo = mid;
-        else hi = mid;
-    }
+    const uint64_t lo = flx_seq_of(pos_base, n_seqs, g, 0);
     const uint64_t p = g - pos_base[lo];  // start position inside the sequence
     const uint8_t *s = bases + offsets[lo] + p;
     uint32_t f = 0, r = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {  // starting_kmer_to_bits_forward / _reverse, kmers.cpp:222-239
         const uint8_t c = s[i];
-        f = (f << 2) | base_fwd(c);
-        r = (r >> 2) | (base_rev_code(c) << 30);
+        f = (f << 2) | flx_base_fwd(c);
+        r = (r >> 2) | (flx_base_rev_code(c) << 30);
     }
     (void)lengths;
     const uint32_t two[2] = {f, r};
@@ -95,15 +65,15 @@ __global__ void __launch_bounds__(256) k_add_reference(const uint8_t *bases, con
     for (int q = 0; q < 2; ++q) {
         const uint32_t k = two[q];
         if (!MULTI) {
-            if (!test_bit(present, k)) set_bit(present, k);  // add_kmer_require_one_copy
+            if (!flx_test_bit(present, k)) flx_set_bit(present, k);  // add_kmer_require_one_copy
         } else {
             // add_kmer_require_multiple_copies: already in the set (assembly, or promoted) -> nothing to do;
             // otherwise raise the saturating count by one level.
-            if (test_bit(present, k)) continue;
-            if (!set_bit(seen1, k)) continue;
-            if (!set_bit(seen2, k)) continue;
-            if (!set_bit(seen3, k)) continue;
-            set_bit(present, k);
+            if (flx_test_bit(present, k)) continue;
+            if (!flx_set_bit(seen1, k)) continue;
+            if (!flx_set_bit(seen2, k)) continue;
+            if (!flx_set_bit(seen3, k)) continue;
+            flx_set_bit(present, k);
         }
     }
 }
@@ -179,7 +149,7 @@ __global__ void __launch_bounds__(256) k_bloom_fill(const uint32_t *seen1, uint6
             const uint32_t k = (uint32_t)(wi << 5) | (uint32_t)b;
             for (int i = 0; i < (int)kBloomHashes; ++i) {
                 const uint32_t idx = bloom_index(k, i);
-                if (set_bit(F1, idx)) set_bit(F2, idx);
+                if (flx_set_bit(F1, idx)) flx_set_bit(F2, idx);
             }
         }
     }
@@ -198,7 +168,7 @@ __global__ void __launch_bounds__(256) k_bloom_candidates(const uint32_t *seen1,
             w &= w - 1;
             const uint32_t k = (uint32_t)(wi << 5) | (uint32_t)b;
             bool all = true;
-            for (int i = 0; i < (int)kBloomHashes && all; ++i) all = test_bit(F2, bloom_index(k, i));
+            for (int i = 0; i < (int)kBloomHashes && all; ++i) all = flx_test_bit(F2, bloom_index(k, i));
             if (all) {
                 const unsigned int at = atomicAdd(n_cand, 1u);
                 if (at < cap) cand[at] = k;
@@ -209,14 +179,12 @@ __global__ void __launch_bounds__(256) k_bloom_candidates(const uint32_t *seen1,
 
 __global__ void __launch_bounds__(256) k_contains(const uint32_t *present, const uint32_t *kmers, uint64_t n, uint8_t *out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = test_bit(present, kmers[i]) ? 1 : 0;
+    if (i < n) out[i] = flx_test_bit(present, kmers[i]) ? 1 : 0;
 }
-
-__global__ void k_set_word_bits(uint32_t *word, uint32_t bits) { *word |= bits; }
 
 __global__ void __launch_bounds__(256) k_set_bits(uint32_t *bm, const uint32_t *kmers, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) set_bit(bm, kmers[i]);
+    if (i < n) flx_set_bit(bm, kmers[i]);
 }
 
 // First-sighting times for the exact Bloom replay (only when candidates exist).  Occurrence index of the 16-mer
@@ -241,24 +209,19 @@ __global__ void __launch_bounds__(256) k_first_sightings(const uint8_t *bases, c
                                                          unsigned long long *cand_tau, unsigned long long *bit_tau_noncand) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_pos) return;
-    uint64_t lo = 0, hi = n_seqs;
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (pos_base[mid] <= g) lo = mid;
-        else hi = mid;
-    }
+    const uint64_t lo = flx_seq_of(pos_base, n_seqs, g, 0);
     const uint8_t *s = bases + offsets[lo] + (g - pos_base[lo]);
     uint32_t f = 0, r = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const uint8_t c = s[i];
-        f = (f << 2) | base_fwd(c);
-        r = (r >> 2) | (base_rev_code(c) << 30);
+        f = (f << 2) | flx_base_fwd(c);
+        r = (r >> 2) | (flx_base_rev_code(c) << 30);
     }
     const uint32_t two[2] = {f, r};
     for (int q = 0; q < 2; ++q) {
         const uint32_t k = two[q];
-        if (test_bit(asm_present, k)) continue;  // never reaches the Bloom filter (kmers.cpp:144-145)
+        if (flx_test_bit(asm_present, k)) continue;  // never reaches the Bloom filter (kmers.cpp:144-145)
         const unsigned long long tau = tau_base + 2ull * g + (unsigned long long)q;
         const int ci = find_sorted(cand_sorted, n_cand, k);
         if (ci >= 0) {
@@ -272,73 +235,11 @@ __global__ void __launch_bounds__(256) k_first_sightings(const uint8_t *bases, c
     }
 }
 
-// ---- the assembly as a text + seed table (kmerset.h: flx_locus) ----------------------------------------------------------
-// one thread per base of the batch's sequences (those of at least 16 bases; cum[i] = bases of the sequences before i)
-__global__ void __launch_bounds__(256) k_locus_text(const uint8_t *bases, const uint64_t *offsets, const uint64_t *pos_base,
-                                                    uint64_t n_seqs, uint64_t n_pos, uint64_t text_base, uint32_t *text_words) {
-    const uint64_t n_bases = n_pos + 15 * n_seqs;
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_bases) return;
-    uint64_t lo = 0, hi = n_seqs;
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (pos_base[mid] + 15 * mid <= g) lo = mid;
-        else hi = mid;
-    }
-    const uint64_t cum = pos_base[lo] + 15 * lo;
-    const uint64_t len = (lo + 1 < n_seqs ? pos_base[lo + 1] : n_pos) - pos_base[lo] + 15;
-    const uint64_t o = g - cum;
-    const uint8_t c = bases[offsets[lo] + o];
-    const uint64_t tf = text_base + 2 * cum + o, tr = text_base + 2 * cum + len + (len - 1 - o);
-    auto put = [&](uint64_t t, uint32_t code, bool starts_copy) {
-        uint32_t *w = text_words + 2 * ((t >> 4) + kLocusPad);
-        if (code) atomicOr(w, code << (30 - 2 * (uint32_t)(t & 15)));
-        if (starts_copy) atomicOr(w + 1, 1u << (uint32_t)(t & 15));
-    };
-    put(tf, base_fwd(c), o == 0);
-    put(tr, base_rev_code(c), o == len - 1);
-}
-
-// U13 (kmerset.h), two passes over every 13-base window inside a strand copy: count its value (saturating at 2: two bitmaps of
-// 4^13 bits), then mark the windows whose value was seen once
-template <int PASS>
-__global__ void __launch_bounds__(256) k_locus_u13(const uint64_t *pos_base, uint64_t n_seqs, uint64_t n_pos, uint64_t text_base,
-                                                   uint32_t *text_words, uint32_t *seen1, uint32_t *seen2) {
-    const uint64_t n_win = n_pos + 3 * n_seqs;  // 13-windows per strand copy: len - 12 = (len - 15) + 3
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_win) return;
-    uint64_t lo = 0, hi = n_seqs;
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (pos_base[mid] + 3 * mid <= g) lo = mid;
-        else hi = mid;
-    }
-    const uint64_t p = g - (pos_base[lo] + 3 * lo);
-    const uint64_t cum = pos_base[lo] + 15 * lo;
-    const uint64_t len = (lo + 1 < n_seqs ? pos_base[lo + 1] : n_pos) - pos_base[lo] + 15;
-    for (int strand = 0; strand < 2; ++strand) {
-        const uint64_t t = text_base + 2 * cum + (strand ? len : 0) + p;
-        const uint32_t v = flx_locus_kmer_at((const uint2 *)text_words, (uint32_t)t) >> 6;  // the first 13 of the 16 codes from t on
-        if (PASS == 0) {
-            if (set_bit(seen1, v)) set_bit(seen2, v);
-        } else if (!test_bit(seen2, v)) {
-            atomicOr(text_words + 2 * ((t >> 4) + kLocusPad) + 1, 0x10000u << (uint32_t)(t & 15));
-        }
-    }
-}
-
 // S1 (kmerset.h), one thread per text position: the 16-window from there on, if it lies in one piece of the text, against the exact
 // bitmap with every one of its bases replaced by the three others (48 far lookups; 10^7 windows: ~10 ms)
 __global__ void __launch_bounds__(256) k_text_safe1(const uint2 *text, uint64_t n_text, const uint32_t *present, uint32_t *safe_words) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t + 16 > n_text) return;
-    {  // no piece starts at t + 1 .. t + 15
-        const uint64_t t1 = t + 1;
-        const uint64_t w = (t1 >> 4) + kLocusPad;
-        const uint32_t s = (uint32_t)(t1 & 15);
-        const uint32_t b = ((text[w].y & 0xffffu) >> s) | ((text[w + 1].y & 0xffffu) << (16 - s));
-        if (b & 0x7fffu) return;
-    }
+    if (!flx_locus_in_piece(text, n_text, t, 16)) return;
     const uint32_t k = flx_locus_kmer_at(text, (uint32_t)t);
     uint32_t any = 0;
 #pragma unroll 4
@@ -354,36 +255,6 @@ __global__ void __launch_bounds__(256) k_text_safe1(const uint2 *text, uint64_t 
     if (!any) {
         const uint64_t wd = (t >> 4) + kLocusPad;  // (uint16 entry wd = half (wd & 1) of 32-bit word wd >> 1)
         atomicOr(safe_words + (wd >> 1), (1u << (uint32_t)(t & 15)) << (16 * (uint32_t)(wd & 1)));
-    }
-}
-
-// one thread per 16-mer start of the batch's sequences, both strand copies: the smallest text position of every distinct 16-mer
-__global__ void __launch_bounds__(256) k_locus_seed(const uint64_t *pos_base, uint64_t n_seqs, uint64_t n_pos, uint64_t text_base,
-                                                    const uint2 *text, uint32_t *seed, uint32_t mask, int shift) {
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_pos) return;
-    uint64_t lo = 0, hi = n_seqs;
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (pos_base[mid] <= g) lo = mid;
-        else hi = mid;
-    }
-    const uint64_t p = g - pos_base[lo];
-    const uint64_t cum = pos_base[lo] + 15 * lo;
-    const uint64_t len = (lo + 1 < n_seqs ? pos_base[lo + 1] : n_pos) - pos_base[lo] + 15;
-    for (int strand = 0; strand < 2; ++strand) {
-        const uint32_t t = (uint32_t)(text_base + 2 * cum + (strand ? len : 0) + p);
-        const uint32_t k = flx_locus_kmer_at(text, t);
-        uint32_t h = flx_locus_hash(k, shift);
-        for (;;) {
-            const uint32_t old = atomicCAS(&seed[h], kLocusEmpty, t);
-            if (old == kLocusEmpty) break;
-            if (flx_locus_kmer_at(text, old) == k) {  // (whoever holds the slot, its text is final: the slot's key cannot change)
-                atomicMin(&seed[h], t);
-                break;
-            }
-            h = (h + 1) & mask;
-        }
     }
 }
 
@@ -446,13 +317,12 @@ static void free_batches(std::vector<flx_kmerset::Batch> &batches) {
     }
     batches.clear();
 }
-static void free_batches(flx_kmerset *s) { free_batches(s->short_batches); }
 
 extern "C" void flx_kmerset_destroy(flx_kmerset *s) {
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    free_batches(s);
+    free_batches(s->short_batches);
     free_batches(s->asm_batches);
     for (uint32_t *p : {s->present, s->asm_only, s->seen1, s->seen2, s->seen3, s->prefilter, s->pre11, s->exact15, s->locus_text, s->locus_seed, s->locus_safe1})
         if (p) (void)hipFree(p);
@@ -617,86 +487,87 @@ static int resolve_bloom_candidates(flx_kmerset *s, std::vector<uint32_t> &cand 
     return FLX_OK;
 }
 
-extern "C" int flx_kmerset_finalize(flx_kmerset *s) {
-    if (!s) return FLX_ERR_INVALID;
+// ---- finalize, stage by stage (each on the context's stream, in this order) ----
+
+// Bloom screening (see the file header), with the promotion of the 16-mers it finds; the counting planes go afterwards
+static int screen_bloom(flx_kmerset *s) {
     flx_ctx *ctx = s->ctx;
-    if (s->final_) return FLX_OK;
-    FLX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    if (s->has_short) {
-        // Bloom screening (see file header)
-        flx_dbuf F1, F2, d_cand, d_n;
-        FLX_CHECK(flx_dalloc(ctx, F1, kBloomWords * 4));
-        FLX_CHECK(flx_dalloc(ctx, F2, kBloomWords * 4));
-        const unsigned cap = 1u << 20;
-        FLX_CHECK(flx_dalloc(ctx, d_cand, (size_t)cap * 4));
-        FLX_CHECK(flx_dalloc(ctx, d_n, 16));
-        FLX_HIP(ctx, hipMemsetAsync(F1.p, 0, kBloomWords * 4, st));
-        FLX_HIP(ctx, hipMemsetAsync(F2.p, 0, kBloomWords * 4, st));
+    flx_dbuf F1, F2, d_cand, d_n;
+    FLX_CHECK(flx_dalloc(ctx, F1, kBloomWords * 4));
+    FLX_CHECK(flx_dalloc(ctx, F2, kBloomWords * 4));
+    const unsigned cap = 1u << 20;
+    FLX_CHECK(flx_dalloc(ctx, d_cand, (size_t)cap * 4));
+    FLX_CHECK(flx_dalloc(ctx, d_n, 16));
+    FLX_HIP(ctx, hipMemsetAsync(F1.p, 0, kBloomWords * 4, st));
+    FLX_HIP(ctx, hipMemsetAsync(F2.p, 0, kBloomWords * 4, st));
+    FLX_HIP(ctx, hipMemsetAsync(d_n.p, 0, 16, st));
+    flx_time_begin(ctx, "flx_kmerset_bloom_screen");
+    hipLaunchKernelGGL(k_bloom_fill, dim3(8192), dim3(256), 0, st, s->seen1, kBitmapWords, F1.as<uint32_t>(), F2.as<uint32_t>());
+    // 1st: is any 16-mer with exactly 3 sightings a candidate?  (only those change the set)
+    hipLaunchKernelGGL(k_bloom_candidates, dim3(8192), dim3(256), 0, st, s->seen1, s->seen3, s->present, kBitmapWords,
+                       F2.as<uint32_t>(), d_cand.as<uint32_t>(), (unsigned int *)d_n.p, cap, 1);
+    flx_time_end(ctx);
+    unsigned int n3 = 0;
+    FLX_HIP(ctx, hipMemcpyAsync(&n3, d_n.p, 4, hipMemcpyDeviceToHost, st));
+    FLX_HIP(ctx, hipStreamSynchronize(st));
+    s->bloom_candidates = n3;
+    if (n3 > 0) {
+        // Exact replay needs EVERY candidate non-inserter (any count), because a false-positive 16-mer does not
+        // insert its bits and that can change the filter other 16-mers see.
         FLX_HIP(ctx, hipMemsetAsync(d_n.p, 0, 16, st));
-        flx_time_begin(ctx, "flx_kmerset_bloom_screen");
-        hipLaunchKernelGGL(k_bloom_fill, dim3(8192), dim3(256), 0, st, s->seen1, kBitmapWords, F1.as<uint32_t>(), F2.as<uint32_t>());
-        // 1st: is any 16-mer with exactly 3 sightings a candidate?  (only those change the set)
         hipLaunchKernelGGL(k_bloom_candidates, dim3(8192), dim3(256), 0, st, s->seen1, s->seen3, s->present, kBitmapWords,
-                           F2.as<uint32_t>(), d_cand.as<uint32_t>(), (unsigned int *)d_n.p, cap, 1);
-        flx_time_end(ctx);
-        unsigned int n3 = 0;
-        FLX_HIP(ctx, hipMemcpyAsync(&n3, d_n.p, 4, hipMemcpyDeviceToHost, st));
+                           F2.as<uint32_t>(), d_cand.as<uint32_t>(), (unsigned int *)d_n.p, cap, 0);
+        unsigned int nall = 0;
+        FLX_HIP(ctx, hipMemcpyAsync(&nall, d_n.p, 4, hipMemcpyDeviceToHost, st));
         FLX_HIP(ctx, hipStreamSynchronize(st));
-        s->bloom_candidates = n3;
-        if (n3 > 0) {
-            // Exact replay needs EVERY candidate non-inserter (any count), because a false-positive 16-mer does not
-            // insert its bits and that can change the filter other 16-mers see.
-            FLX_HIP(ctx, hipMemsetAsync(d_n.p, 0, 16, st));
-            hipLaunchKernelGGL(k_bloom_candidates, dim3(8192), dim3(256), 0, st, s->seen1, s->seen3, s->present, kBitmapWords,
-                               F2.as<uint32_t>(), d_cand.as<uint32_t>(), (unsigned int *)d_n.p, cap, 0);
-            unsigned int nall = 0;
-            FLX_HIP(ctx, hipMemcpyAsync(&nall, d_n.p, 4, hipMemcpyDeviceToHost, st));
+        if (nall > cap) return flx_fail(ctx, FLX_ERR_CAPACITY, "too many Bloom false-positive candidates (%u)", nall);
+        std::vector<uint32_t> cand(nall);
+        FLX_HIP(ctx, hipMemcpy(cand.data(), d_cand.p, (size_t)nall * 4, hipMemcpyDeviceToHost));
+        std::sort(cand.begin(), cand.end());
+        std::vector<uint8_t> is_fp;
+        FLX_CHECK(resolve_bloom_candidates(s, cand, is_fp));
+        // a false positive starts counting at 2 (kmers.cpp:152-155): 3 sightings are enough
+        std::vector<uint32_t> promote;
+        {
+            // which candidates have exactly 3 sightings: seen3 set, present clear
+            flx_dbuf d_q, d_o3, d_op;
+            FLX_CHECK(flx_dalloc(ctx, d_q, (size_t)nall * 4));
+            FLX_CHECK(flx_dalloc(ctx, d_o3, nall));
+            FLX_CHECK(flx_dalloc(ctx, d_op, nall));
+            FLX_HIP(ctx, hipMemcpy(d_q.p, cand.data(), (size_t)nall * 4, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(k_contains, dim3((nall + 255) / 256), dim3(256), 0, st, s->seen3, d_q.as<uint32_t>(), (uint64_t)nall, d_o3.as<uint8_t>());
+            hipLaunchKernelGGL(k_contains, dim3((nall + 255) / 256), dim3(256), 0, st, s->present, d_q.as<uint32_t>(), (uint64_t)nall, d_op.as<uint8_t>());
+            std::vector<uint8_t> o3(nall), op(nall);
             FLX_HIP(ctx, hipStreamSynchronize(st));
-            if (nall > cap) return flx_fail(ctx, FLX_ERR_CAPACITY, "too many Bloom false-positive candidates (%u)", nall);
-            std::vector<uint32_t> cand(nall);
-            FLX_HIP(ctx, hipMemcpy(cand.data(), d_cand.p, (size_t)nall * 4, hipMemcpyDeviceToHost));
-            std::sort(cand.begin(), cand.end());
-            std::vector<uint8_t> is_fp;
-            FLX_CHECK(resolve_bloom_candidates(s, cand, is_fp));
-            // a false positive starts counting at 2 (kmers.cpp:152-155): 3 sightings are enough
-            std::vector<uint32_t> promote;
-            std::vector<uint32_t> h3(nall);
-            {
-                // which candidates have exactly 3 sightings: seen3 set, present clear
-                flx_dbuf d_q, d_o3, d_op;
-                FLX_CHECK(flx_dalloc(ctx, d_q, (size_t)nall * 4));
-                FLX_CHECK(flx_dalloc(ctx, d_o3, nall));
-                FLX_CHECK(flx_dalloc(ctx, d_op, nall));
-                FLX_HIP(ctx, hipMemcpy(d_q.p, cand.data(), (size_t)nall * 4, hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(k_contains, dim3((nall + 255) / 256), dim3(256), 0, st, s->seen3, d_q.as<uint32_t>(), (uint64_t)nall, d_o3.as<uint8_t>());
-                hipLaunchKernelGGL(k_contains, dim3((nall + 255) / 256), dim3(256), 0, st, s->present, d_q.as<uint32_t>(), (uint64_t)nall, d_op.as<uint8_t>());
-                std::vector<uint8_t> o3(nall), op(nall);
-                FLX_HIP(ctx, hipStreamSynchronize(st));
-                FLX_HIP(ctx, hipMemcpy(o3.data(), d_o3.p, nall, hipMemcpyDeviceToHost));
-                FLX_HIP(ctx, hipMemcpy(op.data(), d_op.p, nall, hipMemcpyDeviceToHost));
-                for (unsigned i = 0; i < nall; ++i)
-                    if (is_fp[i]) {
-                        ++s->bloom_false_positives;
-                        if (o3[i] && !op[i]) promote.push_back(cand[i]);
-                    }
-            }
-            if (!promote.empty()) {
-                flx_dbuf d_p;
-                FLX_CHECK(flx_dalloc(ctx, d_p, promote.size() * 4));
-                FLX_HIP(ctx, hipMemcpy(d_p.p, promote.data(), promote.size() * 4, hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(k_set_bits, dim3((unsigned)((promote.size() + 255) / 256)), dim3(256), 0, st, s->present,
-                                   d_p.as<uint32_t>(), (uint64_t)promote.size());
-                FLX_HIP(ctx, hipStreamSynchronize(st));
-            }
+            FLX_HIP(ctx, hipMemcpy(o3.data(), d_o3.p, nall, hipMemcpyDeviceToHost));
+            FLX_HIP(ctx, hipMemcpy(op.data(), d_op.p, nall, hipMemcpyDeviceToHost));
+            for (unsigned i = 0; i < nall; ++i)
+                if (is_fp[i]) {
+                    ++s->bloom_false_positives;
+                    if (o3[i] && !op[i]) promote.push_back(cand[i]);
+                }
         }
-        // (the sequences stay until the locus text is built, below: their 17-mers are its witnesses)
-        for (uint32_t **p : {&s->seen1, &s->seen2, &s->seen3, &s->asm_only}) {
-            (void)hipFree(*p);
-            *p = nullptr;
+        if (!promote.empty()) {
+            flx_dbuf d_p;
+            FLX_CHECK(flx_dalloc(ctx, d_p, promote.size() * 4));
+            FLX_HIP(ctx, hipMemcpy(d_p.p, promote.data(), promote.size() * 4, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(k_set_bits, dim3((unsigned)((promote.size() + 255) / 256)), dim3(256), 0, st, s->present,
+                               d_p.as<uint32_t>(), (uint64_t)promote.size());
+            FLX_HIP(ctx, hipStreamSynchronize(st));
         }
     }
-    // size
+    // (the sequences stay until the locus text is built: their 17-mers are its witnesses)
+    for (uint32_t **p : {&s->seen1, &s->seen2, &s->seen3, &s->asm_only}) {
+        (void)hipFree(*p);
+        *p = nullptr;
+    }
+    return FLX_OK;
+}
+
+static int count_members(flx_kmerset *s) {
+    flx_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
     void *scr;
     FLX_CHECK(flx_scratch(ctx, 64, &scr));
     FLX_HIP(ctx, hipMemsetAsync(scr, 0, 8, st));
@@ -705,10 +576,17 @@ extern "C" int flx_kmerset_finalize(flx_kmerset *s) {
     FLX_HIP(ctx, hipMemcpyAsync(&sz, scr, 8, hipMemcpyDeviceToHost, st));
     FLX_HIP(ctx, hipStreamSynchronize(st));
     s->size = sz;
+    return FLX_OK;
+}
+
+// the 12-mer prefilters and the pair form of the exact bitmap (kmerset.h)
+static int build_filters(flx_kmerset *s) {
+    flx_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
     // prefilter: worth its L2 footprint while the 12-mer table stays sparse (a genome beyond ~20 Mbp saturates it)
     const char *pf_env = getenv("FLX_KMER_PREFILTER");  // "0" disables (A/B measurements)
     const bool pf_off = pf_env && pf_env[0] == '0';
-    if (!pf_off && sz > 0 && sz < (3ull << (kPrefilterBits - 1))) {
+    if (!pf_off && s->size > 0 && s->size < (3ull << (kPrefilterBits - 1))) {
         const size_t pf_bytes = (size_t)1 << (kPrefilterBits - 3);
         FLX_HIP(ctx, hipMalloc((void **)&s->prefilter, pf_bytes));
         FLX_HIP(ctx, hipMemsetAsync(s->prefilter, 0, pf_bytes, st));
@@ -718,7 +596,7 @@ extern "C" int flx_kmerset_finalize(flx_kmerset *s) {
         hipLaunchKernelGGL(k_build_pre11, dim3(2048), dim3(256), 0, st, s->prefilter, s->pre11);
         FLX_HIP(ctx, hipStreamSynchronize(st));
     }
-    if (sz > 0) {  // the pair form of the exact bitmap (what the cover kernel asks)
+    if (s->size > 0) {  // the pair form of the exact bitmap (what the cover kernel asks)
         // (no room for it: the set works without — scoring then takes the kernel that asks the 512 MiB bitmap, cover_wave.hip: k_kmer_cover)
         const char *pt = getenv("FLX_KMER_PAIRTABLE");  // "0": as if the allocation had failed (tests)
         hipError_t e = (pt && pt[0] == '0') ? hipErrorOutOfMemory : hipMalloc((void **)&s->exact15, (size_t)1 << 30);
@@ -731,138 +609,80 @@ extern "C" int flx_kmerset_finalize(flx_kmerset *s) {
             FLX_HIP(ctx, hipStreamSynchronize(st));
         }
     }
-    // the assembly as a text + seed table (kmerset.h).  Worth its memory while the 16-mer space is sparse: up to 2^28 text
-    // positions (a 128 Mbp assembly; the seed table is then 4 GiB); FLX_KMER_LOCUS_BUILD=0 leaves it out.
-    {
-        uint64_t n_text = 0, n_windows = 0;
-        for (auto &b : s->asm_batches) {
-            n_text += 2 * (b.n_pos + 15 * b.n_seqs);
-            n_windows += 2 * b.n_pos;
-        }
-        const char *lb = getenv("FLX_KMER_LOCUS_BUILD");
-        if (s->has_short && sz > 0 && s->exact15 && !(lb && lb[0] == '0')) {
-            // a set with short reads in it: the members themselves as a text (pathtext.hip) — every member is a window of it, so
-            // U13 holds there too; an assembly underneath is part of the same graph
-            std::vector<flx_seq_batch> wb;
-            for (auto *list : {&s->asm_batches, &s->short_batches})
-                for (auto &b : *list) wb.push_back({b.bases, b.offsets, b.pos_base, b.n_seqs, b.n_pos});
-            // (the text is optional — include/filtlong_hip.h: "when that memory cannot be had the set works without" — so a build
-            // that fails on its transient memory, ~12 GB for the C4 set, leaves a set without a text, not a failed finalize)
-            // ONLY a failure for want of memory: a kernel fault or any other HIP error in the build is an error of finalize (it would
-            // otherwise surface later in an unrelated call — hipGetLastError does not clear a sticky fault; advisor, round 5)
-            const int text_rc = flx_build_path_text(ctx, s->present, (const uint8_t *)s->exact15, sz, wb.data(), wb.size(), &s->locus_text, &s->locus_seed, &s->locus);
-            if (text_rc != FLX_OK) {
-                if (s->locus_text) (void)hipFree(s->locus_text);
-                if (s->locus_seed) (void)hipFree(s->locus_seed);
-                s->locus_text = s->locus_seed = nullptr;
-                const bool no_memory = text_rc == FLX_ERR_NOMEM || (text_rc == FLX_ERR_HIP && ctx->err.find(hipGetErrorString(hipErrorOutOfMemory)) != std::string::npos);
-                if (!no_memory) return text_rc;
-                (void)hipGetLastError();
-                ctx->err.clear();  // (the set works without a text: nothing failed)
-            }
-            s->has_locus = s->locus_text != nullptr;
-        } else if (!s->has_short && n_windows > 0 && n_text <= (1ull << 28) && !(lb && lb[0] == '0')) {
-            // (!has_short: with short reads in the set — and no room for the pair table, or the text switched off above — the assembly's
-            // text would NOT hold every member as a window, which is what U13 / S1 rest on: no text then, and no memory spent on one)
-            const uint64_t n_words = (n_text + 15) / 16;
-            const uint64_t n_alloc = n_words + kLocusPad + 68;
-            int bits = 10;
-            while ((1ull << bits) < n_windows * 5 / 2) ++bits;
-            const uint64_t slots = 1ull << bits;
-            hipError_t e1 = hipMalloc((void **)&s->locus_text, n_alloc * 8);
-            hipError_t e2 = e1 == hipSuccess ? hipMalloc((void **)&s->locus_seed, slots * 4) : e1;
-            // the two counting planes of U13 as well, BEFORE anything is built: a failure here is "no text", like the two above
-            uint32_t *u13_planes = nullptr;
-            const size_t plane = (size_t)1 << (26 - 3);
-            hipError_t e3 = e2 == hipSuccess ? hipMalloc((void **)&u13_planes, 2 * plane) : e2;
-            if (e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess) {
-                struct PlaneGuard { uint32_t *p; ~PlaneGuard() { if (p) (void)hipFree(p); } } plane_guard{u13_planes};
-                FLX_HIP(ctx, hipMemsetAsync(s->locus_text, 0, n_alloc * 8, st));
-                // padding: no window may start or end there
-                std::vector<uint32_t> pad_front(2 * kLocusPad), pad_back(2 * 68);
-                for (size_t i = 0; i < pad_front.size(); i += 2) { pad_front[i] = 0; pad_front[i + 1] = 0xffffu; }
-                for (size_t i = 0; i < pad_back.size(); i += 2) { pad_back[i] = 0; pad_back[i + 1] = 0xffffu; }
-                FLX_HIP(ctx, hipMemcpyAsync(s->locus_text, pad_front.data(), pad_front.size() * 4, hipMemcpyHostToDevice, st));
-                FLX_HIP(ctx, hipMemcpyAsync(s->locus_text + 2 * (kLocusPad + n_words), pad_back.data(), pad_back.size() * 4, hipMemcpyHostToDevice, st));
-                FLX_HIP(ctx, hipMemsetAsync(s->locus_seed, 0xff, slots * 4, st));
-                flx_time_begin(ctx, "flx_kmerset_locus_build");
-                uint64_t tb = 0;
-                for (auto &b : s->asm_batches) {
-                    const uint64_t nb_bases = b.n_pos + 15 * b.n_seqs;
-                    if (nb_bases)
-                        hipLaunchKernelGGL(k_locus_text, dim3((unsigned)((nb_bases + 255) / 256)), dim3(256), 0, st, b.bases, b.offsets, b.pos_base,
-                                           b.n_seqs, b.n_pos, tb, s->locus_text);
-                    tb += 2 * nb_bases;
-                }
-                // the last word's bases behind the text must not look like the start of anything: a copy "starts" at n_text
-                if (n_text % 16) {
-                    const uint32_t tail_bits = 0xffffu & ~((1u << (n_text % 16)) - 1u);
-                    hipLaunchKernelGGL(k_set_word_bits, dim3(1), dim3(1), 0, st, s->locus_text + 2 * (kLocusPad + n_words - 1) + 1, tail_bits);
-                }
-                {  // U13: the 13-mers that occur once
-                    FLX_HIP(ctx, hipMemsetAsync(u13_planes, 0, 2 * plane, st));
-                    uint32_t *seen1 = u13_planes, *seen2 = seen1 + plane / 4;
-                    for (int pass = 0; pass < 2; ++pass) {
-                        tb = 0;
-                        for (auto &b : s->asm_batches) {
-                            const uint64_t n_win = b.n_pos + 3 * b.n_seqs;
-                            if (n_win && pass == 0)
-                                hipLaunchKernelGGL(k_locus_u13<0>, dim3((unsigned)((n_win + 255) / 256)), dim3(256), 0, st, b.pos_base, b.n_seqs,
-                                                   b.n_pos, tb, s->locus_text, seen1, seen2);
-                            else if (n_win)
-                                hipLaunchKernelGGL(k_locus_u13<1>, dim3((unsigned)((n_win + 255) / 256)), dim3(256), 0, st, b.pos_base, b.n_seqs,
-                                                   b.n_pos, tb, s->locus_text, seen1, seen2);
-                            tb += 2 * (b.n_pos + 15 * b.n_seqs);
-                        }
-                    }
-                    FLX_HIP(ctx, hipStreamSynchronize(st));  // (the counters go out of scope)
-                }
-                tb = 0;
-                for (auto &b : s->asm_batches) {
-                    if (b.n_pos)
-                        hipLaunchKernelGGL(k_locus_seed, dim3((unsigned)((b.n_pos + 255) / 256)), dim3(256), 0, st, b.pos_base, b.n_seqs, b.n_pos, tb,
-                                           (const uint2 *)s->locus_text, s->locus_seed, (uint32_t)(slots - 1), 32 - bits);
-                    tb += 2 * (b.n_pos + 15 * b.n_seqs);
-                }
-                flx_time_end(ctx);
-                FLX_HIP(ctx, hipGetLastError());
-                FLX_HIP(ctx, hipStreamSynchronize(st));
-                s->locus.text = (const uint2 *)s->locus_text;
-                s->locus.n_alloc = (uint32_t)n_alloc;
-                s->locus.n_text = n_text;
-                s->locus.seed = s->locus_seed;
-                s->locus.seed_mask = (uint32_t)(slots - 1);
-                s->locus.seed_shift = 32 - bits;
-                s->has_locus = true;
-            } else {  // not enough memory for it: the scoring path works without
-                if (s->locus_text) (void)hipFree(s->locus_text);
-                if (s->locus_seed) (void)hipFree(s->locus_seed);
-                if (u13_planes) (void)hipFree(u13_planes);
-                s->locus_text = s->locus_seed = nullptr;
-                (void)hipGetLastError();
-            }
-        }
-        free_batches(s->asm_batches);
-        free_batches(s);
-        s->locus.safe1 = nullptr;
-        const char *s1 = getenv("FLX_KMER_SAFE1");  // "0": without S1 (tests, A/B)
-        if (s->has_locus && !(s1 && s1[0] == '0')) {
-            const size_t bytes = (((size_t)s->locus.n_alloc + 1) / 2) * 4;
-            if (hipMalloc((void **)&s->locus_safe1, bytes) == hipSuccess) {
-                FLX_HIP(ctx, hipMemsetAsync(s->locus_safe1, 0, bytes, st));
-                flx_time_begin(ctx, "flx_kmerset_locus_build");
-                hipLaunchKernelGGL(k_text_safe1, dim3((unsigned)((s->locus.n_text + 255) / 256)), dim3(256), 0, st, s->locus.text, s->locus.n_text,
-                                   s->present, s->locus_safe1);
-                flx_time_end(ctx);
-                FLX_HIP(ctx, hipGetLastError());
-                FLX_HIP(ctx, hipStreamSynchronize(st));
-                s->locus.safe1 = (const uint16_t *)s->locus_safe1;
-            } else {
-                s->locus_safe1 = nullptr;
-                (void)hipGetLastError();
-            }
+    return FLX_OK;
+}
+
+// The set as a text + seed table (kmerset.h; built in pathtext.hip).  Worth its memory while the 16-mer space is sparse: up to 2^28
+// text positions (a 128 Mbp assembly; the seed table is then 4 GiB); FLX_KMER_LOCUS_BUILD=0 leaves it out.
+static int build_text(flx_kmerset *s) {
+    flx_ctx *ctx = s->ctx;
+    const char *lb = getenv("FLX_KMER_LOCUS_BUILD");
+    if (lb && lb[0] == '0') return FLX_OK;
+    std::vector<flx_seq_batch> wb;
+    for (auto *list : {&s->asm_batches, &s->short_batches})
+        for (auto &b : *list) wb.push_back({b.bases, b.offsets, b.pos_base, b.n_seqs, b.n_pos});
+    if (!s->has_short) {
+        // an allocation that fails leaves a set without a text; any other HIP error is an error of finalize
+        FLX_CHECK(flx_build_assembly_text(ctx, wb.data(), wb.size(), &s->locus_text, &s->locus_seed, &s->locus));
+    } else if (s->size > 0 && s->exact15) {
+        // a set with short reads in it: the members themselves as a text — every member is a window of it, so U13 holds there
+        // too; an assembly underneath is part of the same graph.  (Without room for the pair table there is NO text: the assembly's
+        // alone would not hold every member as a window, which is what U13 / S1 rest on.)
+        // (the text is optional — include/filtlong_hip.h: "when that memory cannot be had the set works without" — so a build
+        // that fails on its transient memory, ~12 GB for the C4 set, leaves a set without a text, not a failed finalize)
+        // ONLY a failure for want of memory: a kernel fault or any other HIP error in the build is an error of finalize (it would
+        // otherwise surface later in an unrelated call — hipGetLastError does not clear a sticky fault; advisor, round 5)
+        const int text_rc = flx_build_path_text(ctx, s->present, (const uint8_t *)s->exact15, s->size, wb.data(), wb.size(), &s->locus_text, &s->locus_seed, &s->locus);
+        if (text_rc != FLX_OK) {
+            if (s->locus_text) (void)hipFree(s->locus_text);
+            if (s->locus_seed) (void)hipFree(s->locus_seed);
+            s->locus_text = s->locus_seed = nullptr;
+            const bool no_memory = text_rc == FLX_ERR_NOMEM || (text_rc == FLX_ERR_HIP && ctx->err.find(hipGetErrorString(hipErrorOutOfMemory)) != std::string::npos);
+            if (!no_memory) return text_rc;
+            (void)hipGetLastError();
+            ctx->err.clear();  // (the set works without a text: nothing failed)
         }
     }
+    s->has_locus = s->locus_text != nullptr;
+    return FLX_OK;
+}
+
+// S1 (kmerset.h) from the finished text; no memory for it: the text works without
+static int build_safe1(flx_kmerset *s) {
+    flx_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    s->locus.safe1 = nullptr;
+    const char *s1 = getenv("FLX_KMER_SAFE1");  // "0": without S1 (tests, A/B)
+    if (!s->has_locus || (s1 && s1[0] == '0')) return FLX_OK;
+    const size_t bytes = (((size_t)s->locus.n_alloc + 1) / 2) * 4;
+    if (hipMalloc((void **)&s->locus_safe1, bytes) != hipSuccess) {
+        s->locus_safe1 = nullptr;
+        (void)hipGetLastError();
+        return FLX_OK;
+    }
+    FLX_HIP(ctx, hipMemsetAsync(s->locus_safe1, 0, bytes, st));
+    flx_time_begin(ctx, "flx_kmerset_locus_build");
+    hipLaunchKernelGGL(k_text_safe1, dim3((unsigned)((s->locus.n_text + 255) / 256)), dim3(256), 0, st, s->locus.text, s->locus.n_text,
+                       s->present, s->locus_safe1);
+    flx_time_end(ctx);
+    FLX_HIP(ctx, hipGetLastError());
+    FLX_HIP(ctx, hipStreamSynchronize(st));
+    s->locus.safe1 = (const uint16_t *)s->locus_safe1;
+    return FLX_OK;
+}
+
+extern "C" int flx_kmerset_finalize(flx_kmerset *s) {
+    if (!s) return FLX_ERR_INVALID;
+    flx_ctx *ctx = s->ctx;
+    if (s->final_) return FLX_OK;
+    FLX_HIP(ctx, hipSetDevice(ctx->device));
+    if (s->has_short) FLX_CHECK(screen_bloom(s));
+    FLX_CHECK(count_members(s));
+    FLX_CHECK(build_filters(s));
+    FLX_CHECK(build_text(s));
+    free_batches(s->asm_batches);  // the sequences were kept for the text
+    free_batches(s->short_batches);
+    FLX_CHECK(build_safe1(s));
     s->final_ = true;
     return FLX_OK;
 }

@@ -1,5 +1,8 @@
-// pathtext.hip — a 16-mer set without an assembly (short reads, src/kmers.cpp:142-166) as a TEXT for the locus path of the cover
-// kernel (kmerset.h: flx_locus; cover_wave.hip: k_kmer_cover_w<.., LOCUS>, cover_queue.hip: k_kmer_cover_q).
+// pathtext.hip — a 16-mer set as a TEXT for the locus path of the cover kernels (kmerset.h: flx_locus; cover_wave.hip:
+// k_kmer_cover_w<.., LOCUS>, cover_queue.hip: k_kmer_cover_q).  Three forms write the bases and the piece starts — the assembly itself
+// (flx_build_assembly_text), and for a set with short reads in it (src/kmers.cpp:142-166) the two path forms below
+// (flx_build_path_text) — and ONE finish (text_alloc / text_finish) gives each of them its padding, the U13 bits and the seed table,
+// from nothing but the finished text.
 //
 // The locus path needs a text in which every 16-base window inside one piece is a member, and — for the refutation by unique
 // 13-mers — in which every member IS such a window.  An assembly is that text for its own 16-mers.  For any other set the
@@ -14,7 +17,7 @@
 // a cycle: every member of a cycle becomes a path of its own), a path of m members is a piece of m + 15 bases, and along a
 // genome the pairing is wrong only where a 15-mer repeats — about every 200 bases of a 5 Mbp genome, where the cover kernel
 // seeds again inside the span.  Everything runs on the device: ranks from a popcount index of the bitmap, predecessor links,
-// pointer jumping to (head, distance), lengths, offsets by an exclusive scan, the text, U13, the seed table.
+// pointer jumping to (head, distance), lengths, offsets by an exclusive scan, the text.
 //
 // Round 4, second form (flx_build_path_text, first choice): the same construction one order higher.  At order 16 a piece ends
 // wherever a 16-mer of the genome repeats (every ~580 bases of a read through a 5 Mbp genome even with the witnesses); the
@@ -23,7 +26,7 @@
 // (radix sort), linked by binary search, cut into paths exactly like the 16-mers above — a piece of m 24-mers is a text of m + 23
 // bases in which every 16-base window is a member by construction.  Members that no such 24-mer holds (the ends of the
 // sequences, 16-mers that only just made the count) become pieces of their own, so that every member is a window of the text
-// (U13).  U13 and the seeds are then taken from the text itself, one thread per text position.
+// (U13).
 #include <cstring>
 #include <vector>
 
@@ -32,12 +35,6 @@
 #include "rank_internal.h"
 
 namespace {
-
-__device__ __forceinline__ bool pt_test_bit(const uint32_t *bm, uint32_t k) { return (bm[k >> 5] >> (k & 31)) & 1u; }
-__device__ __forceinline__ bool pt_set_bit(uint32_t *bm, uint32_t k) {
-    const uint32_t m = 1u << (k & 31);
-    return (atomicOr(&bm[k >> 5], m) & m) != 0;
-}
 
 // members per 256 bits of the bitmap (2^24 blocks)
 __global__ void __launch_bounds__(256) k_pt_count256(const uint32_t *bm, int64_t *cnt) {
@@ -80,12 +77,7 @@ __global__ void __launch_bounds__(256) k_pt_witness(const uint8_t *bases, const 
                                                     uint64_t n_pos, const uint8_t *exact15, PtWitness w) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_pos) return;
-    uint64_t lo = 0, hi = n_seqs;
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (pos_base[mid] <= g) lo = mid;
-        else hi = mid;
-    }
+    const uint64_t lo = flx_seq_of(pos_base, n_seqs, g, 0);
     const uint64_t p = g - pos_base[lo];
     const uint64_t len = (lo + 1 < n_seqs ? pos_base[lo + 1] : n_pos) - pos_base[lo] + 15;
     if (p + 17 > len) return;
@@ -93,16 +85,8 @@ __global__ void __launch_bounds__(256) k_pt_witness(const uint8_t *bases, const 
     // the 17 codes of both strands (src/kmers.cpp:176-219): forward as they come, reverse from the other end in the reverse encoder's codes
     uint64_t f = 0, r = 0;
     for (int j = 0; j < 17; ++j) {
-        uint32_t cf = 0, cr = 0;
-        switch (sq[j]) {
-            case 'A': case 'a': cr = 3; break;
-            case 'C': case 'c': cf = 1; cr = 2; break;
-            case 'G': case 'g': cf = 2; cr = 1; break;
-            case 'T': case 't': cf = 3; break;
-            default: break;
-        }
-        f = (f << 2) | cf;
-        r |= (uint64_t)cr << (2 * j);
+        f = (f << 2) | flx_base_fwd(sq[j]);
+        r |= (uint64_t)flx_base_rev_code(sq[j]) << (2 * j);
     }
     const uint64_t two[2] = {f, r};
     for (int q = 0; q < 2; ++q) {
@@ -199,10 +183,11 @@ __global__ void __launch_bounds__(256) k_pt_lengths(uint32_t n, uint32_t *link, 
     }
     atomicMax(&len[link[i]], dist[i] + 1u);
 }
-__global__ void __launch_bounds__(256) k_pt_piece_bases(uint32_t n, const uint32_t *link, const uint32_t *len, int64_t *bases) {
+// bases of the piece every head starts: its elements and the `extra` bases in front of the first one's last
+__global__ void __launch_bounds__(256) k_pt_piece_bases(uint32_t n, const uint32_t *link, const uint32_t *len, int extra, int64_t *bases) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    bases[i] = link[i] == i ? (int64_t)len[i] + 15 : 0;
+    bases[i] = link[i] == i ? (int64_t)len[i] + extra : 0;
 }
 
 __device__ __forceinline__ void pt_put(uint32_t *text_words, uint64_t t, uint32_t code, bool starts_piece) {
@@ -211,56 +196,22 @@ __device__ __forceinline__ void pt_put(uint32_t *text_words, uint64_t t, uint32_
     if (starts_piece) atomicOr(w + 1, 1u << (uint32_t)(t & 15));
 }
 
-__global__ void __launch_bounds__(256) k_pt_text(uint32_t n, const uint32_t *members, const uint32_t *link, const uint32_t *dist, const int64_t *off,
+// every element (an edge of ORDER bases: a member at order 16, a 24-mer at order 24) writes its last base, the head of a piece
+// the ORDER - 1 bases in front of it as well
+template <typename Edge, int ORDER>
+__global__ void __launch_bounds__(256) k_pt_text(uint32_t n, const Edge *edges, const uint32_t *link, const uint32_t *dist, const int64_t *off,
                                                  uint32_t *text_words) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint32_t e = members[i];
+    const Edge e = edges[i];
     const uint64_t o = (uint64_t)off[link[i]];
-    pt_put(text_words, o + 15 + dist[i], e & 3u, false);
+    pt_put(text_words, o + (ORDER - 1) + dist[i], (uint32_t)(e & 3u), false);
     if (dist[i] == 0) {
-        for (int j = 0; j < 15; ++j) pt_put(text_words, o + j, (e >> (30 - 2 * j)) & 3u, j == 0);
+        for (int j = 0; j < ORDER - 1; ++j) pt_put(text_words, o + j, (uint32_t)((e >> (2 * (ORDER - 1 - j))) & 3u), j == 0);
     }
 }
 
-// U13 (kmerset.h): every member's first 13 bases, and behind the last member of a piece the three 13-mers that follow
-template <int PASS>
-__global__ void __launch_bounds__(256) k_pt_u13(uint32_t n, const uint32_t *members, const uint32_t *link, const uint32_t *dist, const uint32_t *len,
-                                                const int64_t *off, uint32_t *text_words, uint32_t *seen1, uint32_t *seen2) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t e = members[i], h = link[i];
-    const uint64_t t = (uint64_t)off[h] + dist[i];
-    const int extra = dist[i] + 1 == len[h] ? 3 : 0;
-    for (int k = 0; k <= extra; ++k) {
-        const uint32_t v = (e >> (6 - 2 * k)) & 0x3FFFFFFu;
-        if (PASS == 0) {
-            if (pt_set_bit(seen1, v)) pt_set_bit(seen2, v);
-        } else if (!pt_test_bit(seen2, v)) {
-            atomicOr(text_words + 2 * (((t + k) >> 4) + kLocusPad) + 1, 0x10000u << (uint32_t)((t + k) & 15));
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256) k_pt_seed(uint32_t n, const uint32_t *members, const uint32_t *link, const uint32_t *dist, const int64_t *off,
-                                                 const uint2 *text, uint32_t *seed, uint32_t mask, int shift) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t k = members[i];
-    const uint32_t t = (uint32_t)((uint64_t)off[link[i]] + dist[i]);
-    uint32_t h = flx_locus_hash(k, shift);
-    for (;;) {
-        const uint32_t old = atomicCAS(&seed[h], kLocusEmpty, t);
-        if (old == kLocusEmpty) break;
-        if (flx_locus_kmer_at(text, old) == k) {  // (cannot happen: every member is the window of one text position)
-            atomicMin(&seed[h], t);
-            break;
-        }
-        h = (h + 1) & mask;
-    }
-}
-
-__global__ void k_pt_set_word_bits(uint32_t *word, uint32_t bits) { *word |= bits; }
+__global__ void k_set_word_bits(uint32_t *word, uint32_t bits) { *word |= bits; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // order 24
@@ -272,12 +223,7 @@ __global__ void __launch_bounds__(256) k24_emit(const uint8_t *bases, const uint
                                                 const uint32_t *present, uint64_t *keys) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_pos) return;
-    uint64_t lo = 0, hi = n_seqs;
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (pos_base[mid] <= g) lo = mid;
-        else hi = mid;
-    }
+    const uint64_t lo = flx_seq_of(pos_base, n_seqs, g, 0);
     const uint64_t p = g - pos_base[lo];
     const uint64_t len = (lo + 1 < n_seqs ? pos_base[lo + 1] : n_pos) - pos_base[lo] + 15;
     uint64_t kf = kNo24, kr = kNo24;
@@ -285,21 +231,13 @@ __global__ void __launch_bounds__(256) k24_emit(const uint8_t *bases, const uint
         const uint8_t *sq = bases + offsets[lo] + p;
         uint64_t f = 0, r = 0;
         for (int j = 0; j < 24; ++j) {
-            uint32_t cf = 0, cr = 0;
-            switch (sq[j]) {
-                case 'A': case 'a': cr = 3; break;
-                case 'C': case 'c': cf = 1; cr = 2; break;
-                case 'G': case 'g': cf = 2; cr = 1; break;
-                case 'T': case 't': cf = 3; break;
-                default: break;
-            }
-            f = (f << 2) | cf;
-            r |= (uint64_t)cr << (2 * j);
+            f = (f << 2) | flx_base_fwd(sq[j]);
+            r |= (uint64_t)flx_base_rev_code(sq[j]) << (2 * j);
         }
         bool okf = true, okr = true;
         for (int w = 0; w < 9; ++w) {
-            okf = okf && pt_test_bit(present, (uint32_t)(f >> (2 * w)));
-            okr = okr && pt_test_bit(present, (uint32_t)(r >> (2 * w)));
+            okf = okf && flx_test_bit(present, (uint32_t)(f >> (2 * w)));
+            okr = okr && flx_test_bit(present, (uint32_t)(r >> (2 * w)));
         }
         if (okf) kf = f;
         if (okr) kr = r;
@@ -347,33 +285,16 @@ __global__ void __launch_bounds__(256) k24_pred(const uint64_t *edges, uint32_t 
     dist[i] = p == i ? 0u : 1u;
 }
 
-__global__ void __launch_bounds__(256) k24_piece_bases(uint32_t n, const uint32_t *link, const uint32_t *len, int64_t *bases) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    bases[i] = link[i] == i ? (int64_t)len[i] + 23 : 0;
-}
-
 __global__ void __launch_bounds__(256) k24_cover(uint32_t n, const uint64_t *edges, uint32_t *covered) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t e = edges[i];
-    for (int w = 0; w < 9; ++w) pt_set_bit(covered, (uint32_t)(e >> (2 * w)));
+    for (int w = 0; w < 9; ++w) flx_set_bit(covered, (uint32_t)(e >> (2 * w)));
 }
 __global__ void __launch_bounds__(256) k24_leftover(const uint32_t *present, uint32_t *covered, uint64_t n_words) {  // covered := present & ~covered
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * blockDim.x) covered[i] = present[i] & ~covered[i];
 }
 
-__global__ void __launch_bounds__(256) k24_text(uint32_t n, const uint64_t *edges, const uint32_t *link, const uint32_t *dist, const int64_t *off,
-                                                uint32_t *text_words) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t e = edges[i];
-    const uint64_t o = (uint64_t)off[link[i]];
-    pt_put(text_words, o + 23 + dist[i], (uint32_t)(e & 3u), false);
-    if (dist[i] == 0) {
-        for (int j = 0; j < 23; ++j) pt_put(text_words, o + j, (uint32_t)((e >> (46 - 2 * j)) & 3u), j == 0);
-    }
-}
 __global__ void __launch_bounds__(256) k24_text_leftover(uint32_t n, const uint32_t *members, uint64_t text_base, uint32_t *text_words) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -381,30 +302,39 @@ __global__ void __launch_bounds__(256) k24_text_leftover(uint32_t n, const uint3
     for (int j = 0; j < 16; ++j) pt_put(text_words, text_base + 16ull * i + j, (e >> (30 - 2 * j)) & 3u, j == 0);
 }
 
-// ---- U13 and seeds from the text itself: one thread per text position ----
-// no piece starts at t + 1 .. t + len - 1 and the window ends inside the text
-__device__ __forceinline__ bool pt_in_piece(const uint2 *text, uint64_t n_text, uint64_t t, int len) {
-    if (t + len > n_text) return false;
-    const uint64_t t1 = t + 1;
-    const uint64_t w = (t1 >> 4) + kLocusPad;
-    const uint32_t s = (uint32_t)(t1 & 15);
-    const uint32_t b = ((text[w].y & 0xffffu) >> s) | ((text[w + 1].y & 0xffffu) << (16 - s));
-    return (b & ((1u << (len - 1)) - 1u)) == 0;
+// ---- the assembly form: one thread per base of the batch's sequences, which writes it into both strand copies ----
+__global__ void __launch_bounds__(256) k_locus_text(const uint8_t *bases, const uint64_t *offsets, const uint64_t *pos_base,
+                                                    uint64_t n_seqs, uint64_t n_pos, uint64_t text_base, uint32_t *text_words) {
+    const uint64_t n_bases = n_pos + 15 * n_seqs;
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_bases) return;
+    const uint64_t lo = flx_seq_of(pos_base, n_seqs, g, 15);
+    const uint64_t cum = pos_base[lo] + 15 * lo;  // bases of the sequences before it
+    const uint64_t len = (lo + 1 < n_seqs ? pos_base[lo + 1] : n_pos) - pos_base[lo] + 15;
+    const uint64_t o = g - cum;
+    const uint8_t c = bases[offsets[lo] + o];
+    const uint64_t tf = text_base + 2 * cum + o, tr = text_base + 2 * cum + len + (len - 1 - o);
+    pt_put(text_words, tf, flx_base_fwd(c), o == 0);
+    pt_put(text_words, tr, flx_base_rev_code(c), o == len - 1);
 }
+
+// ---- U13 and seeds from the text itself, for every form: one thread per text position ----
+// U13 (kmerset.h), two passes over every 13-base window inside a piece: count its value (saturating at 2: two bitmaps of 4^13 bits),
+// then mark the windows whose value was seen once
 template <int PASS>
 __global__ void __launch_bounds__(256) k_text_u13(uint32_t *text_words, uint64_t n_text, uint32_t *seen1, uint32_t *seen2) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_text || !pt_in_piece((const uint2 *)text_words, n_text, t, 13)) return;
+    if (t >= n_text || !flx_locus_in_piece((const uint2 *)text_words, n_text, t, 13)) return;
     const uint32_t v = flx_locus_kmer_at((const uint2 *)text_words, (uint32_t)t) >> 6;
     if (PASS == 0) {
-        if (pt_set_bit(seen1, v)) pt_set_bit(seen2, v);
-    } else if (!pt_test_bit(seen2, v)) {
+        if (flx_set_bit(seen1, v)) flx_set_bit(seen2, v);
+    } else if (!flx_test_bit(seen2, v)) {
         atomicOr(text_words + 2 * ((t >> 4) + kLocusPad) + 1, 0x10000u << (uint32_t)(t & 15));
     }
 }
 __global__ void __launch_bounds__(256) k_text_seed(const uint2 *text, uint64_t n_text, uint32_t *seed, uint32_t mask, int shift) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_text || !pt_in_piece(text, n_text, t, 16)) return;
+    if (t >= n_text || !flx_locus_in_piece(text, n_text, t, 16)) return;
     const uint32_t k = flx_locus_kmer_at(text, (uint32_t)t);
     uint32_t h = flx_locus_hash(k, shift);
     for (;;) {
@@ -418,7 +348,140 @@ __global__ void __launch_bounds__(256) k_text_seed(const uint2 *text, uint64_t n
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// the path section of both orders: predecessor links -> head and distance per element, piece lengths, piece offsets
+// ---------------------------------------------------------------------------------------------------------------------
+struct PathSection {
+    flx_dbuf link0, link1, dist0, dist1, len, bases, off;
+    uint32_t *link = nullptr, *dist = nullptr;  // after paths_from_links: the head of every element's path and its distance from it
+    bool alloc(uint32_t n) {                    // (the pred kernel of the order writes link0 / dist0)
+        for (flx_dbuf *b : {&link0, &link1, &dist0, &dist1, &len})
+            if (hipMalloc(&b->p, (size_t)n * 4) != hipSuccess) return false;
+        return hipMalloc(&bases.p, ((size_t)n + 1) * 8) == hipSuccess && hipMalloc(&off.p, ((size_t)n + 1) * 8) == hipSuccess;
+    }
+};
+
+// Pointer jumping to (head, distance), the pieces' lengths in elements, and their offsets in the text by an exclusive scan of their
+// bases (elements + `extra`: 15 at order 16, 23 at order 24); off[n] is the number of bases of all pieces.
+int paths_from_links(flx_ctx *ctx, PathSection &ps, uint32_t n, int extra, void *ws, size_t ws_bytes) {
+    hipStream_t st = ctx->stream;
+    const uint32_t nb = (n + 255) / 256;
+    uint32_t *link = ps.link0.as<uint32_t>(), *link2 = ps.link1.as<uint32_t>(), *dist = ps.dist0.as<uint32_t>(), *dist2 = ps.dist1.as<uint32_t>();
+    int rounds = 1;
+    while ((1ull << rounds) < (uint64_t)n + 1) ++rounds;
+    for (int r = 0; r < rounds; ++r) {
+        hipLaunchKernelGGL(k_pt_jump, dim3(nb), dim3(256), 0, st, n, link, dist, link2, dist2);
+        std::swap(link, link2);
+        std::swap(dist, dist2);
+    }
+    FLX_HIP(ctx, hipMemsetAsync(ps.len.p, 0, (size_t)n * 4, st));
+    hipLaunchKernelGGL(k_pt_heads, dim3(nb), dim3(256), 0, st, n, link, dist, ps.len.as<uint32_t>());
+    hipLaunchKernelGGL(k_pt_lengths, dim3(nb), dim3(256), 0, st, n, link, dist, ps.len.as<uint32_t>());
+    FLX_HIP(ctx, hipMemsetAsync(ps.bases.p, 0, ((size_t)n + 1) * 8, st));
+    hipLaunchKernelGGL(k_pt_piece_bases, dim3(nb), dim3(256), 0, st, n, link, ps.len.as<uint32_t>(), extra, ps.bases.as<int64_t>());
+    FLX_CHECK(flx_exclusive_scan_i64(ctx, (uint64_t)n + 1, ps.bases.as<int64_t>(), ps.off.as<int64_t>(), ws, ws_bytes));
+    ps.link = link;
+    ps.dist = dist;
+    return FLX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the finish of every form: room for the text, then — once the form has written its bases and piece starts — U13 and the seeds
+// ---------------------------------------------------------------------------------------------------------------------
+struct TextBuild {
+    flx_dbuf text, seed, seen;  // seen: the two counting planes of U13 (4^13 bits each)
+    uint64_t n_text = 0, n_words = 0, n_alloc = 0;
+    int bits = 0;  // log2 of the seed table's slots
+    uint32_t *words() { return text.as<uint32_t>(); }
+};
+constexpr size_t kU13Plane = (size_t)1 << (26 - 3);
+constexpr uint64_t kBackPad = 68;
+
+// Sizes and allocates the text of n_text positions, a seed table for n_keys keys (x 5/2, rounded up to a power of two, at least
+// 2^10 slots) and the U13 planes BEFORE anything is built, and queues the padding, the seed fill and the plane clear.  No memory:
+// FLX_OK with tb.text.p == nullptr, nothing left allocated and the HIP error cleared.
+int text_alloc(flx_ctx *ctx, uint64_t n_text, uint64_t n_keys, TextBuild &tb) {
+    hipStream_t st = ctx->stream;
+    tb.n_text = n_text;
+    tb.n_words = (n_text + 15) / 16;
+    tb.n_alloc = tb.n_words + kLocusPad + kBackPad;
+    tb.bits = 10;
+    while ((1ull << tb.bits) < n_keys * 5 / 2) ++tb.bits;
+    const uint64_t slots = 1ull << tb.bits;
+    if (hipMalloc(&tb.text.p, tb.n_alloc * 8) != hipSuccess || hipMalloc(&tb.seed.p, slots * 4) != hipSuccess || hipMalloc(&tb.seen.p, 2 * kU13Plane) != hipSuccess) {
+        for (flx_dbuf *b : {&tb.text, &tb.seed, &tb.seen}) {
+            if (b->p) (void)hipFree(b->p);
+            b->p = nullptr;
+        }
+        (void)hipGetLastError();
+        return FLX_OK;
+    }
+    FLX_HIP(ctx, hipMemsetAsync(tb.text.p, 0, tb.n_alloc * 8, st));
+    // padding: no window may start or end there
+    std::vector<uint32_t> pad(2 * kBackPad);
+    for (size_t i = 0; i < pad.size(); i += 2) { pad[i] = 0; pad[i + 1] = 0xffffu; }
+    FLX_HIP(ctx, hipMemcpyAsync(tb.words(), pad.data(), 2 * kLocusPad * 4, hipMemcpyHostToDevice, st));
+    FLX_HIP(ctx, hipMemcpyAsync(tb.words() + 2 * (kLocusPad + tb.n_words), pad.data(), pad.size() * 4, hipMemcpyHostToDevice, st));
+    FLX_HIP(ctx, hipMemsetAsync(tb.seed.p, 0xff, slots * 4, st));
+    FLX_HIP(ctx, hipMemsetAsync(tb.seen.p, 0, 2 * kU13Plane, st));
+    return FLX_OK;
+}
+
+// The bases and piece starts are queued: the bits behind n_text, U13 in two passes and the seeds, all from the text itself.  Ends the
+// form's timing bracket, waits, and hands text and seed table over to the caller (`loc` describes them).
+int text_finish(flx_ctx *ctx, TextBuild &tb, flx_time_scope &timed, uint32_t **text_out, uint32_t **seed_out, flx_locus *loc) {
+    hipStream_t st = ctx->stream;
+    uint32_t *text = tb.words(), *seed = tb.seed.as<uint32_t>();
+    // the last word's bases behind the text must not look like the start of anything: a piece "starts" at n_text
+    if (tb.n_text % 16)
+        hipLaunchKernelGGL(k_set_word_bits, dim3(1), dim3(1), 0, st, text + 2 * (kLocusPad + tb.n_words - 1) + 1, 0xffffu & ~((1u << (tb.n_text % 16)) - 1u));
+    uint32_t *seen1 = tb.seen.as<uint32_t>(), *seen2 = seen1 + kU13Plane / 4;
+    const unsigned blocks = (unsigned)((tb.n_text + 255) / 256);
+    const uint32_t mask = (uint32_t)((1ull << tb.bits) - 1);
+    hipLaunchKernelGGL(k_text_u13<0>, dim3(blocks), dim3(256), 0, st, text, tb.n_text, seen1, seen2);
+    hipLaunchKernelGGL(k_text_u13<1>, dim3(blocks), dim3(256), 0, st, text, tb.n_text, seen1, seen2);
+    hipLaunchKernelGGL(k_text_seed, dim3(blocks), dim3(256), 0, st, (const uint2 *)text, tb.n_text, seed, mask, 32 - tb.bits);
+    timed.end();
+    FLX_HIP(ctx, hipGetLastError());
+    FLX_HIP(ctx, hipStreamSynchronize(st));
+    loc->text = (const uint2 *)text;
+    loc->n_alloc = (uint32_t)tb.n_alloc;
+    loc->n_text = tb.n_text;
+    loc->seed = seed;
+    loc->seed_mask = mask;
+    loc->seed_shift = 32 - tb.bits;
+    *text_out = text;
+    *seed_out = seed;
+    tb.text.p = tb.seed.p = nullptr;
+    return FLX_OK;
+}
+
 }  // namespace
+
+// The assembly form (kmerset.h): for every sequence its forward strand, then its reverse strand.
+int flx_build_assembly_text(flx_ctx *ctx, const flx_seq_batch *batches, size_t n_batches, uint32_t **text_out, uint32_t **seed_out, flx_locus *loc) {
+    *text_out = nullptr;
+    *seed_out = nullptr;
+    uint64_t n_text = 0, n_windows = 0;
+    for (size_t b = 0; b < n_batches; ++b) {
+        n_text += 2 * (batches[b].n_pos + 15 * batches[b].n_seqs);
+        n_windows += 2 * batches[b].n_pos;
+    }
+    if (n_windows == 0 || n_text > (1ull << 28)) return FLX_OK;
+    TextBuild tb;
+    FLX_CHECK(text_alloc(ctx, n_text, n_windows, tb));
+    if (!tb.text.p) return FLX_OK;
+    flx_time_scope timed(ctx, "flx_kmerset_locus_build");
+    uint64_t text_base = 0;
+    for (size_t b = 0; b < n_batches; ++b) {
+        const uint64_t n_bases = batches[b].n_pos + 15 * batches[b].n_seqs;
+        if (n_bases)
+            hipLaunchKernelGGL(k_locus_text, dim3((unsigned)((n_bases + 255) / 256)), dim3(256), 0, ctx->stream, batches[b].bases, batches[b].offsets,
+                               batches[b].pos_base, batches[b].n_seqs, batches[b].n_pos, text_base, tb.words());
+        text_base += 2 * n_bases;
+    }
+    return text_finish(ctx, tb, timed, text_out, seed_out, loc);
+}
 
 // Order 24 (see the file header).  *text_out stays nullptr when this form cannot be built (no sequences, too many, no memory):
 // the caller then takes the order-16 form below.
@@ -437,7 +500,7 @@ static int build_path_text_k24(flx_ctx *ctx, const uint32_t *present, uint64_t n
         (void)hipGetLastError();
         return FLX_OK;
     }
-    flx_time_begin(ctx, "flx_kmerset_locus_build");
+    flx_time_scope timed(ctx, "flx_kmerset_locus_build");
     uint64_t done = 0;
     for (size_t b = 0; b < n_batches; ++b) {
         if (!batches[b].n_pos) continue;
@@ -454,39 +517,20 @@ static int build_path_text_k24(flx_ctx *ctx, const uint32_t *present, uint64_t n
     uint32_t m = 0;
     FLX_HIP(ctx, hipMemcpyAsync(&m, at.as<uint32_t>() + nk, 4, hipMemcpyDeviceToHost, st));
     FLX_HIP(ctx, hipStreamSynchronize(st));
-    if (m == 0 || m > (1u << 27)) {
-        flx_time_end(ctx);
-        return FLX_OK;
-    }
+    if (m == 0 || m > (1u << 27)) return FLX_OK;
     uint64_t *edges = sk == k0.as<uint64_t>() ? k1.as<uint64_t>() : k0.as<uint64_t>();  // the buffer the sort did not end in
     hipLaunchKernelGGL(k24_compact, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, nk, sk, flag.as<uint32_t>(), at.as<uint32_t>(), edges);
     const uint32_t nb = (m + 255) / 256;
-    // paths (the same jumps as at order 16)
-    flx_dbuf d_link0, d_link1, d_dist0, d_dist1, d_len, d_bases, d_off, d_cov, d_cnt, d_pre, d_left, ws2;
+    PathSection ps;
+    flx_dbuf d_cov, d_cnt, d_pre, d_left, ws2;
     const uint64_t n_blocks = 1ull << 24;
     const size_t ws2_bytes = std::max(flx_radix_sort_workspace(n_blocks + 1), flx_radix_sort_workspace((uint64_t)m + 1));
-    if (!alloc(d_link0, (size_t)m * 4) || !alloc(d_link1, (size_t)m * 4) || !alloc(d_dist0, (size_t)m * 4) || !alloc(d_dist1, (size_t)m * 4) || !alloc(d_len, (size_t)m * 4) ||
-        !alloc(d_bases, ((size_t)m + 1) * 8) || !alloc(d_off, ((size_t)m + 1) * 8) || !alloc(d_cov, (size_t)1 << 29) || !alloc(d_cnt, (n_blocks + 1) * 8) ||
-        !alloc(d_pre, (n_blocks + 1) * 8) || !alloc(ws2, ws2_bytes)) {
+    if (!ps.alloc(m) || !alloc(d_cov, (size_t)1 << 29) || !alloc(d_cnt, (n_blocks + 1) * 8) || !alloc(d_pre, (n_blocks + 1) * 8) || !alloc(ws2, ws2_bytes)) {
         (void)hipGetLastError();
-        flx_time_end(ctx);
         return FLX_OK;
     }
-    hipLaunchKernelGGL(k24_pred, dim3(nb), dim3(256), 0, st, edges, m, d_link0.as<uint32_t>(), d_dist0.as<uint32_t>());
-    uint32_t *link = d_link0.as<uint32_t>(), *link2 = d_link1.as<uint32_t>(), *dist = d_dist0.as<uint32_t>(), *dist2 = d_dist1.as<uint32_t>();
-    int rounds = 1;
-    while ((1ull << rounds) < (uint64_t)m + 1) ++rounds;
-    for (int r = 0; r < rounds; ++r) {
-        hipLaunchKernelGGL(k_pt_jump, dim3(nb), dim3(256), 0, st, m, link, dist, link2, dist2);
-        std::swap(link, link2);
-        std::swap(dist, dist2);
-    }
-    FLX_HIP(ctx, hipMemsetAsync(d_len.p, 0, (size_t)m * 4, st));
-    hipLaunchKernelGGL(k_pt_heads, dim3(nb), dim3(256), 0, st, m, link, dist, d_len.as<uint32_t>());
-    hipLaunchKernelGGL(k_pt_lengths, dim3(nb), dim3(256), 0, st, m, link, dist, d_len.as<uint32_t>());
-    FLX_HIP(ctx, hipMemsetAsync(d_bases.p, 0, ((size_t)m + 1) * 8, st));
-    hipLaunchKernelGGL(k24_piece_bases, dim3(nb), dim3(256), 0, st, m, link, d_len.as<uint32_t>(), d_bases.as<int64_t>());
-    FLX_CHECK(flx_exclusive_scan_i64(ctx, (uint64_t)m + 1, d_bases.as<int64_t>(), d_off.as<int64_t>(), ws2.p, ws2_bytes));
+    hipLaunchKernelGGL(k24_pred, dim3(nb), dim3(256), 0, st, edges, m, ps.link0.as<uint32_t>(), ps.dist0.as<uint32_t>());
+    FLX_CHECK(paths_from_links(ctx, ps, m, 23, ws2.p, ws2_bytes));
     // members no 24-mer holds
     FLX_HIP(ctx, hipMemsetAsync(d_cov.p, 0, (size_t)1 << 29, st));
     hipLaunchKernelGGL(k24_cover, dim3(nb), dim3(256), 0, st, m, edges, d_cov.as<uint32_t>());
@@ -495,71 +539,28 @@ static int build_path_text_k24(flx_ctx *ctx, const uint32_t *present, uint64_t n
     hipLaunchKernelGGL(k_pt_count256, dim3((unsigned)(n_blocks / 256)), dim3(256), 0, st, d_cov.as<uint32_t>(), d_cnt.as<int64_t>());
     FLX_CHECK(flx_exclusive_scan_i64(ctx, n_blocks + 1, d_cnt.as<int64_t>(), d_pre.as<int64_t>(), ws2.p, ws2_bytes));
     int64_t path_bases = 0, n_left = 0;
-    FLX_HIP(ctx, hipMemcpyAsync(&path_bases, d_off.as<int64_t>() + m, 8, hipMemcpyDeviceToHost, st));
+    FLX_HIP(ctx, hipMemcpyAsync(&path_bases, ps.off.as<int64_t>() + m, 8, hipMemcpyDeviceToHost, st));
     FLX_HIP(ctx, hipMemcpyAsync(&n_left, d_pre.as<int64_t>() + n_blocks, 8, hipMemcpyDeviceToHost, st));
     FLX_HIP(ctx, hipStreamSynchronize(st));
     const uint64_t n_text = (uint64_t)path_bases + 16ull * (uint64_t)n_left;
-    if (n_text == 0 || n_text > (1ull << 28) || (uint64_t)n_left > n_members) {
-        flx_time_end(ctx);
-        return FLX_OK;
-    }
+    if (n_text == 0 || n_text > (1ull << 28) || (uint64_t)n_left > n_members) return FLX_OK;
     if (n_left > 0 && !alloc(d_left, (size_t)n_left * 4)) {
         (void)hipGetLastError();
-        flx_time_end(ctx);
         return FLX_OK;
     }
-    const uint64_t n_words = (n_text + 15) / 16;
-    const uint64_t n_alloc = n_words + kLocusPad + 68;
-    int bits = 10;
-    while ((1ull << bits) < n_members * 5 / 2) ++bits;
-    const uint64_t slots = 1ull << bits;
-    uint32_t *text = nullptr, *seed = nullptr;
-    flx_dbuf seen;
-    const size_t plane = (size_t)1 << (26 - 3);
-    if (hipMalloc((void **)&text, n_alloc * 8) != hipSuccess || hipMalloc((void **)&seed, slots * 4) != hipSuccess || !alloc(seen, 2 * plane)) {
-        if (text) (void)hipFree(text);
-        if (seed) (void)hipFree(seed);
-        (void)hipGetLastError();
-        flx_time_end(ctx);
-        return FLX_OK;
-    }
-    FLX_HIP(ctx, hipMemsetAsync(text, 0, n_alloc * 8, st));
-    std::vector<uint32_t> pad_front(2 * kLocusPad), pad_back(2 * 68);
-    for (size_t i = 0; i < pad_front.size(); i += 2) { pad_front[i] = 0; pad_front[i + 1] = 0xffffu; }
-    for (size_t i = 0; i < pad_back.size(); i += 2) { pad_back[i] = 0; pad_back[i + 1] = 0xffffu; }
-    FLX_HIP(ctx, hipMemcpyAsync(text, pad_front.data(), pad_front.size() * 4, hipMemcpyHostToDevice, st));
-    FLX_HIP(ctx, hipMemcpyAsync(text + 2 * (kLocusPad + n_words), pad_back.data(), pad_back.size() * 4, hipMemcpyHostToDevice, st));
-    FLX_HIP(ctx, hipMemsetAsync(seed, 0xff, slots * 4, st));
-    FLX_HIP(ctx, hipMemsetAsync(seen.p, 0, 2 * plane, st));
-    hipLaunchKernelGGL(k24_text, dim3(nb), dim3(256), 0, st, m, edges, link, dist, d_off.as<int64_t>(), text);
+    TextBuild tb;
+    FLX_CHECK(text_alloc(ctx, n_text, n_members, tb));
+    if (!tb.text.p) return FLX_OK;
+    hipLaunchKernelGGL((k_pt_text<uint64_t, 24>), dim3(nb), dim3(256), 0, st, m, edges, ps.link, ps.dist, ps.off.as<int64_t>(), tb.words());
     if (n_left > 0) {
         hipLaunchKernelGGL(k_pt_members, dim3((unsigned)(n_blocks / 256)), dim3(256), 0, st, d_cov.as<uint32_t>(), d_pre.as<int64_t>(), d_left.as<uint32_t>());
-        hipLaunchKernelGGL(k24_text_leftover, dim3((unsigned)((n_left + 255) / 256)), dim3(256), 0, st, (uint32_t)n_left, d_left.as<uint32_t>(), (uint64_t)path_bases, text);
+        hipLaunchKernelGGL(k24_text_leftover, dim3((unsigned)((n_left + 255) / 256)), dim3(256), 0, st, (uint32_t)n_left, d_left.as<uint32_t>(), (uint64_t)path_bases, tb.words());
     }
-    if (n_text % 16)
-        hipLaunchKernelGGL(k_pt_set_word_bits, dim3(1), dim3(1), 0, st, text + 2 * (kLocusPad + n_words - 1) + 1, 0xffffu & ~((1u << (n_text % 16)) - 1u));
-    uint32_t *seen1 = seen.as<uint32_t>(), *seen2 = seen1 + plane / 4;
-    const unsigned tb = (unsigned)((n_text + 255) / 256);
-    hipLaunchKernelGGL(k_text_u13<0>, dim3(tb), dim3(256), 0, st, text, n_text, seen1, seen2);
-    hipLaunchKernelGGL(k_text_u13<1>, dim3(tb), dim3(256), 0, st, text, n_text, seen1, seen2);
-    hipLaunchKernelGGL(k_text_seed, dim3(tb), dim3(256), 0, st, (const uint2 *)text, n_text, seed, (uint32_t)(slots - 1), 32 - bits);
-    flx_time_end(ctx);
-    FLX_HIP(ctx, hipGetLastError());
-    FLX_HIP(ctx, hipStreamSynchronize(st));
-    loc->text = (const uint2 *)text;
-    loc->n_alloc = (uint32_t)n_alloc;
-    loc->n_text = n_text;
-    loc->seed = seed;
-    loc->seed_mask = (uint32_t)(slots - 1);
-    loc->seed_shift = 32 - bits;
-    *text_out = text;
-    *seed_out = seed;
-    return FLX_OK;
+    return text_finish(ctx, tb, timed, text_out, seed_out, loc);
 }
 
-// Builds text + seed table for the members of `present` (n_members of them; exact15 is their pair table).  On success the caller
-// owns *text_out / *seed_out (hipFree) and `loc` describes them; returns FLX_OK with *text_out == nullptr when the set is too
-// large for it or the device memory is not there (the scoring path works without).
+// The path forms (kmerset.h) for the members of `present` (n_members of them; exact15 is their pair table): order 24 first, then —
+// here — order 16.
 int flx_build_path_text(flx_ctx *ctx, const uint32_t *present, const uint8_t *exact15, uint64_t n_members, const flx_seq_batch *batches,
                         size_t n_batches, uint32_t **text_out, uint32_t **seed_out, flx_locus *loc) {
     *text_out = nullptr;
@@ -576,18 +577,17 @@ int flx_build_path_text(flx_ctx *ctx, const uint32_t *present, const uint8_t *ex
     const uint32_t n = (uint32_t)n_members;
     const uint32_t nb = (n + 255) / 256;
     const uint64_t n_blocks = 1ull << 24;
-    flx_dbuf d_cnt, d_pre, d_members, d_link0, d_link1, d_dist0, d_dist1, d_len, d_bases, d_off, d_ws, d_wkeys, d_wvals;
+    PathSection ps;
+    flx_dbuf d_cnt, d_pre, d_members, d_ws, d_wkeys, d_wvals;
     const uint32_t wit_slots = 1u << 22;  // (a 5 Mbp genome has ~1e5 branching 15-mers; what does not fit is paired by order)
     const size_t ws_bytes = std::max(flx_radix_sort_workspace(n_blocks + 1), flx_radix_sort_workspace((uint64_t)n + 1));
     auto alloc = [&](flx_dbuf &b, size_t bytes) { return hipMalloc(&b.p, bytes) == hipSuccess; };
-    if (!alloc(d_cnt, (n_blocks + 1) * 8) || !alloc(d_pre, (n_blocks + 1) * 8) || !alloc(d_members, (size_t)n * 4) || !alloc(d_link0, (size_t)n * 4) ||
-        !alloc(d_link1, (size_t)n * 4) || !alloc(d_dist0, (size_t)n * 4) || !alloc(d_dist1, (size_t)n * 4) || !alloc(d_len, (size_t)n * 4) ||
-        !alloc(d_bases, ((size_t)n + 1) * 8) || !alloc(d_off, ((size_t)n + 1) * 8) || !alloc(d_ws, ws_bytes) || !alloc(d_wkeys, (size_t)wit_slots * 4) ||
-        !alloc(d_wvals, (size_t)wit_slots * 4)) {
+    if (!alloc(d_cnt, (n_blocks + 1) * 8) || !alloc(d_pre, (n_blocks + 1) * 8) || !alloc(d_members, (size_t)n * 4) || !ps.alloc(n) || !alloc(d_ws, ws_bytes) ||
+        !alloc(d_wkeys, (size_t)wit_slots * 4) || !alloc(d_wvals, (size_t)wit_slots * 4)) {
         (void)hipGetLastError();
         return FLX_OK;
     }
-    flx_time_begin(ctx, "flx_kmerset_locus_build");
+    flx_time_scope timed(ctx, "flx_kmerset_locus_build");
     FLX_HIP(ctx, hipMemsetAsync(d_cnt.p, 0, (n_blocks + 1) * 8, st));
     hipLaunchKernelGGL(k_pt_count256, dim3((unsigned)(n_blocks / 256)), dim3(256), 0, st, present, d_cnt.as<int64_t>());
     FLX_CHECK(flx_exclusive_scan_i64(ctx, n_blocks + 1, d_cnt.as<int64_t>(), d_pre.as<int64_t>(), d_ws.p, ws_bytes));
@@ -602,70 +602,16 @@ int flx_build_path_text(flx_ctx *ctx, const uint32_t *present, const uint8_t *ex
         if (batches[b].n_pos)
             hipLaunchKernelGGL(k_pt_witness, dim3((unsigned)((batches[b].n_pos + 255) / 256)), dim3(256), 0, st, batches[b].bases, batches[b].offsets,
                                batches[b].pos_base, batches[b].n_seqs, batches[b].n_pos, exact15, wit);
-    hipLaunchKernelGGL(k_pt_pred, dim3(nb), dim3(256), 0, st, present, d_pre.as<int64_t>(), exact15, d_members.as<uint32_t>(), n, wit, d_link0.as<uint32_t>(),
-                       d_dist0.as<uint32_t>());
-    uint32_t *link = d_link0.as<uint32_t>(), *link2 = d_link1.as<uint32_t>(), *dist = d_dist0.as<uint32_t>(), *dist2 = d_dist1.as<uint32_t>();
-    int rounds = 1;
-    while ((1ull << rounds) < (uint64_t)n + 1) ++rounds;
-    for (int r = 0; r < rounds; ++r) {
-        hipLaunchKernelGGL(k_pt_jump, dim3(nb), dim3(256), 0, st, n, link, dist, link2, dist2);
-        std::swap(link, link2);
-        std::swap(dist, dist2);
-    }
-    FLX_HIP(ctx, hipMemsetAsync(d_len.p, 0, (size_t)n * 4, st));
-    hipLaunchKernelGGL(k_pt_heads, dim3(nb), dim3(256), 0, st, n, link, dist, d_len.as<uint32_t>());
-    hipLaunchKernelGGL(k_pt_lengths, dim3(nb), dim3(256), 0, st, n, link, dist, d_len.as<uint32_t>());
-    FLX_HIP(ctx, hipMemsetAsync(d_bases.p, 0, ((size_t)n + 1) * 8, st));
-    hipLaunchKernelGGL(k_pt_piece_bases, dim3(nb), dim3(256), 0, st, n, link, d_len.as<uint32_t>(), d_bases.as<int64_t>());
-    FLX_CHECK(flx_exclusive_scan_i64(ctx, (uint64_t)n + 1, d_bases.as<int64_t>(), d_off.as<int64_t>(), d_ws.p, ws_bytes));
+    hipLaunchKernelGGL(k_pt_pred, dim3(nb), dim3(256), 0, st, present, d_pre.as<int64_t>(), exact15, d_members.as<uint32_t>(), n, wit, ps.link0.as<uint32_t>(),
+                       ps.dist0.as<uint32_t>());
+    FLX_CHECK(paths_from_links(ctx, ps, n, 15, d_ws.p, ws_bytes));
     int64_t n_text = 0;
-    FLX_HIP(ctx, hipMemcpyAsync(&n_text, d_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    FLX_HIP(ctx, hipMemcpyAsync(&n_text, ps.off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
     FLX_HIP(ctx, hipStreamSynchronize(st));
-    if (n_text <= 0 || (uint64_t)n_text > (1ull << 28)) {
-        flx_time_end(ctx);
-        return FLX_OK;
-    }
-    const uint64_t n_words = ((uint64_t)n_text + 15) / 16;
-    const uint64_t n_alloc = n_words + kLocusPad + 68;
-    int bits = 10;
-    while ((1ull << bits) < (uint64_t)n * 5 / 2) ++bits;
-    const uint64_t slots = 1ull << bits;
-    uint32_t *text = nullptr, *seed = nullptr;
-    flx_dbuf seen;
-    const size_t plane = (size_t)1 << (26 - 3);
-    if (hipMalloc((void **)&text, n_alloc * 8) != hipSuccess || hipMalloc((void **)&seed, slots * 4) != hipSuccess || !alloc(seen, 2 * plane)) {
-        if (text) (void)hipFree(text);
-        if (seed) (void)hipFree(seed);
-        (void)hipGetLastError();
-        flx_time_end(ctx);
-        return FLX_OK;
-    }
-    FLX_HIP(ctx, hipMemsetAsync(text, 0, n_alloc * 8, st));
-    std::vector<uint32_t> pad_front(2 * kLocusPad), pad_back(2 * 68);
-    for (size_t i = 0; i < pad_front.size(); i += 2) { pad_front[i] = 0; pad_front[i + 1] = 0xffffu; }
-    for (size_t i = 0; i < pad_back.size(); i += 2) { pad_back[i] = 0; pad_back[i + 1] = 0xffffu; }
-    FLX_HIP(ctx, hipMemcpyAsync(text, pad_front.data(), pad_front.size() * 4, hipMemcpyHostToDevice, st));
-    FLX_HIP(ctx, hipMemcpyAsync(text + 2 * (kLocusPad + n_words), pad_back.data(), pad_back.size() * 4, hipMemcpyHostToDevice, st));
-    FLX_HIP(ctx, hipMemsetAsync(seed, 0xff, slots * 4, st));
-    FLX_HIP(ctx, hipMemsetAsync(seen.p, 0, 2 * plane, st));
-    hipLaunchKernelGGL(k_pt_text, dim3(nb), dim3(256), 0, st, n, d_members.as<uint32_t>(), link, dist, d_off.as<int64_t>(), text);
-    if (n_text % 16)
-        hipLaunchKernelGGL(k_pt_set_word_bits, dim3(1), dim3(1), 0, st, text + 2 * (kLocusPad + n_words - 1) + 1, 0xffffu & ~((1u << (n_text % 16)) - 1u));
-    uint32_t *seen1 = seen.as<uint32_t>(), *seen2 = seen1 + plane / 4;
-    hipLaunchKernelGGL(k_pt_u13<0>, dim3(nb), dim3(256), 0, st, n, d_members.as<uint32_t>(), link, dist, d_len.as<uint32_t>(), d_off.as<int64_t>(), text, seen1, seen2);
-    hipLaunchKernelGGL(k_pt_u13<1>, dim3(nb), dim3(256), 0, st, n, d_members.as<uint32_t>(), link, dist, d_len.as<uint32_t>(), d_off.as<int64_t>(), text, seen1, seen2);
-    hipLaunchKernelGGL(k_pt_seed, dim3(nb), dim3(256), 0, st, n, d_members.as<uint32_t>(), link, dist, d_off.as<int64_t>(), (const uint2 *)text, seed,
-                       (uint32_t)(slots - 1), 32 - bits);
-    flx_time_end(ctx);
-    FLX_HIP(ctx, hipGetLastError());
-    FLX_HIP(ctx, hipStreamSynchronize(st));
-    loc->text = (const uint2 *)text;
-    loc->n_alloc = (uint32_t)n_alloc;
-    loc->n_text = (uint64_t)n_text;
-    loc->seed = seed;
-    loc->seed_mask = (uint32_t)(slots - 1);
-    loc->seed_shift = 32 - bits;
-    *text_out = text;
-    *seed_out = seed;
-    return FLX_OK;
+    if (n_text <= 0 || (uint64_t)n_text > (1ull << 28)) return FLX_OK;
+    TextBuild tb;
+    FLX_CHECK(text_alloc(ctx, (uint64_t)n_text, n, tb));
+    if (!tb.text.p) return FLX_OK;
+    hipLaunchKernelGGL((k_pt_text<uint32_t, 16>), dim3(nb), dim3(256), 0, st, n, d_members.as<uint32_t>(), ps.link, ps.dist, ps.off.as<int64_t>(), tb.words());
+    return text_finish(ctx, tb, timed, text_out, seed_out, loc);
 }

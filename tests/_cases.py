@@ -143,6 +143,31 @@ def short_read_pairs(contigs, seed=17, depth=12, rl=100):
     return r1, r2
 
 
+def path_text_case():
+    """Short reads whose set becomes a text by cutting the members' de Bruijn graph into paths (csrc/pathtext.hip): a 16 kb genome
+    with a segment that occurs three times (once reverse-complemented: branching 15-mers), tandem repeats (AC.., a 23-mer unit:
+    cycles) and a homopolymer (a self-loop).  `files`: 100-mers at every 7th position, alternately as they are and
+    reverse-complemented, split over two files — every inner 16-mer is seen about a dozen times; `tiny`: sequences below 24 bases,
+    whose members mostly lie in no 24-mer at all; `asm`: a part of the genome to put underneath as an assembly.  `rng` and `rnd`
+    go on where the genome's draws ended (for the reads of a test)."""
+    rng = np.random.RandomState(808)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+    def rnd(n):
+        return acgt[rng.randint(0, 4, n)].tobytes()
+
+    seg = rnd(300)
+    unit23 = rnd(23)
+    genome = (rnd(3000) + seg + rnd(2500) + seg + rnd(1200) + b"AC" * 120 + rnd(800) + b"A" * 90 + rnd(700) + unit23 * 12 + rnd(1500) +
+              revcomp(seg) + rnd(2000))
+    files = [[], []]
+    for k, at in enumerate(range(0, len(genome) - 100, 7)):
+        piece = genome[at:at + 100]
+        files[k % 2].append(piece if k % 3 else revcomp(piece))
+    tiny = [genome[a:a + 20] for a in range(0, 4000, 3)] * 2
+    return {"genome": genome, "seg": seg, "unit23": unit23, "files": files, "tiny": tiny, "asm": genome[:6000], "rng": rng, "rnd": rnd}
+
+
 def fastq_bytes(seqs, prefix="sr", qchar=b"I"):
     out = []
     for i, s in enumerate(seqs):

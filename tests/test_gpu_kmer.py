@@ -680,22 +680,9 @@ def test_path_text_of_short_read_sets_vs_oracle(ctx, be, monkeypatch):
     entering and leaving members is wrong for some passages and the diagonal must be found again inside the span), on cycles
     (tandem repeats: AC.., a 23-mer unit) and on the self-loop of a homopolymer.  Reads through all of that, every field against
     the oracle and against the kernel without the text and round 2's kernel; assembly + short reads in one set as well."""
-    rng = np.random.RandomState(808)
-    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
-
-    def rnd(n):
-        return acgt[rng.randint(0, 4, n)].tobytes()
-
-    seg = rnd(300)
-    unit23 = rnd(23)
-    genome = (rnd(3000) + seg + rnd(2500) + seg + rnd(1200) + b"AC" * 120 + rnd(800) + b"A" * 90 + rnd(700) + unit23 * 12 + rnd(1500) +
-              _cases.revcomp(seg) + rnd(2000))
-    # 100-mers at every 7th position, alternately as they are and reverse-complemented, split over two files: every inner 16-mer
-    # is seen about a dozen times
-    files = [[], []]
-    for k, at in enumerate(range(0, len(genome) - 100, 7)):
-        piece = genome[at:at + 100]
-        files[k % 2].append(piece if k % 3 else _cases.revcomp(piece))
+    case = _cases.path_text_case()  # (shared with tests/test_gpu_locus_text.py, which looks at the texts themselves)
+    rng, rnd, acgt = case["rng"], case["rnd"], np.frombuffer(b"ACGT", dtype=np.uint8)
+    seg, unit23, genome, files = case["seg"], case["unit23"], case["genome"], case["files"]
     orc = _oracle.KmerSet(); orc.add_short_reads(files[0]); orc.add_short_reads(files[1])
     ks = be.kmers(short_files=files)
     assert len(ks) == len(orc) and len(ks) > 20000
@@ -737,15 +724,15 @@ def test_path_text_of_short_read_sets_vs_oracle(ctx, be, monkeypatch):
             return [bits(x) for x in v]
         return v
 
-    both = be.kmers(assembly=[genome[:6000]], short_files=files)
-    orc_both = _oracle.KmerSet(); orc_both.add_assembly([genome[:6000]]); orc_both.add_short_reads(files[0]); orc_both.add_short_reads(files[1])
+    both = be.kmers(assembly=[case["asm"]], short_files=files)
+    orc_both = _oracle.KmerSet(); orc_both.add_assembly([case["asm"]]); orc_both.add_short_reads(files[0]); orc_both.add_short_reads(files[1])
     assert len(both) == len(orc_both)
     # the text at order 24 (default: paths of the sequences' 24-mers) and at order 16 (paths of the members themselves)
     monkeypatch.setenv("FLX_KMER_TEXT_ORDER", "16")
     ks16 = be.kmers(short_files=files)
     monkeypatch.delenv("FLX_KMER_TEXT_ORDER")
     # short sequences (below 24 bases) and a set whose members mostly lie in no 24-mer at all
-    tiny = [genome[a:a + 20] for a in range(0, 4000, 3)] * 2
+    tiny = case["tiny"]
     orc_tiny = _oracle.KmerSet(); orc_tiny.add_short_reads(tiny)
     ks_tiny = be.kmers(short_files=[tiny])
     assert len(ks_tiny) == len(orc_tiny) > 1000
