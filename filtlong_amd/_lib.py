@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "flx_bgzf_bound", "flx_bgzf_compress_dev", "flx_bgzf_create", "flx_bgzf_compress", "flx_bgzf_destroy",
     "flx_bgzf_index", "flx_bgzf_inflate_dev", "flx_bgzf_inflate",
     "flx_bam_index", "flx_bam_to_fastq_dev", "flx_bam_to_fastq",
+    "flx_bam_header", "flx_bam_from_fastq_bound", "flx_bam_from_fastq_dev", "flx_bgzf_bam_from_fastq",
     "flx_summary_q_edges", "flx_summary_dev", "flx_summary",
 ]
 
@@ -198,6 +199,10 @@ def load():
     L.flx_bam_index.argtypes = [vp, u64, u64, vp, C.POINTER(u64), C.POINTER(C.c_int)]
     L.flx_bam_to_fastq_dev.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.flx_bam_to_fastq.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.flx_bam_header.argtypes = [vp, u64, C.POINTER(u64)]
+    L.flx_bam_from_fastq_bound.argtypes = [u64, u64, C.POINTER(u64)]
+    L.flx_bam_from_fastq_dev.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64)]
+    L.flx_bgzf_bam_from_fastq.argtypes = [vp, vp, u64, vp, u64, i32, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.flx_summary_q_edges.argtypes = [vp]
     L.flx_summary_dev.argtypes = [vp, u64, vp, vp, vp, vp, i32, C.POINTER(Summary)]
     L.flx_summary.argtypes = [vp, u64, vp, vp, vp, vp, i32, C.POINTER(Summary)]

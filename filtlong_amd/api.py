@@ -411,6 +411,19 @@ class Context:
             raise e
         return out_len.value, skipped.value, first_bad.value
 
+    def bam_from_fastq_dev(self, d_text, n, d_rec_off, n_records, d_out, out_cap, d_out_off):
+        """flx_bam_from_fastq_dev: the strict FASTQ / FASTA records [d_rec_off[k], d_rec_off[k+1]) of the n device bytes at d_text as
+        unaligned BAM records into d_out (device, out_cap bytes); d_out_off (device, uint64, n_records + 1) gets their offsets ->
+        (out_len, first_bad).  FLX_ERR_CAPACITY raises FlxError with the length needed in its `needed`."""
+        out_len, first_bad = C.c_uint64(), C.c_uint64()
+        rc = self.L.flx_bam_from_fastq_dev(self.h, d_text, int(n), d_rec_off, int(n_records), d_out, int(out_cap), d_out_off,
+                                           C.byref(out_len), C.byref(first_bad))
+        if rc:
+            e = FlxError(rc, self.L.flx_last_error(self.h).decode())
+            e.needed = out_len.value
+            raise e
+        return out_len.value, first_bad.value
+
     # ---- read summary (include/filtlong_hip.h, flx_summary*) ------------------------------------------------------
     def summary(self, lengths, mean_q=None, window_q=None, mask=None, global_=False):
         """flx_summary over host arrays: the struct's fields as a dictionary (integers and lists of integers).  `mask`:
@@ -525,6 +538,73 @@ def bam_to_fastq(ctx, data, piece_bytes=0, out_cap=None, with_offsets=False):
         raise ValueError("bam_to_fastq: record %d is malformed" % first_bad.value)
     text = out[:out_len.value].tobytes()
     return (text, out_off, skipped.value) if with_offsets else text
+
+
+def bam_header():
+    """flx_bam_header: the header bytes of a BAM file written from text."""
+    n = C.c_uint64()
+    L = _lib.load()
+    L.flx_bam_header(None, 0, C.byref(n))
+    out = np.zeros(n.value, dtype=np.uint8)
+    rc = L.flx_bam_header(out.ctypes.data, len(out), C.byref(n))
+    if rc:
+        raise FlxError(rc, "flx_bam_header")
+    return out.tobytes()
+
+
+def bam_from_fastq_bound(n_text, n_records):
+    """flx_bam_from_fastq_bound: the most BAM bytes n_records records in n_text bytes of text can take."""
+    b = C.c_uint64()
+    rc = _lib.load().flx_bam_from_fastq_bound(int(n_text), int(n_records), C.byref(b))
+    if rc:
+        raise FlxError(rc, "flx_bam_from_fastq_bound")
+    return b.value
+
+
+def _text_and_offsets(text, rec_off):
+    src = np.frombuffer(bytes(text), dtype=np.uint8)
+    off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+    if len(off) < 1:
+        raise ValueError("rec_off needs n_records + 1 entries")
+    return src, off
+
+
+def bam_from_fastq(ctx, text, rec_off, with_offsets=False):
+    """Strict FASTQ / FASTA record text (record k is text[rec_off[k]:rec_off[k+1]]) -> the BAM records, without a header, through
+    flx_bam_from_fastq_dev (device buffers from torch).  An invalid record raises ValueError.  with_offsets: -> (bytes, offsets)."""
+    import torch
+    src, off = _text_and_offsets(text, rec_off)
+    n = len(off) - 1
+    if n == 0:
+        return (b"", [0]) if with_offsets else b""
+    cap = bam_from_fastq_bound(len(src), n)
+    d_text = torch.from_numpy(src.copy()).to("cuda") if len(src) else torch.zeros(1, dtype=torch.uint8, device="cuda")
+    d_off = torch.from_numpy(off.view(np.int64).copy()).to("cuda")
+    d_out = torch.empty(cap + 16, dtype=torch.uint8, device="cuda")
+    d_oo = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    out_len, first_bad = ctx.bam_from_fastq_dev(d_text.data_ptr(), len(src), d_off.data_ptr(), n, d_out.data_ptr(), cap, d_oo.data_ptr())
+    if first_bad != n:
+        raise ValueError("bam_from_fastq: record %d is not valid" % first_bad)
+    data = d_out[:out_len].cpu().numpy().tobytes()
+    return (data, [int(x) for x in d_oo.cpu().numpy()]) if with_offsets else data
+
+
+def bgzf_bam_from_fastq(bgzf, text, rec_off, eof=True, out_cap=None):
+    """flx_bgzf_bam_from_fastq through a slot of the Bgzf object: strict record text in, BGZF-compressed BAM records (no header)
+    out -> bytes.  An invalid record raises ValueError."""
+    src, off = _text_and_offsets(text, rec_off)
+    n = len(off) - 1
+    cap = bgzf_bound(bam_from_fastq_bound(len(src), n), eof) + 31 * n if out_cap is None else int(out_cap)
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    got, first_bad = C.c_uint64(), C.c_uint64()
+    rc = bgzf.ctx.L.flx_bgzf_bam_from_fastq(bgzf.h, src.ctypes.data if len(src) else None, len(src), off.ctypes.data, n,
+                                            BGZF_EOF if eof else 0, out.ctypes.data, cap, C.byref(got), C.byref(first_bad))
+    if rc:
+        raise FlxError(rc, "flx_bgzf_bam_from_fastq")
+    if first_bad.value != n:
+        raise ValueError("bgzf_bam_from_fastq: record %d is not valid" % first_bad.value)
+    return out[:got.value].tobytes()
 
 
 class Bgzf:

@@ -35,6 +35,7 @@ struct Args {
     bool verbose = false;
     int gpus = 1;  // not a reference flag: --gpus N scores on N GPUs of this node (one process per GPU)
     bool gzip = false;  // not a reference flag: --gzip writes stdout as BGZF, compressed on the GPU
+    bool bam = false;   // not a reference flag: --bam writes stdout as BGZF-compressed unaligned BAM, packed and compressed on the GPU
     bool report_set = false; std::string report;  // not a reference flag: --report FILE receives a JSON summary of the reads before and after
 };
 enum ParsingResult { GOOD, BAD, HELP, VERSION };
@@ -107,7 +108,7 @@ static long long read_ll(const std::string &name, const std::string &value, long
 // terminal on STDOUT (TIOCGWINSZ; indent 1 / 2 / 3 / 4 for widths up to 60 / 80 / 120 / beyond).  When stdout is no terminal the
 // reference reads the width out of an untouched `struct winsize` — 0 in practice: the description comes out one word per line and,
 // the other widths being unsigned differences that wrap around, nothing else is wrapped at all.  Both cases are restated here.
-// (--gpus, --gzip and --report, this binary's flags of its own, are documented in README.md: the menu is the reference's.)
+// (--gpus, --gzip, --bam and --report, this binary's flags of its own, are documented in README.md: the menu is the reference's.)
 static std::vector<std::string> help_wrap(const std::string &in, size_t width, size_t first = 0) {  // src/args.h:94-149
     std::vector<std::string> out;
     size_t cur = first ? first : width, linesize = 0;
@@ -270,6 +271,7 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
             else if (flag == "window_size") a.window_size = read_ll("int", need("window_size"), a.window_size);
             else if (flag == "gpus") a.gpus = (int)read_ll("int", need("gpus"), a.gpus);
             else if (flag == "gzip") a.gzip = true;
+            else if (flag == "bam") a.bam = true;
             else if (flag == "report") { a.report = need("report"); a.report_set = true; }
             else throw ParseError("Error: flag could not be matched: " + flag);
         }
@@ -315,6 +317,7 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     a.window_size = (long long)(int32_t)(uint32_t)(unsigned long long)a.window_size;
     if (a.window_size <= 0) { std::cerr << "Error: the value for --window_size must be a positive integer\n"; return BAD; }
     if (a.gpus < 1 || a.gpus > 64) { std::cerr << "Error: the value for --gpus must be between 1 and 64\n"; return BAD; }
+    if (a.gzip && a.bam) { std::cerr << "Error: --gzip and --bam cannot be used together\n"; return BAD; }  // (BAM is BGZF already)
     return GOOD;
 }
 

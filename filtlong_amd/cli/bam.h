@@ -7,7 +7,8 @@
 //   FLX_CLI_GPU_BAM=1   through flx_bam_to_fastq (csrc/bam.hip); a device path that fails falls back to the host walk, silently;
 //   FLX_CLI_GPU_BAM=0   the same csrc/bam_record.h walked on the host threads over record ranges.  The same bytes either way.
 //   FLX_CLI_BAM_TIMING=1   one more stderr line: records, skipped records, `device` or `host`, milliseconds.
-// Memory is O(inflated file + text): a BAM input is never streamed.
+// Memory is O(inflated file + text): a BAM input is never streamed.  --bam without --trim / --split keeps the inflated file for
+// the whole run (Input::keep_bam): the output pass writes the kept reads' original records out of it (output.h).
 #pragma once
 #include <chrono>
 #include <functional>
@@ -48,7 +49,8 @@ static bool bam_detect(const unsigned char *file, size_t n) {
 }
 
 // The inflated file `data` (n bytes) as FASTQ text: false and a reason for a file that is truncated or malformed.
-static bool bam_to_text(const char *data, size_t n, std::unique_ptr<char[]> &text, size_t &text_len, std::string &reason) {
+static bool bam_to_text(const char *data, size_t n, std::unique_ptr<char[]> &text, size_t &text_len, std::string &reason, uint64_t *header_len,
+                        std::vector<uint64_t> *rec_at) {
     const auto t0 = std::chrono::steady_clock::now();
     const uint8_t *src = (const uint8_t *)data;
     uint64_t n_rec = 0, again = 0;
@@ -78,6 +80,15 @@ static bool bam_to_text(const char *data, size_t n, std::unique_ptr<char[]> &tex
         }
     }
     if (!device) parallel_for(parts, [&](size_t i) { bam::emit_records_host(src, rec_off.data(), first[i], first[i + 1], (uint8_t *)text.get() + at[i]); });
+    *header_len = rec_off[0];
+    if (rec_at) {  // (--bam, reads that go out whole: the record of every text record; one cache line per record, as above)
+        rec_at->clear();
+        rec_at->reserve((size_t)(n_rec - n_skipped));
+        for (uint64_t k = 0; k < n_rec; ++k) {
+            bam::Rec r;
+            if (bam::read_record(src, rec_off[k + 1], rec_off[k], r) == bam::REC_OK && bam::has_text(r)) rec_at->push_back(rec_off[k]);
+        }
+    }
     if (const char *e = getenv("FLX_CLI_BAM_TIMING"); e && e[0] == '1')
         fprintf(stderr, "[bam] %llu record(s), %llu skipped, %s, %.3f ms\n", (unsigned long long)n_rec, (unsigned long long)n_skipped,
                 device ? "device" : "host", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());

@@ -62,9 +62,12 @@ static void parallel_for(size_t n_parts, F &&body) {  // body(part) for part in 
 
 // What an Input needs to take unaligned BAM (bam.h: kBamHooks): whether a mapped file is BAM, and the inflated file as FASTQ text
 // (false: `reason` says what is wrong with it).  This header knows nothing else about BAM.
+// *header_len gets the length of the file's header; `rec_at` (null: not wanted) gets, for every record that HAS text, in order, the
+// offset of its BAM record in `data`: rec_at[j] = the record of text record j.
 struct BamHooks {
     bool (*detect)(const unsigned char *file, size_t n);
-    bool (*to_text)(const char *data, size_t n, std::unique_ptr<char[]> &text, size_t &text_len, std::string &reason);
+    bool (*to_text)(const char *data, size_t n, std::unique_ptr<char[]> &text, size_t &text_len, std::string &reason, uint64_t *header_len,
+                    std::vector<uint64_t> *rec_at);
 };
 
 // The whole input, addressable.  Plain files are mapped (no copy; pages are faulted in by several threads); gzip and
@@ -83,6 +86,12 @@ struct Input {
     const BamHooks *bam = nullptr;       // set by the caller before open(): this input may be unaligned BAM
     std::unique_ptr<char[]> bam_text;    // a BAM input: the text its records were turned into (p points here)
     std::string bam_error;               // open() returned false because the input is BAM and truncated or malformed: the reason
+    // --bam: what the output pass needs of a BAM input.  The file's header always; with keep_bam (set by the caller before open():
+    // the records go out as they came in) the inflated file stays in `owned` beside its text, and bam_rec_at[j] is where the BAM
+    // record of text record j starts in it (skipped records break the 1:1 numbering).
+    bool from_bam = false, keep_bam = false;
+    std::string bam_header;
+    std::vector<uint64_t> bam_rec_at;
     Input() = default;
     Input(const Input &) = delete;
     Input &operator=(const Input &) = delete;
@@ -143,9 +152,16 @@ struct Input {
                     ::close(fd);
                     if (!ok) bam_error = "the BGZF members could not be read";
                     else if (stream_error) bam_error = "a BGZF member does not inflate";
-                    else if (bam->to_text(owned.data(), owned.size(), bam_text, n, bam_error)) p = bam_text.get();
+                    uint64_t header_len = 0;
+                    if (ok && !stream_error && bam->to_text(owned.data(), owned.size(), bam_text, n, bam_error, &header_len, keep_bam ? &bam_rec_at : nullptr))
+                        p = bam_text.get();
                     stream_error = false;
-                    std::string().swap(owned);
+                    from_bam = p != nullptr;
+                    if (from_bam) bam_header.assign(owned.data(), (size_t)header_len);
+                    if (!from_bam || !keep_bam) {
+                        std::string().swap(owned);
+                        std::vector<uint64_t>().swap(bam_rec_at);
+                    }
                     return p != nullptr;
                 }
                 if (ok) {

@@ -243,8 +243,8 @@ int main(int argc, char **argv) {
 
     // ---- output in input order (src/main.cpp:263-313) -----------------------------------------------------
     Output out;
-    if (const int rc = begin_output(run, out); rc != kGoOn) return rc;
     const Emitter em(r2, p);
+    if (const int rc = begin_output(run, out, in, p, em); rc != kGoOn) return rc;
     if (const int rc = in.streamed ? write_output_streamed(run, in, p, em, out) : write_output_mapped(run, in, p, em, out); rc != kGoOn) return rc;
     if (const int rc = finish_output(run, out, em); rc != kGoOn) return rc;
     run.stage("output");

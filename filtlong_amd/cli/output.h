@@ -116,6 +116,21 @@ static bool gz_piece(flx_bgzf *gz, std::string &buf) {
     buf.swap(z);
     return true;
 }
+// --bam: a piece is STRICT record text (csrc/bam_encode.h: what Emitter::emit_strict appends) with its record offsets; one call
+// uploads it, packs the BAM records on the device and compresses them there, so only compressed bytes come back.  Like gz_piece
+// it runs on the worker that produced the piece, all workers at once.
+static bool bam_piece(flx_bgzf *gz, std::string &buf, const std::vector<uint64_t> &rec_off) {
+    const uint64_t n_rec = rec_off.size() - 1;
+    if (!gz || n_rec == 0) return buf.empty();
+    uint64_t enc = 0, bound = 0, got = 0, bad = 0;
+    if (flx_bam_from_fastq_bound(buf.size(), n_rec, &enc) != FLX_OK || flx_bgzf_bound(enc, 0, &bound) != FLX_OK) return false;
+    bound += 31 * n_rec;
+    std::string z(bound, '\0');
+    if (flx_bgzf_bam_from_fastq(gz, buf.data(), buf.size(), rec_off.data(), n_rec, 0, &z[0], bound, &got, &bad) != FLX_OK || bad != n_rec) return false;
+    z.resize(got);
+    buf.swap(z);
+    return true;
+}
 static const char kBgzfEof[28] = {0x1f, (char)0x8b, 8, 4, 0, 0, 0, 0, 0, (char)0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 // ---- one read of reads2 as text ------------------------------------------------------------------------------------------
@@ -152,6 +167,42 @@ struct Emitter {
             else out.append(r.qual.p + o.start, (size_t)(o.end - o.start));
             out += '\n';
         }
+    }
+    // --bam: read i as strict record text and its end in rec_off.  The name goes without its comment (the records carry names
+    // only).  A read whose quality line would not have exactly its L bytes (the header-only records above), or holds a byte
+    // outside '!'..'~', goes as a FASTA record: its BAM record says "no qualities" (0xFF).  Reads behind dies_at are not written.
+    bool written(uint64_t i) const {
+        if (!r2.pass[i] || i > dies_at) return false;
+        const Reads2::Out &o = r2.reads[i];
+        return !(o.child && o.end - o.start <= 0);
+    }
+    void emit_strict(std::string &out, std::vector<uint64_t> &rec_off, uint64_t i, const Record &r) const {
+        if (!written(i)) return;
+        const Reads2::Out &o = r2.reads[i];
+        const size_t L = (size_t)(o.end - o.start);
+        bool with_qual = fastq_output && !fasta_output && i != dies_at && !repeated_qual(i) && r.qual.n == r.seq.n;
+        if (with_qual) {
+            unsigned out_of_range = 0;
+            for (size_t j = 0; j < L; ++j) out_of_range |= (unsigned)((unsigned char)r.qual.p[o.start + j] - 33u > 93u);
+            with_qual = !out_of_range;
+        }
+        out += with_qual ? '@' : '>';
+        out += o.name;
+        out += '\n';
+        out.append(r.seq.p + o.start, L);
+        out += '\n';
+        if (with_qual) {
+            out += "+\n";
+            out.append(r.qual.p + o.start, L);
+            out += '\n';
+        }
+        rec_off.push_back(out.size());
+    }
+    // --bam, a BAM input whose reads go out whole: read i is its record of the inflated input, block_size through the last tag
+    void emit_original(std::string &out, const Input &src, uint64_t i) const {
+        if (!written(i)) return;
+        const uint64_t at = src.bam_rec_at[r2.reads[i].rec];
+        out.append(src.owned.data() + at, 4 + (size_t)bam::rd32((const uint8_t *)src.owned.data() + at));
     }
     uint64_t out_bytes(uint64_t i, const Record &r) const {  // what emit appends for read i
         if (!r2.pass[i]) return 0;
@@ -205,6 +256,20 @@ struct Output {
     off_t shared_base = -1, shared_end = -1;
     flx_bgzf *gz = nullptr;
     bool pieces_ok = true;
+    // --bam (gz is set as well): the file's header, and the BAM input whose records go out as they came in (null: every read is
+    // encoded from its text)
+    bool bam = false;
+    std::string bam_header;
+    const Input *bam_original = nullptr;
+    // read i of reads2 into a piece under construction, and the piece on its way out
+    void emit(const Emitter &em, std::string &buf, std::vector<uint64_t> &rec_off, uint64_t i, const Record &r) const {
+        if (!bam) em.emit(buf, i, r);
+        else if (bam_original) em.emit_original(buf, *bam_original, i);
+        else em.emit_strict(buf, rec_off, i, r);
+    }
+    bool compress(std::string &buf, const std::vector<uint64_t> &rec_off) const {
+        return bam && !bam_original ? bam_piece(gz, buf, rec_off) : gz_piece(gz, buf);
+    }
 };
 
 static int open_part(const Run &run, Output &out) {
@@ -214,11 +279,82 @@ static int open_part(const Run &run, Output &out) {
     return kGoOn;
 }
 
-static int begin_output(Run &run, Output &out) {
+// --bam: a name BAM cannot hold (l_read_name is one byte and counts the NUL) ends the job before anything is written.  Several
+// ranks: every rank looks at its own reads, the lowest rank that found one leaves the name where rank 0 reads it.
+static int check_bam_names(const Run &run, const Emitter &em) {
+    const std::string *bad = nullptr;
+    for (uint64_t i = 0; i < em.r2.reads.size() && !bad; ++i)
+        if (em.written(i) && (em.r2.reads[i].name.empty() || em.r2.reads[i].name.size() > 254)) bad = &em.r2.reads[i].name;
+    std::string name = bad ? *bad : std::string();
+    if (run.world > 1) {
+        std::vector<uint64_t> found((size_t)run.world, 0);
+        found[(size_t)run.rank] = bad != nullptr;
+        if (bad && run.rank > 0) {
+            FILE *f = fopen(run.part_path("badname", run.rank).c_str(), "wb");
+            if (f) { fwrite(name.data(), 1, name.size(), f); fclose(f); }
+        }
+        if (flx_comm_sum_u64(run.ctx, found.data(), found.size()) != FLX_OK) return run.fail("exchange");
+        int first = -1;
+        for (int r = run.world - 1; r >= 0; --r)
+            if (found[(size_t)r]) first = r;
+        if (first < 0) return kGoOn;
+        if (run.rank > 0) return 0;  // (rank 0 speaks for the job and gives it its status)
+        for (int r = 1; r < run.world; ++r) {
+            if (!found[(size_t)r]) continue;
+            const std::string pth = run.part_path("badname", r);
+            if (r == first)
+                if (FILE *f = fopen(pth.c_str(), "rb")) {
+                    char buf[4096];
+                    size_t got;
+                    name.clear();
+                    while ((got = fread(buf, 1, sizeof buf, f)) > 0) name.append(buf, got);
+                    fclose(f);
+                }
+            unlink(pth.c_str());
+        }
+    } else if (!bad) {
+        return kGoOn;
+    }
+    std::cerr << "Error: read name cannot be written as BAM: " << name << "\n";
+    return 1;
+}
+
+static int begin_output(Run &run, Output &out, const ReadsInput &in, const Pass1 &p, const Emitter &em) {
+    const Args &args = run.args;
+    if (args.bam) {
+        out.bam = true;
+        if (in.data.from_bam && in.data.keep_bam) {
+            // (the text of record j must be parsed record j: anything else would write some other read's record)
+            if (in.streamed || in.data.bam_rec_at.size() != p.kept.recs.size()) {
+                if (run.rank == 0) std::cerr << "Error: the records of the BAM input do not match their text\n";
+                return run.rank == 0 ? 1 : 0;
+            }
+            out.bam_original = &in.data;
+        }
+        if (!out.bam_original)
+            if (const int rc = check_bam_names(run, em); rc != kGoOn) return rc;
+        if (in.data.from_bam) {
+            out.bam_header = in.data.bam_header;
+        } else {
+            uint64_t len = 0;
+            (void)flx_bam_header(nullptr, 0, &len);
+            out.bam_header.resize((size_t)len);
+            if (flx_bam_header(&out.bam_header[0], len, &len) != FLX_OK) return run.fail("bam header");
+        }
+    }
     if (run.rank == 0) std::cerr << "Outputting passed long reads\n";
-    if (run.args.gzip && flx_bgzf_create(run.ctx, 16u << 20, (unsigned)std::min<size_t>(host_threads(), 16), &out.gz) != FLX_OK)
-        return run.fail("gzip");
+    // (--bam: a piece of ~16 MiB of text ends with the read that crosses that mark; slots with room for it take a piece in one go)
+    if ((args.gzip || args.bam) &&
+        flx_bgzf_create(run.ctx, args.bam ? 20u << 20 : 16u << 20, (unsigned)std::min<size_t>(host_threads(), 16), &out.gz) != FLX_OK)
+        return run.fail(args.bam ? "bam" : "gzip");
     return kGoOn;
+}
+
+// --bam: the compressed header in front of rank 0's first piece (a member of its own)
+static bool write_bam_header(const Run &run, Output &out) {
+    if (!out.bam || run.rank != 0) return true;
+    std::string h = out.bam_header;
+    return gz_piece(out.gz, h) && fwrite(h.data(), 1, h.size(), out.sink) == h.size();
 }
 
 // Round-3 review, item 8: ONE output file.  The ranks forked by --gpus N share the job's stdout; when that is a regular file
@@ -335,16 +471,17 @@ static int write_output_mapped(const Run &run, const ReadsInput &in, const Pass1
         if (const int rc = open_shared_or_part(run, out, piece_at.back(), em.dies_at != UINT64_MAX); rc != kGoOn) return rc;
     const char *fail_env = getenv("FLX_CLI_FAIL_WRITE_RANK");  // tests: this rank's writes fail (a full disk under one rank's share of the file)
     const bool fail_writes = fail_env && atoi(fail_env) == run.rank;
-    const bool ok = out.shared_skip || write_pieces(piece_first.size() - 1, [&](size_t j, std::string &buf, const PieceTarget &to) {
+    const bool ok = out.shared_skip || (write_bam_header(run, out) && write_pieces(piece_first.size() - 1, [&](size_t j, std::string &buf, const PieceTarget &to) {
         if (fail_writes) return false;
         if (!to.direct) {  // a pipe / terminal / append-mode file: the caller writes the formatted piece in order
-            for (uint64_t i = piece_first[j]; i < piece_first[j + 1]; ++i) em.emit(buf, i, recs[r2.reads[i].rec]);
-            return gz_piece(out.gz, buf);
+            std::vector<uint64_t> rec_off{0};
+            for (uint64_t i = piece_first[j]; i < piece_first[j + 1]; ++i) out.emit(em, buf, rec_off, i, recs[r2.reads[i].rec]);
+            return out.compress(buf, rec_off);
         }
         // regular file: this thread writes the piece itself
         buf.clear();
         return pwritev_piece(em, recs, in.data, piece_first[j], piece_first[j + 1], to.fd, to.base + (off_t)piece_at[j], to.base + (off_t)piece_at[j + 1]);
-    }, out.sink, out.gz ? nullptr : &piece_at, out.shared_file ? out.shared_base : (off_t)-1);  // (--gzip: formatted and compressed, in order)
+    }, out.sink, out.gz ? nullptr : &piece_at, out.shared_file ? out.shared_base : (off_t)-1));  // (--gzip, --bam: formatted and compressed, in order)
     // (several ranks: a rank that could not write — a full disk under its pwrite — still goes to the exchange of finish_output, where
     // every rank learns of it and rank 0 says why; leaving here would strand the others in that exchange)
     if (!ok && run.world == 1) return write_error();
@@ -371,7 +508,7 @@ static int write_output_streamed(const Run &run, const ReadsInput &in, const Pas
             r2_at[j] = cur;
         }
     }
-    const bool ok = write_pieces(n_units, [&](size_t j, std::string &buf, const PieceTarget &) {
+    const bool ok = write_bam_header(run, out) && write_pieces(n_units, [&](size_t j, std::string &buf, const PieceTarget &) {
         bool any = false;
         for (uint64_t i = r2_at[j]; i < r2_at[j + 1] && !any; ++i) any = r2.pass[i] != 0;
         if (!any) return true;
@@ -384,14 +521,15 @@ static int write_output_streamed(const Run &run, const ReadsInput &in, const Pas
         parse_sequential(view, got);
         if (got.recs.size() != units.first_rec[j + 1] - units.first_rec[j]) return false;
         uint64_t cur = r2_at[j];
+        std::vector<uint64_t> rec_off{0};
         for (size_t k = 0; k < got.recs.size(); ++k) {
             const uint64_t rec = units.first_rec[j] + k;
             const Record &r = got.recs[k];
             if (rec < p.lo_rec || rec - p.lo_rec >= n) continue;  // (several ranks: a unit at the edge of the share holds other ranks' records too)
             if (r.name.sv() != p.names[rec - p.lo_rec] || (int32_t)r.seq.size() != p.lengths[rec - p.lo_rec]) return false;
-            for (; cur < r2_at[j + 1] && r2.reads[cur].rec == rec; ++cur) em.emit(buf, cur, r);
+            for (; cur < r2_at[j + 1] && r2.reads[cur].rec == rec; ++cur) out.emit(em, buf, rec_off, cur, r);
         }
-        return gz_piece(out.gz, buf);
+        return out.compress(buf, rec_off);
     }, out.sink, nullptr);
     if (g_gpu_inflater.output_pass && getenv("FLX_CLI_PINFLATE_TIMING"))
         fprintf(stderr, "[pinflate] device: output pass: %llu units inflated on the device, %llu by zlib\n",
@@ -422,7 +560,7 @@ static int stitch_rank_outputs(const Run &run, const std::vector<uint64_t> &done
             return write_error();
         }
     }
-    if ((run.args.gzip && fwrite(kBgzfEof, 1, 28, stdout) != 28) || fflush(stdout) != 0) return write_error();
+    if (((run.args.gzip || run.args.bam) && fwrite(kBgzfEof, 1, 28, stdout) != 28) || fflush(stdout) != 0) return write_error();
     return kGoOn;
 }
 

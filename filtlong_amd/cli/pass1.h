@@ -50,6 +50,7 @@ static int open_reads_input(Run &run, ReadsInput &in) {
             if (file.open(args.input_reads) && bam_detect(file.p, file.n)) in.streamed = false;
         }
         in.data.bam = &kBamHooks;
+        in.data.keep_bam = args.bam && !args.trim && !args.split_set;  // (--bam: the reads go out whole, as their original records)
     }
     if (in.streamed ? !in.blocks.open(args.input_reads, true) : !in.data.open(args.input_reads)) {
         if (!in.streamed && !in.data.bam_error.empty()) std::cerr << "Error: could not read BAM input " << args.input_reads << ": " << in.data.bam_error << "\n";

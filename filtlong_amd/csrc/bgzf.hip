@@ -197,6 +197,12 @@ struct flx_bgzf_slot {
     void *work = nullptr;
     uint64_t *h_state = nullptr;
     uint64_t *d_tab = nullptr, *h_tab = nullptr;  // inflate: the piece's offsets, its first bad member, its status words
+    // text -> BAM (flx_bgzf_bam_from_fastq): allocated by the first such call on the slot, each grown alone.  The text of a piece
+    // goes through h_in / d_in like the compressor's input; e_h_text / e_d_text exist only behind a record larger than the slot.
+    uint8_t *e_h_text = nullptr, *e_d_text = nullptr, *e_d_bam = nullptr;
+    uint64_t *e_h_off = nullptr, *e_d_off = nullptr, *e_d_out_off = nullptr, *e_h_state = nullptr;
+    void *e_work = nullptr;
+    uint64_t e_text_cap = 0, e_rec_cap = 0, e_bam_cap = 0, e_work_cap = 0;
     bool busy = false;
 };
 
@@ -215,7 +221,23 @@ struct flx_bgzf {
     std::condition_variable cv;
 };
 
+static void free_encoder(flx_bgzf_slot &s) {
+    if (s.e_h_text) (void)hipHostFree(s.e_h_text);
+    if (s.e_d_text) (void)hipFree(s.e_d_text);
+    if (s.e_d_bam) (void)hipFree(s.e_d_bam);
+    if (s.e_h_off) (void)hipHostFree(s.e_h_off);
+    if (s.e_d_off) (void)hipFree(s.e_d_off);
+    if (s.e_d_out_off) (void)hipFree(s.e_d_out_off);
+    if (s.e_h_state) (void)hipHostFree(s.e_h_state);
+    if (s.e_work) (void)hipFree(s.e_work);
+    s.e_h_text = s.e_d_text = s.e_d_bam = nullptr;
+    s.e_h_off = s.e_d_off = s.e_d_out_off = s.e_h_state = nullptr;
+    s.e_work = nullptr;
+    s.e_text_cap = s.e_rec_cap = s.e_bam_cap = s.e_work_cap = 0;
+}
+
 static void free_slot(flx_bgzf_slot &s) {
+    free_encoder(s);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.d_in) (void)hipFree(s.d_in);
     if (s.d_out) (void)hipFree(s.d_out);
@@ -382,4 +404,135 @@ extern "C" int flx_bgzf_compress(flx_bgzf *z, const void *in, uint64_t n, int fl
     give_slot(z, s);
     if (rc == FLX_OK) *out_len = len;
     return rc;
+}
+
+// ---- text -> BAM -> BGZF through one slot ---------------------------------------------------------------------------------
+// Room on the (idle) slot for a piece of text_bytes of text in n_rec records.  Every buffer grows alone, and only when it is too
+// small: a free synchronises the device under the other workers' streams.  Text of at most slot_bytes needs no buffer of its own.
+static hipError_t reserve_encoder(flx_bgzf_slot &s, uint64_t slot_bytes, uint64_t text_bytes, uint64_t n_rec) {
+    hipError_t e = hipSuccess;
+    if (!s.e_h_state) e = hipHostMalloc((void **)&s.e_h_state, 32, hipHostMallocDefault);
+    if (e == hipSuccess && text_bytes > slot_bytes && text_bytes > s.e_text_cap) {
+        if (s.e_h_text) (void)hipHostFree(s.e_h_text);
+        if (s.e_d_text) (void)hipFree(s.e_d_text);
+        s.e_h_text = s.e_d_text = nullptr;
+        s.e_text_cap = 0;
+        e = hipHostMalloc((void **)&s.e_h_text, text_bytes + 16, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void **)&s.e_d_text, text_bytes + 16);
+        if (e == hipSuccess) s.e_text_cap = text_bytes;
+    }
+    if (e == hipSuccess && n_rec > s.e_rec_cap) {
+        if (s.e_h_off) (void)hipHostFree(s.e_h_off);
+        if (s.e_d_off) (void)hipFree(s.e_d_off);
+        if (s.e_d_out_off) (void)hipFree(s.e_d_out_off);
+        s.e_h_off = s.e_d_off = s.e_d_out_off = nullptr;
+        s.e_rec_cap = 0;
+        e = hipHostMalloc((void **)&s.e_h_off, (n_rec + 1) * 8, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void **)&s.e_d_off, (n_rec + 1) * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&s.e_d_out_off, (n_rec + 1) * 8);
+        if (e == hipSuccess) s.e_rec_cap = n_rec;
+    }
+    uint64_t bb = 0;
+    (void)flx_bam_from_fastq_bound(text_bytes, n_rec, &bb);
+    if (e == hipSuccess && bb > s.e_bam_cap) {
+        if (s.e_d_bam) (void)hipFree(s.e_d_bam);
+        s.e_d_bam = nullptr;
+        s.e_bam_cap = 0;
+        if ((e = hipMalloc((void **)&s.e_d_bam, bb + kSlotSlack)) == hipSuccess) s.e_bam_cap = bb;
+    }
+    const uint64_t wb = flx_bam_encode_work_bytes(n_rec, text_bytes);
+    if (e == hipSuccess && wb > s.e_work_cap) {
+        if (s.e_work) (void)hipFree(s.e_work);
+        s.e_work = nullptr;
+        s.e_work_cap = 0;
+        if ((e = hipMalloc(&s.e_work, wb)) == hipSuccess) s.e_work_cap = wb;
+    }
+    return e;
+}
+
+// Thread-safe like flx_bgzf_compress.  A piece is whole records of at most slot_bytes of text (one record when that record is
+// larger): its text goes up, the encode kernels write the BAM bytes into the slot's own buffer, and the compressor's kernels run
+// over those bytes in slot-sized chunks exactly as flx_bgzf_compress runs them over an uploaded chunk; only compressed bytes come
+// back.  The piece's first bad record is known before anything of the piece is compressed.
+extern "C" int flx_bgzf_bam_from_fastq(flx_bgzf *z, const void *text, uint64_t n, const uint64_t *rec_off, uint64_t n_records, int flags,
+                                       void *out, uint64_t out_cap, uint64_t *out_len, uint64_t *first_bad) {
+    if (!z || !out_len || !first_bad || (flags & ~FLX_BGZF_EOF) || (!out && out_cap)) return FLX_ERR_INVALID;
+    *out_len = 0;
+    *first_bad = n_records;
+    if (n_records && (!text || !rec_off || n_records > 0xffffffffull)) return FLX_ERR_INVALID;
+    // offsets that leave the text or run backwards: the lowest such record is bad, nothing is uploaded
+    for (uint64_t k = 0; k < n_records; ++k)
+        if (!(rec_off[k] <= rec_off[k + 1] && rec_off[k + 1] <= n)) {
+            *first_bad = k;
+            return FLX_OK;
+        }
+    constexpr uint64_t kPieceRecords = 1u << 20;
+    flx_bgzf_slot *s = take_slot(z);
+    int rc = FLX_OK;
+    hipError_t e = hipSetDevice(z->device);
+    const unsigned emit_blocks = flx_bam_encode_blocks(z->ctx);
+    uint64_t k = 0, len = 0, bad = n_records;
+    while (e == hipSuccess && rc == FLX_OK && k < n_records) {
+        uint64_t c = 1;  // at least one record: the buffers grow to the largest
+        while (k + c < n_records && c < kPieceRecords && rec_off[k + c + 1] - rec_off[k] <= z->slot_bytes) ++c;
+        const uint64_t nin = rec_off[k + c] - rec_off[k];
+        // (sized for whole slots, so that the pieces of a run find room the first piece made)
+        if ((e = reserve_encoder(*s, z->slot_bytes, nin > z->slot_bytes ? nin : z->slot_bytes, c > 4096 ? c : 4096)) != hipSuccess) {
+            rc = FLX_ERR_NOMEM;
+            break;
+        }
+        uint8_t *h_text = nin <= z->slot_bytes ? s->h_in : s->e_h_text, *d_text = nin <= z->slot_bytes ? s->d_in : s->e_d_text;
+        for (uint64_t j = 0; j <= c; ++j) s->e_h_off[j] = rec_off[k + j] - rec_off[k];
+        memcpy(h_text, (const uint8_t *)text + rec_off[k], (size_t)nin);
+        if (nin) e = hipMemcpyAsync(d_text, h_text, nin, hipMemcpyHostToDevice, s->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->e_d_off, s->e_h_off, (c + 1) * 8, hipMemcpyHostToDevice, s->stream);
+        if (e == hipSuccess)
+            e = flx_bam_encode_launch(s->stream, emit_blocks, d_text, nin, s->e_d_off, c, s->e_work, s->e_d_out_off, s->e_d_bam, s->e_bam_cap,
+                                      s->e_h_state);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(s->stream);
+            break;
+        }
+        const uint64_t enc = s->e_h_state[0], nbad = s->e_h_state[3];
+        if (nbad) {
+            bad = k + (c - (nbad <= c ? nbad : c));
+            break;
+        }
+        if (enc > s->e_bam_cap) {  // (cannot happen: the buffer has the bound of the piece)
+            rc = FLX_ERR_STATE;
+            break;
+        }
+        const bool last_piece = k + c == n_records;
+        for (uint64_t done = 0; done < enc && rc == FLX_OK;) {
+            const uint64_t cb = enc - done < z->slot_bytes ? enc - done : z->slot_bytes;
+            const int f = (last_piece && done + cb == enc) ? flags : 0;
+            if ((e = bgzf_run(s->stream, s->e_d_bam + done, cb, f, s->d_out, bound_of(cb, f), s->work, s->h_state)) != hipSuccess) break;
+            const uint64_t got = s->h_state[0];
+            if (got > out_cap - len) {
+                rc = FLX_ERR_CAPACITY;
+                break;
+            }
+            if ((e = hipMemcpyAsync(s->h_out, s->d_out, got, hipMemcpyDeviceToHost, s->stream)) == hipSuccess) e = hipStreamSynchronize(s->stream);
+            if (e != hipSuccess) break;
+            memcpy((uint8_t *)out + len, s->h_out, (size_t)got);
+            len += got;
+            done += cb;
+        }
+        k += c;
+    }
+    // (the end-of-file block of a call whose last piece held no byte to carry it: no records at all)
+    if (e == hipSuccess && rc == FLX_OK && bad == n_records && n_records == 0 && (flags & FLX_BGZF_EOF)) {
+        if (out_cap < 28) rc = FLX_ERR_CAPACITY;
+        else {
+            memcpy(out, kEof, 28);
+            len = 28;
+        }
+    }
+    give_slot(z, s);
+    if (e != hipSuccess && rc == FLX_OK) rc = FLX_ERR_HIP;
+    if (rc != FLX_OK) return rc;
+    *first_bad = bad;
+    if (bad == n_records) *out_len = len;
+    return FLX_OK;
 }

@@ -100,6 +100,13 @@ struct flx_time_scope {
 hipError_t flx_bgzf_inflate_launch(hipStream_t st, const void *d_in, const uint64_t *d_in_off, const uint64_t *d_out_off,
                                    uint64_t n_members, void *d_out, uint32_t *d_status, uint64_t *d_first);
 
+// bam_encode.hip: the launches of one text -> BAM call on `st` (for flx_bgzf's slots in bgzf.hip); h_state[0]: the BAM bytes,
+// h_state[3]: n_rec - the lowest bad record (0: none), both valid once the stream has been synchronised
+size_t flx_bam_encode_work_bytes(uint64_t n_rec, uint64_t bytes);
+unsigned flx_bam_encode_blocks(const flx_ctx *ctx);
+hipError_t flx_bam_encode_launch(hipStream_t st, unsigned emit_blocks, const void *d_text, uint64_t n, const uint64_t *d_off, uint64_t n_rec,
+                                 void *work, uint64_t *d_out_off, void *d_out, uint64_t out_cap, uint64_t *h_state);
+
 // grow-only scratch on the device
 int flx_scratch(flx_ctx *ctx, size_t bytes, void **out);
 // grow-only pinned host buffer; valid until the next call that asks for more

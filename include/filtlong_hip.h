@@ -41,8 +41,9 @@ extern "C" {
 /* 3 (round 5): + flx_last_kmer_fold_grid */
 /* 4 (round 6): + flx_last_kmer_cover, flx_last_kmer_handed_over, flx_synth_seq_profile_dev; added under version 4: the BGZF
  * compressor (flx_bgzf_bound, flx_bgzf_compress_dev, flx_bgzf_create / _compress / _destroy), the read summary
- * (flx_summary_q_edges, flx_summary_dev, flx_summary) and the BGZF inflater (flx_bgzf_index, flx_bgzf_inflate_dev,
- * flx_bgzf_inflate) */
+ * (flx_summary_q_edges, flx_summary_dev, flx_summary), the BGZF inflater (flx_bgzf_index, flx_bgzf_inflate_dev,
+ * flx_bgzf_inflate), the BAM reader (flx_bam_index, flx_bam_to_fastq_dev, flx_bam_to_fastq) and the BAM writer (flx_bam_header,
+ * flx_bam_from_fastq_bound, flx_bam_from_fastq_dev, flx_bgzf_bam_from_fastq) */
 #define FLX_ABI_VERSION 4
 
 enum flx_status {
@@ -405,6 +406,43 @@ int flx_bam_to_fastq_dev(flx_ctx *ctx, const void *d_bam, uint64_t n, const uint
                          uint64_t out_cap, uint64_t *d_out_off, uint64_t *out_len, uint64_t *n_skipped, uint64_t *first_bad);
 int flx_bam_to_fastq(flx_ctx *ctx, const void *bam, uint64_t n, const uint64_t *rec_off, uint64_t n_records, uint64_t piece_bytes,
                      void *out, uint64_t out_cap, uint64_t *out_off, uint64_t *out_len, uint64_t *n_skipped, uint64_t *first_bad);
+
+/* ------------------------------------------------------------------------------------------
+ * FASTQ / FASTA text to unaligned BAM (added under version 4): the write side of the functions above.  Input is STRICT record text:
+ * record k is the bytes [rec_off[k], rec_off[k+1]) and has the form
+ *   '@' HEADER '\n' SEQ '\n' '+' '\n' QUAL '\n'    (FASTQ, |SEQ| == |QUAL| == L)      or      '>' HEADER '\n' SEQ '\n'    (FASTA)
+ * Only the header line is scanned (to its first '\n'); L follows from the record's length and the bytes at the derived positions
+ * must be '\n', '+', '\n', '\n'.  The name is the header up to its first blank or tab; the rest of the line (the comment) is NOT
+ * stored.  A record is valid when it has that shape, the name has 1..254 bytes, L <= 2^31 - 1 and every QUAL byte is in 33..126.
+ * Its BAM record: refID -1, pos -1, mapq 0, bin 4680, no CIGAR, flag 4, next_refID -1, next_pos -1, tlen 0, the name, the bases
+ * packed by "=ACMGRSVTWYHKDBN" (upper-cased; any other byte is 'N'; a zero low nibble behind an odd L), the qualities c - 33 (0xFF
+ * at every position for a FASTA record), no tags: 37 + name + (L + 1) / 2 + L bytes.
+ *   flx_bam_header            host only: the header of a file written from text ("BAM\1", l_text, "@HD\tVN:1.6\tSO:unknown\n", n_ref 0);
+ *                             *out_len = its size; out == NULL: the size only; FLX_ERR_CAPACITY when out_cap is below it.
+ *   flx_bam_from_fastq_bound  the most bytes the records of n_text bytes of text in n_records records can take:
+ *                             n_text + n_text / 2 + 34 n_records (a FASTA record of L bases grows by 34 + ceil(L/2) at most, a FASTQ
+ *                             record by 31 at most).
+ *   flx_bam_from_fastq_dev    device to device on the context's stream (timed as "flx_bam_encode"): d_out_off[0..n_records] (device,
+ *                             u64) gets the records' offsets in d_out, *out_len the BAM length.  FLX_ERR_CAPACITY when out_cap is
+ *                             below it (*out_len = the length needed; nothing is written).  An invalid record is data, not an
+ *                             error: *first_bad = the lowest such k (else n_records), and the output is then no result.  Offsets
+ *                             that leave [0, n) or run backwards make their records invalid.  n_records == 0 is a no-op.
+ *   flx_bgzf_bam_from_fastq   host to host through ONE slot of a flx_bgzf: the text is uploaded, encoded, the encoded bytes are
+ *                             compressed by the kernels of flx_bgzf_compress_dev and the compressed bytes come back; the uncompressed
+ *                             BAM never crosses the link.  May be called from several threads at once like flx_bgzf_compress.
+ *                             rec_off is relative to `text` (rec_off[0] .. rec_off[n_records] <= n).  Text beyond the slot goes
+ *                             through in pieces of whole records and the slot's buffers grow to the largest record.  The
+ *                             DECOMPRESSED bytes are a pure function of the text; where the members are cut depends on the pieces.
+ *                             FLX_BGZF_EOF as for the compressor.  out_cap of flx_bgzf_bound(flx_bam_from_fastq_bound(..)) + 31
+ *                             n_records always suffices (a piece ends with a member of its own); FLX_ERR_CAPACITY below what is
+ *                             needed.  With an invalid record: FLX_OK, *first_bad = its number, *out_len = 0, `out` is no result.
+ * ---------------------------------------------------------------------------------------- */
+int flx_bam_header(void *out, uint64_t out_cap, uint64_t *out_len);
+int flx_bam_from_fastq_bound(uint64_t n_text, uint64_t n_records, uint64_t *bound);
+int flx_bam_from_fastq_dev(flx_ctx *ctx, const void *d_text, uint64_t n, const uint64_t *d_rec_off, uint64_t n_records, void *d_out,
+                           uint64_t out_cap, uint64_t *d_out_off, uint64_t *out_len, uint64_t *first_bad);
+int flx_bgzf_bam_from_fastq(flx_bgzf *z, const void *text, uint64_t n, const uint64_t *rec_off, uint64_t n_records, int flags, void *out,
+                            uint64_t out_cap, uint64_t *out_len, uint64_t *first_bad);
 
 /* ------------------------------------------------------------------------------------------
  * read summary (added under version 4): what a set of reads looks like — entries, bases, shortest, longest, median, N10..N90
