@@ -13,8 +13,10 @@
 //     are rotated so that every lane then pulls its own bytes with conflict-free ds_read_b128.  The next chunk's DMA
 //     is issued as soon as the slot has been read, a whole round (64 bases per lane) of compute ahead.
 //   * per base: 2 address ops, 3 ds_read_b64 gathers, 3 v_add_f64, 1 v_min_f64 — written as asm statements of
-//     4 bases (12 gathers issued back to back, the FP64 chain follows as data arrives); left to hipcc the unrolled
-//     loop gets its gathers hoisted away from the chain and spills.
+//     4 bases (12 gathers issued back to back, the FP64 chain follows as data arrives, one counted wait per base); left
+//     to hipcc the unrolled loop gets its gathers hoisted away from the chain and spills.  In the static window-250
+//     kernel a whole round's 16 statements form one chain: each computes the next one's addresses between its last
+//     gather and its first wait, where the wave would otherwise sit out the gather latency (steady_round).
 //   * optional bank-private tables (FLX_PHRED_TABLES=private): every table entry is replicated once per bank pair
 //     (lane l reads copy l % 32), so a gather never has a bank conflict whatever the quality distribution is
 //     (plain tables: entries e and e+32 collide; a wide Phred range costs up to 1.5x per gather).  128 entries per
@@ -75,40 +77,74 @@ __device__ __forceinline__ uint32_t tab_addr_at(const uint32_t (&x)[8], int e, u
 
 // ---- the FP64 folds as asm statements (see the header comment) ---------------------------------------------
 // steady state, 4 bases: s += Q[new]; w -= D[old]; w += D[new]; mn = min(mn, w)     (src/read.cpp:210, 228-231)
+// Operands of both forms: %0 s, %1 w, %2 mn, %3..%14 the gathered values (Q[new], D[old], D[new] per base), %15..%18 the leading
+// and %19..%22 the trailing addresses, %23 QOFF, %24 DOFF.  LDS returns in order: one counted wait per base (the three values
+// of a base arrive within a few cycles of each other), not one per operand.
+#define FLX_FOLD4_GATHERS                                                                                             \
+    "ds_read_b64 %3, %15 offset:%23\n\tds_read_b64 %4, %19 offset:%24\n\tds_read_b64 %5, %15 offset:%24\n\t"         \
+    "ds_read_b64 %6, %16 offset:%23\n\tds_read_b64 %7, %20 offset:%24\n\tds_read_b64 %8, %16 offset:%24\n\t"         \
+    "ds_read_b64 %9, %17 offset:%23\n\tds_read_b64 %10, %21 offset:%24\n\tds_read_b64 %11, %17 offset:%24\n\t"       \
+    "ds_read_b64 %12, %18 offset:%23\n\tds_read_b64 %13, %22 offset:%24\n\tds_read_b64 %14, %18 offset:%24\n\t"
+#define FLX_FOLD4_CHAIN                                                                                                          \
+    "s_waitcnt lgkmcnt(9)\n\tv_add_f64 %0, %0, %3\n\tv_add_f64 %1, %1, -%4\n\tv_add_f64 %1, %1, %5\n\tv_min_f64 %2, %2, %1\n\t"   \
+    "s_waitcnt lgkmcnt(6)\n\tv_add_f64 %0, %0, %6\n\tv_add_f64 %1, %1, -%7\n\tv_add_f64 %1, %1, %8\n\tv_min_f64 %2, %2, %1\n\t"   \
+    "s_waitcnt lgkmcnt(3)\n\tv_add_f64 %0, %0, %9\n\tv_add_f64 %1, %1, -%10\n\tv_add_f64 %1, %1, %11\n\tv_min_f64 %2, %2, %1\n\t" \
+    "s_waitcnt lgkmcnt(0)\n\tv_add_f64 %0, %0, %12\n\tv_add_f64 %1, %1, -%13\n\tv_add_f64 %1, %1, %14\n\tv_min_f64 %2, %2, %1"
+#define FLX_FOLD4_VALUES                                                                                                       \
+    "+v"(s), "+v"(w), "+v"(mn), "=&v"(q0), "=&v"(i0), "=&v"(j0), "=&v"(q1), "=&v"(i1), "=&v"(j1), "=&v"(q2), "=&v"(i2), "=&v"(j2), \
+        "=&v"(q3), "=&v"(i3), "=&v"(j3)
 template <int QOFF, int DOFF>
 __device__ __forceinline__ void fold4(uint32_t aj0, uint32_t aj1, uint32_t aj2, uint32_t aj3, uint32_t ai0, uint32_t ai1,
                                       uint32_t ai2, uint32_t ai3, double &s, double &w, double &mn) {
     double q0, i0, j0, q1, i1, j1, q2, i2, j2, q3, i3, j3;
-    asm volatile(
-        "ds_read_b64 %3, %15 offset:%23\n\tds_read_b64 %4, %19 offset:%24\n\tds_read_b64 %5, %15 offset:%24\n\t"
-        "ds_read_b64 %6, %16 offset:%23\n\tds_read_b64 %7, %20 offset:%24\n\tds_read_b64 %8, %16 offset:%24\n\t"
-        "ds_read_b64 %9, %17 offset:%23\n\tds_read_b64 %10, %21 offset:%24\n\tds_read_b64 %11, %17 offset:%24\n\t"
-        "ds_read_b64 %12, %18 offset:%23\n\tds_read_b64 %13, %22 offset:%24\n\tds_read_b64 %14, %18 offset:%24\n\t"
-        "s_waitcnt lgkmcnt(11)\n\tv_add_f64 %0, %0, %3\n\t"
-        "s_waitcnt lgkmcnt(10)\n\tv_add_f64 %1, %1, -%4\n\t"
-        "s_waitcnt lgkmcnt(9)\n\tv_add_f64 %1, %1, %5\n\tv_min_f64 %2, %2, %1\n\t"
-        "s_waitcnt lgkmcnt(8)\n\tv_add_f64 %0, %0, %6\n\t"
-        "s_waitcnt lgkmcnt(7)\n\tv_add_f64 %1, %1, -%7\n\t"
-        "s_waitcnt lgkmcnt(6)\n\tv_add_f64 %1, %1, %8\n\tv_min_f64 %2, %2, %1\n\t"
-        "s_waitcnt lgkmcnt(5)\n\tv_add_f64 %0, %0, %9\n\t"
-        "s_waitcnt lgkmcnt(4)\n\tv_add_f64 %1, %1, -%10\n\t"
-        "s_waitcnt lgkmcnt(3)\n\tv_add_f64 %1, %1, %11\n\tv_min_f64 %2, %2, %1\n\t"
-        "s_waitcnt lgkmcnt(2)\n\tv_add_f64 %0, %0, %12\n\t"
-        "s_waitcnt lgkmcnt(1)\n\tv_add_f64 %1, %1, -%13\n\t"
-        "s_waitcnt lgkmcnt(0)\n\tv_add_f64 %1, %1, %14\n\tv_min_f64 %2, %2, %1"
-        : "+v"(s), "+v"(w), "+v"(mn), "=&v"(q0), "=&v"(i0), "=&v"(j0), "=&v"(q1), "=&v"(i1), "=&v"(j1), "=&v"(q2), "=&v"(i2),
-          "=&v"(j2), "=&v"(q3), "=&v"(i3), "=&v"(j3)
-        : "v"(aj0), "v"(aj1), "v"(aj2), "v"(aj3), "v"(ai0), "v"(ai1), "v"(ai2), "v"(ai3), "i"(QOFF), "i"(DOFF));
+    asm volatile(FLX_FOLD4_GATHERS FLX_FOLD4_CHAIN
+                 : FLX_FOLD4_VALUES
+                 : "v"(aj0), "v"(aj1), "v"(aj2), "v"(aj3), "v"(ai0), "v"(ai1), "v"(ai2), "v"(ai3), "i"(QOFF), "i"(DOFF));
 }
-// positions before the first full window, 4 bases: s += Q[new]
+// The same fold with the NEXT group's eight addresses computed in the shadow of this group's gather latency: the 12 gathers
+// issue from a[0..3] (leading) and a[4..7] (trailing); the next group's address instructions then overwrite a[] in place (a DS
+// instruction has read its address register once it has issued, and the first DS read of the new addresses is a whole
+// FP64 chain later: no wait states are needed), and only then does the chain start waiting.  nl: the next group's leading dword;
+// t0..t3: the dwords that hold its four trailing bytes, bytes T0..T3 of them (the byte select is assembler text for the SDWA
+// shift, a selector register for v_perm_b32).
+template <bool PRIV, int QOFF, int DOFF, int T0, int T1, int T2, int T3>
+__device__ __forceinline__ void fold4_next(uint32_t (&a)[8], uint32_t nl, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3,
+                                           uint32_t laneoff, double &s, double &w, double &mn) {
+    double q0, i0, j0, q1, i1, j1, q2, i2, j2, q3, i3, j3;
+    if constexpr (PRIV) {
+        constexpr uint32_t sel = 0x0c0c0400u;  // tab_addr's selector of byte 0; byte b: + (b << 8)
+        asm volatile(FLX_FOLD4_GATHERS
+                     "v_perm_b32 %15, %25, %30, %31\n\tv_perm_b32 %16, %25, %30, %32\n\tv_perm_b32 %17, %25, %30, %33\n\t"
+                     "v_perm_b32 %18, %25, %30, %34\n\tv_perm_b32 %19, %26, %30, %35\n\tv_perm_b32 %20, %27, %30, %36\n\t"
+                     "v_perm_b32 %21, %28, %30, %37\n\tv_perm_b32 %22, %29, %30, %38\n\t" FLX_FOLD4_CHAIN
+                     : FLX_FOLD4_VALUES, "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7])
+                     : "i"(QOFF), "i"(DOFF), "v"(nl), "v"(t0), "v"(t1), "v"(t2), "v"(t3), "v"(laneoff), "s"(sel), "s"(sel + 0x100u),
+                       "s"(sel + 0x200u), "s"(sel + 0x300u), "s"(sel + (T0 << 8)), "s"(sel + (T1 << 8)), "s"(sel + (T2 << 8)),
+                       "s"(sel + (T3 << 8)));
+    } else {
+        const uint32_t three = 3;
+#define FLX_SDWA(dst, src, sel) \
+    "v_lshlrev_b32_sdwa " dst ", %30, " src " dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_" sel "\n\t"
+        asm volatile(FLX_FOLD4_GATHERS
+                     FLX_SDWA("%15", "%25", "0") FLX_SDWA("%16", "%25", "1") FLX_SDWA("%17", "%25", "2") FLX_SDWA("%18", "%25", "3")
+                     FLX_SDWA("%19", "%26", "%c31") FLX_SDWA("%20", "%27", "%c32") FLX_SDWA("%21", "%28", "%c33")
+                     FLX_SDWA("%22", "%29", "%c34") FLX_FOLD4_CHAIN
+                     : FLX_FOLD4_VALUES, "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7])
+                     : "i"(QOFF), "i"(DOFF), "v"(nl), "v"(t0), "v"(t1), "v"(t2), "v"(t3), "v"(three), "i"(T0), "i"(T1), "i"(T2), "i"(T3));
+#undef FLX_SDWA
+    }
+}
+#undef FLX_FOLD4_GATHERS
+#undef FLX_FOLD4_CHAIN
+#undef FLX_FOLD4_VALUES
+// positions before the first full window, 4 bases: s += Q[new]  (one wait for the group)
 template <int QOFF>
 __device__ __forceinline__ void head4(uint32_t aj0, uint32_t aj1, uint32_t aj2, uint32_t aj3, double &s) {
     double q0, q1, q2, q3;
     asm volatile(
         "ds_read_b64 %1, %5 offset:%9\n\tds_read_b64 %2, %6 offset:%9\n\tds_read_b64 %3, %7 offset:%9\n\t"
         "ds_read_b64 %4, %8 offset:%9\n\t"
-        "s_waitcnt lgkmcnt(3)\n\tv_add_f64 %0, %0, %1\n\ts_waitcnt lgkmcnt(2)\n\tv_add_f64 %0, %0, %2\n\t"
-        "s_waitcnt lgkmcnt(1)\n\tv_add_f64 %0, %0, %3\n\ts_waitcnt lgkmcnt(0)\n\tv_add_f64 %0, %0, %4"
+        "s_waitcnt lgkmcnt(0)\n\tv_add_f64 %0, %0, %1\n\tv_add_f64 %0, %0, %2\n\tv_add_f64 %0, %0, %3\n\tv_add_f64 %0, %0, %4"
         : "+v"(s), "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3)
         : "v"(aj0), "v"(aj1), "v"(aj2), "v"(aj3), "i"(QOFF));
 }
@@ -318,6 +354,44 @@ __global__ void __launch_bounds__(WAVES * 64) flx_score_phred_regs(const PhredAr
             fold4<T::QOFF, T::DOFF>(aj[0], aj[1], aj[2], aj[3], ai[0], ai[1], ai[2], ai[3], s, w, mn);
         }
     };
+    // A round of four steady pieces that every lane still has whole (all but a wave's last rounds), ring pieces t0 .. t0 + 3: one
+    // chain of 16 folds, each computing the next group's addresses, in place, behind its own gathers (fold4_next); only the
+    // first group's addresses are computed ahead of its fold.  load_round has loaded all four pieces, so the chain crosses the
+    // pieces; it does not cross rounds.  Straight-line code: the addresses are live across no branch.  Static instantiations
+    // only (BS >= 0): with the funnel's dwords as sources the generic plain-table kernels of A = 13 .. 15 went to scratch.
+    constexpr int TS0 = (16 - BS) & 3, TS1 = (17 - BS) & 3, TS2 = (18 - BS) & 3, TS3 = (19 - BS) & 3;  // byte of its dword that
+    auto steady_round = [&](int t0) {                                                       // holds trailing base i of a group
+        uint32_t adr[8];
+        {
+            const uint32_t(&p0)[4] = ring[(t0 + R - A - 1) % R];
+            const uint32_t(&p1)[4] = ring[(t0 + R - A) % R];
+            uint32_t aj[4], ai[4];
+            addr4(ring[t0][0], false, 0, 0, aj);
+            trail4_static(p0, p1, 0, false, 0, ai);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { adr[i] = aj[i]; adr[4 + i] = ai[i]; }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int t = t0 + k;
+            const uint32_t(&p0)[4] = ring[(t + R - A - 1) % R];
+            const uint32_t(&p1)[4] = ring[(t + R - A) % R];
+            const uint32_t(&np1)[4] = ring[(t + 1 + R - A) % R];  // the next piece's trailing pieces are (p1 : np1)
+            const uint32_t x[12] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3], np1[0], np1[1], np1[2], np1[3]};
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                if (k == 3 && d == 3) {
+                    fold4<T::QOFF, T::DOFF>(adr[0], adr[1], adr[2], adr[3], adr[4], adr[5], adr[6], adr[7], s, w, mn);
+                    break;
+                }
+                uint32_t ts[4];  // the dwords that hold the next group's trailing bases: group d + 1 of (p0 : p1 : np1)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) ts[i] = x[(16 - BS + 4 * (d + 1) + i) >> 2];
+                fold4_next<PRIV, T::QOFF, T::DOFF, TS0, TS1, TS2, TS3>(adr, d < 3 ? ring[t][d + 1] : ring[k < 3 ? t + 1 : t][0], ts[0], ts[1],
+                                                                      ts[2], ts[3], laneoff, s, w, mn);
+            }
+        }
+    };
     auto boundary_piece = [&](const uint32_t (&lw)[4], const uint32_t (&p0)[4], const uint32_t (&p1)[4], int Tp) {
         // piece A: positions 16 A + k; k < B belongs to the first window, k == B - 1 completes it (src/read.cpp:219-224)
         const int rem = L - 16 * Tp;
@@ -376,8 +450,14 @@ __global__ void __launch_bounds__(WAVES * 64) flx_score_phred_regs(const PhredAr
             if (r >= n_rounds) goto done;
             const int sr = (H + u) % RR;  // ring round (compile-time)
             load_round(4 * sr, r);
+            if constexpr (BS >= 0) {
+                if (__builtin_expect(64 * (r + 1) <= Lmin, 1)) {
+                    steady_round(4 * sr);
+                    continue;
+                }
+            }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
+            for (int k = 0; k < 4; ++k) {  // a round that some lane ends in: piece by piece, masked where it has to be
                 const int t = 4 * sr + k;  // ring piece (compile-time)
                 const int Tp = 4 * r + k;  // stream piece
                 if (16 * Tp >= Lmax) break;
