@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "flx_bam_index", "flx_bam_to_fastq_dev", "flx_bam_to_fastq",
     "flx_bam_header", "flx_bam_from_fastq_bound", "flx_bam_from_fastq_dev", "flx_bgzf_bam_from_fastq",
     "flx_summary_q_edges", "flx_summary_dev", "flx_summary",
+    "flx_qsplit_table", "flx_qsplit_threshold", "flx_score_batch_qsplit", "flx_score_batch_qsplit_dev", "flx_pipeline_set_qsplit",
 ]
 
 
@@ -206,5 +207,10 @@ def load():
     L.flx_summary_q_edges.argtypes = [vp]
     L.flx_summary_dev.argtypes = [vp, u64, vp, vp, vp, vp, i32, C.POINTER(Summary)]
     L.flx_summary.argtypes = [vp, u64, vp, vp, vp, vp, i32, C.POINTER(Summary)]
+    L.flx_qsplit_table.argtypes = [vp]
+    L.flx_qsplit_threshold.argtypes = [dbl, C.POINTER(u64)]
+    L.flx_score_batch_qsplit.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.POINTER(Params), dbl, C.POINTER(Scores)]
+    L.flx_score_batch_qsplit_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.POINTER(Params), dbl, C.POINTER(Scores)]
+    L.flx_pipeline_set_qsplit.argtypes = [vp, dbl]
     _lib = L
     return L

@@ -118,8 +118,11 @@ class Context:
         return ms.value, n.value
 
     # ---- seam 2: per-read scoring (host buffers) -----------------------------------------------
-    def score_reads(self, plane, offsets, lengths, params, kmers=None, order=None, child_capacity=None):
-        """Batched Read::Read.  Returns a dict of numpy arrays in input order."""
+    def score_reads(self, plane, offsets, lengths, params, kmers=None, order=None, child_capacity=None, split_window_q=None):
+        """Batched Read::Read.  Returns a dict of numpy arrays in input order.  split_window_q (Phred mode only): the reads are
+        split at their low-quality windows (flx_score_batch_qsplit)."""
+        if split_window_q is not None and kmers is not None:
+            raise ValueError("split_window_q is for Phred mode")
         n = len(lengths)
         plane = np.ascontiguousarray(plane, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -147,9 +150,13 @@ class Context:
             s.child_ranges, s.child_mean_q, s.child_window_q, s.child_passed = (cr.ctypes.data, cm.ctypes.data,
                                                                               cw.ctypes.data, cp.ctypes.data)
             s.child_capacity = child_capacity
-            rc = self.L.flx_score_batch(self.h, kmers.h if kmers is not None else None, plane.ctypes.data,
-                                        plane.nbytes, offsets.ctypes.data, lengths.ctypes.data, ordp, n,
-                                        C.byref(params), C.byref(s))
+            if split_window_q is not None:
+                rc = self.L.flx_score_batch_qsplit(self.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data,
+                                                   ordp, n, C.byref(params), float(split_window_q), C.byref(s))
+            else:
+                rc = self.L.flx_score_batch(self.h, kmers.h if kmers is not None else None, plane.ctypes.data,
+                                            plane.nbytes, offsets.ctypes.data, lengths.ctypes.data, ordp, n,
+                                            C.byref(params), C.byref(s))
             if rc == 5 and s.n_children > child_capacity:  # FLX_ERR_CAPACITY: retry with the reported size
                 child_capacity = int(s.n_children)
                 continue
@@ -161,15 +168,18 @@ class Context:
         return out
 
     # ---- seam 2, streaming ----------------------------------------------------------------------
-    def score_stream(self, chunks, params, kmers=None, chunk_bytes=1 << 20, chunk_reads=1 << 12, grow=False):
+    def score_stream(self, chunks, params, kmers=None, chunk_bytes=1 << 20, chunk_reads=1 << 12, grow=False, split_window_q=None):
         """flx_pipeline_*: `chunks` is an iterable of lists of byte strings (Phred mode: qualities, k-mer mode: sequences).
         Every chunk is packed into the pipeline's pinned buffer and submitted; returns the same dict as score_reads for
-        all reads in submission order.  grow: enlarge the slots (flx_pipeline_reserve) for a chunk that does not fit."""
+        all reads in submission order.  grow: enlarge the slots (flx_pipeline_reserve) for a chunk that does not fit.
+        split_window_q: flx_pipeline_set_qsplit before the first chunk."""
         L = self.L
         pipe = C.c_void_p()
         self._check(L.flx_pipeline_create(self.h, kmers.h if kmers is not None else None, C.byref(params), chunk_bytes,
                                           chunk_reads, C.byref(pipe)))
         try:
+            if split_window_q is not None:
+                self._check(L.flx_pipeline_set_qsplit(pipe, float(split_window_q)))
             for strings in chunks:
                 n = len(strings)
                 lengths = np.array([len(x) for x in strings], dtype=np.int32)
@@ -452,6 +462,24 @@ class Context:
 
 SUMMARY_FIELDS = ("n", "bases", "min_length", "max_length", "median_length", "nx", "len_count", "len_bases",
                   "mean_q_count", "mean_q_bases", "window_q_count", "window_q_bases")
+
+
+def qsplit_table():
+    """E[0..255] of --split_window_q (flx_qsplit_table; no device needed)."""
+    e = np.zeros(256, dtype=np.uint32)
+    rc = _lib.load().flx_qsplit_table(e.ctypes.data)
+    if rc:
+        raise FlxError(rc, "flx_qsplit_table")
+    return e
+
+
+def qsplit_threshold(q):
+    """t of --split_window_q q (flx_qsplit_threshold; no device needed)."""
+    t = C.c_uint64()
+    rc = _lib.load().flx_qsplit_threshold(float(q), C.byref(t))
+    if rc:
+        raise FlxError(rc, "split_window_q must be greater than 0 and less than 100")
+    return int(t.value)
 
 
 def summary_dict(s):

@@ -37,6 +37,7 @@ struct Args {
     bool gzip = false;  // not a reference flag: --gzip writes stdout as BGZF, compressed on the GPU
     bool bam = false;   // not a reference flag: --bam writes stdout as BGZF-compressed unaligned BAM, packed and compressed on the GPU
     bool report_set = false; std::string report;  // not a reference flag: --report FILE receives a JSON summary of the reads before and after
+    bool split_window_q_set = false; double split_window_q = 0;  // not a reference flag: --split_window_q Q splits reads at windows below Q (Phred mode)
 };
 enum ParsingResult { GOOD, BAD, HELP, VERSION };
 
@@ -108,7 +109,7 @@ static long long read_ll(const std::string &name, const std::string &value, long
 // terminal on STDOUT (TIOCGWINSZ; indent 1 / 2 / 3 / 4 for widths up to 60 / 80 / 120 / beyond).  When stdout is no terminal the
 // reference reads the width out of an untouched `struct winsize` — 0 in practice: the description comes out one word per line and,
 // the other widths being unsigned differences that wrap around, nothing else is wrapped at all.  Both cases are restated here.
-// (--gpus, --gzip, --bam and --report, this binary's flags of its own, are documented in README.md: the menu is the reference's.)
+// (--gpus, --gzip, --bam, --report and --split_window_q, this binary's flags of its own, are documented in README.md: the menu is the reference's.)
 static std::vector<std::string> help_wrap(const std::string &in, size_t width, size_t first = 0) {  // src/args.h:94-149
     std::vector<std::string> out;
     size_t cur = first ? first : width, linesize = 0;
@@ -273,6 +274,7 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
             else if (flag == "gzip") a.gzip = true;
             else if (flag == "bam") a.bam = true;
             else if (flag == "report") { a.report = need("report"); a.report_set = true; }
+            else if (flag == "split_window_q") { a.split_window_q = read_double("float", need("split_window_q")); a.split_window_q_set = true; }
             else throw ParseError("Error: flag could not be matched: " + flag);
         }
     } catch (const ParseError &e) {
@@ -297,7 +299,7 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     for (auto &f : files)
         if (!file_exists(f)) { std::cerr << "Error: cannot find file: " << f << "\n"; return BAD; }
     if (!a.trim && !a.split_set && !a.target_bases_set && !a.keep_percent_set && !a.min_length_set && !a.max_length_set &&
-        !a.min_mean_q_set && !a.min_window_q_set) {
+        !a.min_mean_q_set && !a.min_window_q_set && !a.split_window_q_set) {
         std::cerr << "Error: no thresholds set, you must use one of the following options:\n";
         std::cerr << "target_bases, keep_percent, min_length, max_length, min_mean_q, min_window_q, trim, split\n";
         return BAD;
@@ -318,6 +320,10 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     if (a.window_size <= 0) { std::cerr << "Error: the value for --window_size must be a positive integer\n"; return BAD; }
     if (a.gpus < 1 || a.gpus > 64) { std::cerr << "Error: the value for --gpus must be between 1 and 64\n"; return BAD; }
     if (a.gzip && a.bam) { std::cerr << "Error: --gzip and --bam cannot be used together\n"; return BAD; }  // (BAM is BGZF already)
+    // --split_window_q: behind every check above, so the reference's messages keep their order
+    if (a.split_window_q_set && !(a.split_window_q > 0.0 && a.split_window_q < 100.0)) {
+        std::cerr << "Error: the value for --split_window_q must be greater than 0 and less than 100\n"; return BAD; }
+    if (a.split_window_q_set && some_reference) { std::cerr << "Error: --split_window_q cannot be used with an external reference\n"; return BAD; }
     return GOOD;
 }
 

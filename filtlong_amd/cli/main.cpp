@@ -80,7 +80,7 @@ static int exchange_totals(const Run &run, Reads2 &r2) {
             std::cerr << "\n";
         }
     }
-    if ((args.trim || args.split_set) && rank == 0) {  // src/main.cpp:155-166
+    if ((args.trim || args.split_set || args.split_window_q_set) && rank == 0) {  // src/main.cpp:155-166 (--split_window_q: "after splitting")
         if (args.trim && args.split_set) std::cerr << "  after trimming and splitting: ";
         else if (args.trim) std::cerr << "  after trimming: ";
         else std::cerr << "  after splitting: ";

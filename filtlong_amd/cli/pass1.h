@@ -50,7 +50,7 @@ static int open_reads_input(Run &run, ReadsInput &in) {
             if (file.open(args.input_reads) && bam_detect(file.p, file.n)) in.streamed = false;
         }
         in.data.bam = &kBamHooks;
-        in.data.keep_bam = args.bam && !args.trim && !args.split_set;  // (--bam: the reads go out whole, as their original records)
+        in.data.keep_bam = args.bam && !args.trim && !args.split_set && !args.split_window_q_set;  // (--bam: the reads go out whole, as their original records)
     }
     if (in.streamed ? !in.blocks.open(args.input_reads, true) : !in.data.open(args.input_reads)) {
         if (!in.streamed && !in.data.bam_error.empty()) std::cerr << "Error: could not read BAM input " << args.input_reads << ": " << in.data.bam_error << "\n";
@@ -108,7 +108,10 @@ struct Scorer {
     ~Scorer() { destroy(); }  // an error return must not leave the worker thread running into the runtime's teardown
     void destroy() { if (pipe) { flx_pipeline_destroy(pipe); pipe = nullptr; } }
     bool create_pipe() {  // if no record has come yet
-        return pipe || flx_pipeline_create(run.ctx, run.kmers_empty ? nullptr : run.kmers, &run.prm, chunk_bytes, chunk_reads, &pipe) == FLX_OK;
+        if (pipe) return true;
+        if (flx_pipeline_create(run.ctx, run.kmers_empty ? nullptr : run.kmers, &run.prm, chunk_bytes, chunk_reads, &pipe) != FLX_OK) return false;
+        // --split_window_q: the pipeline then splits the reads at their low-quality windows and returns children, as --split does
+        return !run.args.split_window_q_set || flx_pipeline_set_qsplit(pipe, run.args.split_window_q) == FLX_OK;
     }
 
     // Pack records [lo, lo + cnt) of a batch chunk by chunk; their lengths are appended to `lengths`.

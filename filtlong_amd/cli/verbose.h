@@ -34,6 +34,8 @@ static void print_read_blocks(std::ostream &os, const Run &run, const Pass1 &p, 
             if (from < lengths[i]) bad.push_back({from, lengths[i]});
         } else if (!run.kmers_empty && args.split_set && res.first[i] == -1 && lengths[i] > 0 && lengths[i] >= args.split) {
             bad.push_back({0, lengths[i]});
+        } else if (args.split_window_q_set && res.first[i] == -1 && lengths[i] > 0) {  // --split_window_q: every base lies in a bad window
+            bad.push_back({0, lengths[i]});
         }
         if (!bad.empty()) {
             os << "        bad ranges = ";

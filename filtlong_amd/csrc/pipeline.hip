@@ -42,6 +42,9 @@ struct flx_pipeline {
     flx_ctx *ctx = nullptr;
     const flx_kmerset *set = nullptr;
     flx_params params;
+    bool qsplit = false;     // flx_pipeline_set_qsplit: Phred mode, reads split at their low-quality windows
+    double qsplit_q = 0;
+    bool submitted = false;  // a chunk has been submitted
     uint64_t cap_bytes = 0, cap_reads = 0;
     Slot slot[2];
     int cur = 0;            // the slot the caller is packing
@@ -122,7 +125,7 @@ int score_slot(flx_pipeline *p, Slot &s) {
     const uint64_t n = s.n;
     FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, s.copied, 0));
     const bool kmer_mode = p->set && flx_kmerset_size(p->set) > 0;
-    const bool want_children = kmer_mode && (p->params.trim || p->params.split_set);
+    const bool want_children = (kmer_mode && (p->params.trim || p->params.split_set)) || p->qsplit;
     flx_scores dev;
     for (;;) {
         memset(&dev, 0, sizeof dev);
@@ -134,7 +137,8 @@ int score_slot(flx_pipeline *p, Slot &s) {
             dev.child_ranges = p->d_crng; dev.child_mean_q = p->d_cmean; dev.child_window_q = p->d_cwin;
             dev.child_passed = p->d_cpass; dev.child_capacity = p->child_cap;
         }
-        const int rc = flx_score_batch_dev(ctx, p->set, s.d_plane, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, &p->params, &dev);
+        const int rc = p->qsplit ? flx_score_batch_qsplit_dev(ctx, s.d_plane, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, &p->params, p->qsplit_q, &dev)
+                                 : flx_score_batch_dev(ctx, p->set, s.d_plane, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, &p->params, &dev);
         if (rc == FLX_ERR_CAPACITY && dev.n_children > p->child_cap) {
             FLX_CHECK(grow_children(p, dev.n_children + dev.n_children / 4));
             continue;
@@ -238,6 +242,19 @@ extern "C" int flx_pipeline_create(flx_ctx *ctx, const flx_kmerset *set, const f
     return FLX_OK;
 }
 
+extern "C" int flx_pipeline_set_qsplit(flx_pipeline *p, double q) {
+    if (!p) return FLX_ERR_INVALID;
+    flx_ctx *ctx = p->ctx;
+    if (p->set && flx_kmerset_size(p->set) > 0) return flx_fail(ctx, FLX_ERR_STATE, "split_window_q is for Phred mode: the pipeline has a k-mer set");
+    if (p->submitted) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_qsplit after flx_pipeline_submit");
+    uint64_t t = 0;
+    if (flx_qsplit_threshold(q, &t) != FLX_OK) return flx_fail(ctx, FLX_ERR_INVALID, "split_window_q must be greater than 0 and less than 100");
+    if (p->params.trim || p->params.split_set) return flx_fail(ctx, FLX_ERR_INVALID, "trim/split need a k-mer set: not with split_window_q");
+    p->qsplit = true;
+    p->qsplit_q = q;
+    return FLX_OK;
+}
+
 extern "C" int flx_pipeline_reserve(flx_pipeline *p, uint64_t chunk_plane_bytes, uint64_t chunk_reads) {
     if (!p) return FLX_ERR_INVALID;
     flx_ctx *ctx = p->ctx;
@@ -296,6 +313,7 @@ extern "C" int flx_pipeline_submit(flx_pipeline *p, uint64_t plane_bytes, const 
         if (lengths[i] < 0 || (offsets[i] & 15) || offsets[i] + (((uint64_t)lengths[i] + 15) & ~15ull) > plane_bytes)
             return flx_fail(ctx, FLX_ERR_INVALID, "read %llu: offset must be 16-byte aligned and inside the chunk", (unsigned long long)i);
     p->handed_out = false;
+    p->submitted = true;
     s.n = n_reads;
     s.plane_bytes = plane_bytes;
     if (n_reads) {

@@ -57,9 +57,11 @@ extern "C" int flx_score_batch_dev(flx_ctx *ctx, const flx_kmerset *set, const v
                               (const int32_t *)d_lengths, (const uint32_t *)d_order, n_reads, params, out);
 }
 
-extern "C" int flx_score_batch(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *plane, uint64_t plane_bytes,
-                               const uint64_t *offsets, const int32_t *lengths, const uint32_t *order,
-                               uint64_t n_reads, const flx_params *params, flx_scores *out) {
+// the host-array form of a scoring call: everything staged through device buffers of the call's own.  split_window_q (not NULL:
+// flx_score_batch_qsplit) sends the batch through flx_score_batch_qsplit_dev instead of flx_score_batch_dev.
+static int score_batch_host(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *plane, uint64_t plane_bytes,
+                            const uint64_t *offsets, const int32_t *lengths, const uint32_t *order,
+                            uint64_t n_reads, const flx_params *params, const double *split_window_q, flx_scores *out) {
     FLX_CHECK(validate_common(ctx, n_reads, plane_bytes, params, out));
     if (n_reads == 0) {
         out->n_children = 0;
@@ -77,7 +79,7 @@ extern "C" int flx_score_batch(flx_ctx *ctx, const flx_kmerset *set, const uint8
     pt.mark("validate");
     FLX_HIP(ctx, hipSetDevice(ctx->device));
     const bool kmer_mode = set && flx_kmerset_size(set) > 0;
-    const bool want_children = kmer_mode && (params->trim || params->split_set);
+    const bool want_children = (kmer_mode && (params->trim || params->split_set)) || split_window_q;
     if (want_children && !out->child_offsets)
         return flx_fail(ctx, FLX_ERR_INVALID, "trim/split requested but child outputs are NULL");
 
@@ -134,8 +136,10 @@ extern "C" int flx_score_batch(flx_ctx *ctx, const flx_kmerset *set, const uint8
     FLX_HIP(ctx, hipMemsetAsync(d_win.p, 0xA5, n_reads * 8, ctx->stream));
     FLX_HIP(ctx, hipMemsetAsync(d_pass.p, 0xA5, n_reads, ctx->stream));
     pt.mark("small uploads + alloc");
-    int rc = flx_score_batch_dev(ctx, set, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr,
-                                 n_reads, params, &dev);
+    int rc = split_window_q ? flx_score_batch_qsplit_dev(ctx, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr, n_reads,
+                                                         params, *split_window_q, &dev)
+                            : flx_score_batch_dev(ctx, set, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr,
+                                                  n_reads, params, &dev);
     pt.mark("kernels");
     if (rc != FLX_OK) {
         out->n_children = dev.n_children;  // on FLX_ERR_CAPACITY this is the required capacity
@@ -163,4 +167,19 @@ extern "C" int flx_score_batch(flx_ctx *ctx, const flx_kmerset *set, const uint8
     FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pt.mark("download");
     return FLX_OK;
+}
+
+extern "C" int flx_score_batch(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *plane, uint64_t plane_bytes,
+                               const uint64_t *offsets, const int32_t *lengths, const uint32_t *order,
+                               uint64_t n_reads, const flx_params *params, flx_scores *out) {
+    return score_batch_host(ctx, set, plane, plane_bytes, offsets, lengths, order, n_reads, params, nullptr, out);
+}
+
+extern "C" int flx_score_batch_qsplit(flx_ctx *ctx, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets,
+                                      const int32_t *lengths, const uint32_t *order, uint64_t n_reads, const flx_params *params,
+                                      double split_window_q, flx_scores *out) {
+    uint64_t t = 0;
+    if (ctx && flx_qsplit_threshold(split_window_q, &t) != FLX_OK)
+        return flx_fail(ctx, FLX_ERR_INVALID, "split_window_q must be greater than 0 and less than 100");
+    return score_batch_host(ctx, nullptr, plane, plane_bytes, offsets, lengths, order, n_reads, params, &split_window_q, out);
 }

@@ -170,6 +170,32 @@ int flx_score_batch_dev(flx_ctx *ctx, const flx_kmerset *set, const void *d_plan
                         const flx_params *params, flx_scores *out_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * seam 2, Phred mode with --split_window_q (added under version 4; the reference has no counterpart: its --trim / --split need
+ * an external reference and --min_window_q drops the whole read): reads are split at their low-quality windows.  Defined on
+ * integers, so every decomposition gives the same answer:
+ *   E[b], uint32, for quality byte b: q = (signed char)b - 33; 2^32 - 1 for q <= 0, else min(2^32 - 1, floor(10^(-q/10) 2^32 + 0.5))
+ *   t = (uint64_t)floor((100 - Q) / 100 * 2^32) in IEEE double, 0 < Q < 100 on the scale of --min_window_q
+ *   with W = params->window_size, L the read's length and n = min(W, L): the window ending at base j, n - 1 <= j < L, is bad iff
+ *   the sum of E over bases j - n + 1 .. j is > t * n (uint64).  Every base inside a bad window is removed; a child is a maximal
+ *   run of the bases left, (start, end) half-open and 0-based.
+ * The plane holds the QUALITY strings, laid out as for flx_score_batch.  A read keeps the mean_q / window_q of flx_score_batch; a
+ * child gets the bits flx_score_batch gives its quality substring as a read of its own, and its pass flag from the hard cut-offs
+ * applied to it.  A read without a bad window has no children and goes on as itself; one with bad windows and no base left has no
+ * children and passed = 0.  first / last (when not NULL) hold the first kept base and one past the last: 0 and L without a bad
+ * window, -1 and -1 when nothing is kept.  out->child_offsets is required; FLX_ERR_CAPACITY as for --trim / --split
+ * (out->n_children is then the capacity needed).  params->trim and params->split_set must be 0.
+ *   flx_qsplit_table / flx_qsplit_threshold   host only, no device: E and t (FLX_ERR_INVALID unless 0 < q < 100)
+ * ---------------------------------------------------------------------------------------- */
+int flx_qsplit_table(uint32_t e[256]);
+int flx_qsplit_threshold(double q, uint64_t *t);
+int flx_score_batch_qsplit(flx_ctx *ctx, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets,
+                           const int32_t *lengths, const uint32_t *order, uint64_t n_reads, const flx_params *params,
+                           double split_window_q, flx_scores *out);
+int flx_score_batch_qsplit_dev(flx_ctx *ctx, const void *d_plane, uint64_t plane_bytes, const void *d_offsets,
+                               const void *d_lengths, const void *d_order, uint64_t n_reads, const flx_params *params,
+                               double split_window_q, flx_scores *out_dev);
+
+/* ------------------------------------------------------------------------------------------
  * between seam 2 and seam 3 — the reads2 gather     (replaces src/main.cpp:138-147)
  *
  * reads2 = file order with every trimmed / split parent replaced IN PLACE by its children.  Gathers what the global
@@ -265,6 +291,10 @@ int flx_rank_and_cut_sharded_dev(flx_ctx *ctx, uint64_t n_total, const void *d_m
 typedef struct flx_pipeline flx_pipeline;
 int flx_pipeline_create(flx_ctx *ctx, const flx_kmerset *set /* NULL or empty: Phred mode */, const flx_params *params,
                         uint64_t chunk_plane_bytes, uint64_t chunk_reads, flx_pipeline **out);
+/* --split_window_q for a Phred-mode pipeline (added under version 4): every chunk then goes through flx_score_batch_qsplit_dev and
+ * flx_pipeline_finish returns the children in its global CSR.  Before the first submit; FLX_ERR_STATE on a pipeline with a non-empty
+ * set or after a submit, FLX_ERR_INVALID unless 0 < q < 100. */
+int flx_pipeline_set_qsplit(flx_pipeline *p, double q);
 int flx_pipeline_next_buffer(flx_pipeline *p, uint8_t **plane, uint64_t *capacity_bytes, uint64_t *capacity_reads);
 /* Grow both slots to at least this capacity (never shrinks; waits for the chunks in flight first).  For callers that learn
  * the longest read only while streaming.  Not between next_buffer and submit. */
