@@ -16,7 +16,8 @@
 //     4 bases (12 gathers issued back to back, the FP64 chain follows as data arrives, one counted wait per base); left
 //     to hipcc the unrolled loop gets its gathers hoisted away from the chain and spills.  In the static window-250
 //     kernel a whole round's 16 statements form one chain: each computes the next one's addresses between its last
-//     gather and its first wait, where the wave would otherwise sit out the gather latency (steady_round).
+//     gather and its first wait, where the wave would otherwise sit out the gather latency (steady_round); while every lane
+//     has a whole ring revolution ahead, its five rounds run straight-line, with no compare or branch between them.
 //   * optional bank-private tables (FLX_PHRED_TABLES=private): every table entry is replicated once per bank pair
 //     (lane l reads copy l % 32), so a gather never has a bank conflict whatever the quality distribution is
 //     (plain tables: entries e and e+32 collide; a wide Phred range costs up to 1.5x per gather).  128 entries per
@@ -443,7 +444,23 @@ __global__ void __launch_bounds__(WAVES * 64) flx_score_phred_regs(const PhredAr
         }
     }
     // ---- main loop: one ring revolution per iteration, starting at ring round H % RR -------------------------
-    for (int rb = H;; rb += RR) {
+    {
+    int rb = H;
+    if constexpr (BS >= 0) {
+        // Fast revolutions: while every lane has all RR rounds of the coming ring revolution whole, the revolution runs straight-line:
+        // 16 RR statements and the slot reads, no compare or branch between the rounds.  Lmin is fixed for the group, so whole
+        // rounds come first: decided once per revolution, and once it fails the per-round code below takes the rest of the group
+        // (fewer than RR whole rounds, then the rounds some lane ends in).
+        while (64 * (rb + RR) <= Lmin) {
+#pragma unroll
+            for (int u = 0; u < RR; ++u) {
+                load_round(4 * ((H + u) % RR), rb + u);
+                steady_round(4 * ((H + u) % RR));
+            }
+            rb += RR;
+        }
+    }
+    for (;; rb += RR) {
 #pragma unroll
         for (int u = 0; u < RR; ++u) {
             const int r = rb + u;
@@ -464,6 +481,7 @@ __global__ void __launch_bounds__(WAVES * 64) flx_score_phred_regs(const PhredAr
                 steady_piece(ring[t], ring[(t + R - A - 1) % R], ring[(t + R - A) % R], Tp);
             }
         }
+    }
     }
 done:
     if (live) {
