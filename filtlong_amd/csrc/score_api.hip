@@ -131,10 +131,24 @@ static int score_batch_host(flx_ctx *ctx, const flx_kmerset *set, const uint8_t 
     // The outputs start out as a pattern no result can be (0xA5...: a huge negative quality, pass flag 165): device memory that
     // comes back from the allocator holds the previous call's results at the same addresses, and a kernel that wrote nothing
     // would otherwise hand back yesterday's right answers (round 5: that is how the fold kernels with both streams from global
-    // memory were found dead — their launch had failed silently while the tests compared stale buffers).
+    // memory were found dead — their launch had failed silently while the tests compared stale buffers); first / last, the child
+    // CSR and the children's outputs, which --split and --split_window_q write, start out the same way (a range of 0xA5A5A5A5).
     FLX_HIP(ctx, hipMemsetAsync(d_mean.p, 0xA5, n_reads * 8, ctx->stream));
     FLX_HIP(ctx, hipMemsetAsync(d_win.p, 0xA5, n_reads * 8, ctx->stream));
     FLX_HIP(ctx, hipMemsetAsync(d_pass.p, 0xA5, n_reads, ctx->stream));
+    if (dev.first) {
+        FLX_HIP(ctx, hipMemsetAsync(d_first.p, 0xA5, n_reads * 4, ctx->stream));
+        FLX_HIP(ctx, hipMemsetAsync(d_last.p, 0xA5, n_reads * 4, ctx->stream));
+    }
+    if (dev.child_offsets) {
+        FLX_HIP(ctx, hipMemsetAsync(d_coff.p, 0xA5, (n_reads + 1) * 8, ctx->stream));
+        if (out->child_capacity) {
+            FLX_HIP(ctx, hipMemsetAsync(d_crng.p, 0xA5, out->child_capacity * 8, ctx->stream));
+            FLX_HIP(ctx, hipMemsetAsync(d_cmean.p, 0xA5, out->child_capacity * 8, ctx->stream));
+            FLX_HIP(ctx, hipMemsetAsync(d_cwin.p, 0xA5, out->child_capacity * 8, ctx->stream));
+            FLX_HIP(ctx, hipMemsetAsync(d_cpass.p, 0xA5, out->child_capacity, ctx->stream));
+        }
+    }
     pt.mark("small uploads + alloc");
     int rc = split_window_q ? flx_score_batch_qsplit_dev(ctx, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr, n_reads,
                                                          params, *split_window_q, &dev)

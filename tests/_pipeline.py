@@ -27,13 +27,24 @@ class OracleBackend:
     def kmers_empty(self, ks):
         return ks is None or len(ks) == 0
 
-    def score(self, reads, pkw, ks):
+    def score(self, reads, pkw, ks, split_window_q=None):
         p = _oracle.make_params(**pkw)
         kmer_mode = not self.kmers_empty(ks)
         res = []
         for name, seq, qual in reads:
             o = _oracle.score_read(seq, qual if qual is not None else b"\0" * len(seq), p, ks if kmer_mode else None)
             res.append(o)
+        if split_window_q is not None:
+            # --split_window_q (Phred mode): the children are the model's, each scored as a read of its own on its quality substring;
+            # the parents keep their scores and a wholly bad read fails
+            import _qsplit_model as model
+            assert not kmer_mode
+            off, rng, first, last, wholly = model.split_batch([qual for _, _, qual in reads], pkw.get("window_size", 250), split_window_q)
+            for i, ((name, seq, qual), o) in enumerate(zip(reads, res)):
+                ranges = [(int(s), int(e)) for s, e in rng[int(off[i]):int(off[i + 1])]]
+                kids = [_oracle.score_read(None, qual[s:e], p) for s, e in ranges]
+                o.update(first=int(first[i]), last=int(last[i]), child_ranges=ranges, passed=0 if wholly[i] else o["passed"],
+                         children=[{k: c[k] for k in ("length", "mean_q", "window_q", "passed")} for c in kids])
         return res
 
     def reads2(self, lengths, sc):
@@ -66,14 +77,14 @@ class HipBackend:
     def kmers_empty(self, ks):
         return ks is None or ks.empty()
 
-    def score(self, reads, pkw, ks):
+    def score(self, reads, pkw, ks, split_window_q=None):
         api = self.api
         p = api.make_params(**pkw)
         kmer_mode = not self.kmers_empty(ks)
         strings = [(seq if kmer_mode else qual) for _, seq, qual in reads]
         plane, offsets, lengths = api.pack_reads(strings)
         order = api.length_order(lengths)
-        o = self.ctx.score_reads(plane, offsets, lengths, p, kmers=ks if kmer_mode else None, order=order)
+        o = self.ctx.score_reads(plane, offsets, lengths, p, kmers=ks if kmer_mode else None, order=order, split_window_q=split_window_q)
         res = []
         co = o["child_offsets"]
         for i in range(len(reads)):
@@ -95,7 +106,21 @@ class HipBackend:
         r = self.ctx.rank_and_cut(mean_q, window_q, length, passed, length_weight=lw, mean_q_weight=mw,
                                   window_q_weight=ww, **kw)
         rep = r["report"]
+        self.last_report = rep
         return r["passed"], rep.target_bases, rep.kept_bases, rep.outcome
+
+
+class SplitWindowQ:
+    """A backend whose scoring call splits at low-quality windows (--split_window_q q); everything else is the backend's own."""
+
+    def __init__(self, backend, q):
+        self.backend, self.q = backend, q
+
+    def __getattr__(self, name):
+        return getattr(self.backend, name)
+
+    def score(self, reads, pkw, ks):
+        return self.backend.score(reads, pkw, ks, split_window_q=self.q)
 
 
 def run_filter(backend, reads, ks, pkw=None, target_bases=None, keep_percent=None, lw=1.0, mw=1.0, ww=1.0):

@@ -2,7 +2,8 @@
 substrings, named name_start-end like the children of --split, and the untouched reads whole; a wholly bad read is gone; the
 "after splitting" line, the --verbose blocks and --report's scored summary are the model's; the reference binary, fed the children as
 reads of their own, prints their blocks' numbers; and --gzip, a streamed gzip input, --gpus 2, a BAM input and --bam give the same
-reads."""
+reads.  With --target_bases / --keep_percent the kept reads and the cut's report are those of the oracle's rank_and_cut over the
+model's children and the whole reads together, by the same roads."""
 import gzip
 import json
 import os
@@ -87,6 +88,32 @@ class Expected:
     def after_splitting(self):
         e = self.entries()
         return b"  after splitting: %d reads (%d bp)\n" % (len(e), sum(len(s) for _, s, _, _ in e))
+
+    def reads2_bases(self):
+        return sum(len(s) for _, s, _, _ in self.entries())
+
+    def filtered(self, target_bases=None, keep_percent=None, min_length=None, lw=1.0):
+        """(stdout, [the "target:" line, the line behind it]) of a run with --target_bases / --keep_percent: every reads2 entry
+        scored by the oracle as a read of its own (a wholly bad read fails, and still counts in the statistics), the oracle's
+        rank_and_cut with total_bases the INPUT's bases."""
+        e = self.entries()
+        p = _oracle.make_params(window_size=self.w, min_length=min_length)
+        sc = [_oracle.score_read(None, q, p) for _, _, q, _ in e]
+        passed = np.array([s["passed"] if ok else 0 for s, (_, _, _, ok) in zip(sc, e)], dtype=np.uint8)
+        r = _oracle.rank_and_cut(np.array([s["mean_q"] for s in sc]), np.array([s["window_q"] for s in sc]),
+                                 np.array([len(s) for _, s, _, _ in e], dtype=np.int32), passed, lw=lw, target_bases=target_bases,
+                                 keep_percent=keep_percent, total_bases=sum(len(s) for _, s, _ in self.reads))
+        second = {1: b"  not enough reads to reach target\n", 2: b"  reads already fall below target after filtering\n",
+                  3: b"  keeping %d bp\n" % r["kept_bases"]}[r["outcome"]]
+        return fastq_bytes([x[:3] for x, keep in zip(e, r["passed"]) if keep]), [b"  target: %d bp\n" % r["target_bases"], second]
+
+
+def cut_lines(err):
+    """The "target:" line of a run's stderr and the line behind it."""
+    lines = err.split(b"\n")
+    at = [k for k, l in enumerate(lines) if l.startswith(b"  target: ")]
+    assert len(at) == 1, err[-2000:]
+    return [lines[at[0]] + b"\n", lines[at[0] + 1] + b"\n"]
 
 
 @pytest.fixture(scope="module")
@@ -205,3 +232,50 @@ def test_bam_out_is_the_children_without_tags(made):
         records, end = _bam.walk_model(data)
         assert end == _bam.END and _bam.expected_fastq(records)[0] == made["want"].stdout()
         assert b"RGZ" not in data and all(r["flag"] == 4 for r in records)
+
+
+def filtered_run(want, args, path, extra=None, **kw):
+    """One run with a cut: stdout and the two lines of the cut's report are the oracle's over the model's children."""
+    out_want, lines_want = want.filtered(**kw)
+    rc, out, err = run(ARGS + args + [path], extra)
+    assert rc == 0 and b"Error" not in err, err[-2000:]
+    assert cut_lines(err) == lines_want and want.after_splitting() in err
+    assert out == out_want, "stdout differs: %d bytes, %d expected" % (len(out), len(out_want))
+    return out_want, lines_want
+
+
+def test_target_bases_and_keep_percent_over_the_children(made):
+    """The global stage behind the split: the cut ranks children and whole reads together, a wholly bad read counts in the quality
+    statistics and the percentage is of the input's bases, not of what is left after splitting."""
+    want = made["want"]
+    b2 = want.reads2_bases()
+    outs = []
+    for t in (b2 // 3, 2 * b2 // 3):
+        out, lines = filtered_run(want, ["--target_bases", str(t)], made["fastq"], target_bases=t)
+        assert lines[0] == b"  target: %d bp\n" % t and lines[1].startswith(b"  keeping ")
+        outs.append(out)
+    assert 0 < len(outs[0]) < len(outs[1]) < len(want.stdout())
+    assert re.search(rb"^@read_\d+_\d+-\d+$", outs[0], re.M), "no child among the kept reads"
+    out, lines = filtered_run(want, ["--keep_percent", "60"], made["fastq"], keep_percent=60.0)
+    total = sum(len(s) for _, s, _ in made["reads"])
+    assert lines[0] == b"  target: %d bp\n" % int(0.6 * total) and b2 < total
+    t = b2 // 2
+    out, _ = filtered_run(want, ["--target_bases", str(t), "--min_length", "500", "--length_weight", "0"], made["fastq"],
+                          target_bases=t, min_length=500, lw=0.0)
+    assert 0 < len(out) < len(want.stdout(min_length=500))
+    # more than reads2 holds, less than the input: the reads "already fall below", they are not "not enough"
+    _, lines = filtered_run(want, ["--target_bases", str(b2 + 1)], made["fastq"], target_bases=b2 + 1)
+    assert lines[1] == b"  reads already fall below target after filtering\n" and b2 + 1 < total
+
+
+def test_the_cut_by_every_road(made):
+    want = made["want"]
+    t = want.reads2_bases() // 3
+    filtered_run(want, ["--target_bases", str(t), "--gpus", "2"], made["fastq"], shim_env(), target_bases=t)
+    filtered_run(want, ["--keep_percent", "60"], made["gz"], {"FLX_CLI_BLOCK_BYTES": "20000", "FLX_CLI_CHUNK_BYTES": "30000"}, keep_percent=60.0)
+    out_want, lines_want = want.filtered(target_bases=t)
+    rc, out, err = run(ARGS + ["--target_bases", str(t), "--bam", made["fastq"]])
+    assert rc == 0 and cut_lines(err) == lines_want
+    data, info = _bgzf.validate(out)
+    records, end = _bam.walk_model(data)
+    assert info["eof"] and end == _bam.END and _bam.expected_fastq(records)[0] == out_want

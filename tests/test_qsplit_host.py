@@ -1,7 +1,8 @@
 """The record core of --split_window_q (csrc/qsplit.h) without a GPU: tests/qsplit_host.cpp walks it on the host, built with -O2
 and again with the address and undefined-behaviour sanitizers (a stand-alone program: no preload, no Python, no GPU; every quality
 string sits in a heap block of exactly its size).  It is held, for equality, against tests/_qsplit_model.py: the table from 60-digit
-decimals, the children as the runs of bases that no bad window covers."""
+decimals, the children as the runs of bases that no bad window covers.  Window sizes go to 5000: the sizes at which the GPU tests
+hold the detection kernel against the same model (tests/test_qsplit_gpu_deep.py)."""
 import os
 import struct
 import subprocess
@@ -64,8 +65,8 @@ def test_table_and_threshold(program, tmp_path):
 def test_lengths_around_the_window(program, tmp_path):
     rng = np.random.default_rng(11)
     cases = []
-    for w in (1, 2, 7, 250):
-        for length in sorted({0, 1, max(w - 1, 0), w, w + 1, 2 * w - 1, 2 * w}):
+    for w in (1, 2, 7, 250, 1026, 2048, 5000):  # (the last three: windows deeper than one step of the detection kernel)
+        for length in sorted({0, 1, max(w - 1, 0), w, w + 1, 2 * w - 1, 2 * w} | ({2 * w + 1, 3 * w + 7} if w > 1000 else set())):
             for q in (50, 85, 99):
                 t = model.threshold(q)
                 cases.append((w, t, model.junk_read(rng, length, [])))                      # nothing bad
@@ -136,3 +137,19 @@ def test_random_reads(program, tmp_path):
                 cases.append((w, t, model.junk_read(rng, length, st)))
     got = check(program, tmp_path, cases)
     assert sum(len(r) >= 2 for r, _, _, _ in got) > 20
+    # windows deeper than one step of the detection kernel, reads up to 3 W + 7 bases, stretches up to W
+    deep = []
+    for w in (1026, 2048, 5000):
+        for q in (50, 85, 90, 99):
+            t = model.threshold(q)
+            for i in range(12):
+                length = int(rng.integers(0, 3 * w + 8))
+                k = int(rng.integers(0, 4))
+                st = [(a, a + int(rng.integers(1, w + 1))) for a in rng.integers(0, max(length, 1), size=k)]
+                if i % 2:  # two children need 2 W + 1 bases and a stretch away from both ends
+                    length = int(rng.integers(2 * w + 1, 3 * w + 8))
+                    a = int(rng.integers(length // 2 - w // 4, length // 2))
+                    st = [(a, a + int(rng.integers(w // 4, w // 2)))]
+                deep.append((w, t, model.junk_read(rng, length, st)))
+    got = check(program, tmp_path, deep)
+    assert sum(len(r) >= 2 for r, _, _, _ in got) > 5
