@@ -1,118 +1,48 @@
 // bam.hip — unaligned BAM records turned into FASTQ text on the GPU: the layer inside the BGZF container of bgzf_inflate.hip.
 //
 // flx_bam_index         (host) the header and the chain of block_size fields: one load per record, serial, so it stays on the host;
-// k_bam_sizes           one thread per record: validates it (bam_record.h: read_record) and gives its text size, its number of
-//                       emit items and whether it is skipped; the tile's sums;
-// k_bam_scan_tiles      one workgroup: exclusive scan of the tiles' sums, the totals and the lowest bad record;
-// k_bam_offsets         the scan inside each tile: out_off[k], item_off[k], and the record of every emit item;
+// the layout pass       (record_pipeline.h) with the Decode codec below: a record is validated (bam_record.h: read_record) and
+//                       gives its text size, its number of emit items and whether it is skipped;
 // k_bam_emit            one workgroup per (record, chunk of BAM_CHUNK bases), grid-stride over the items: a 4 Mbp record is a
 //                       thousand items spread over the chip, a 200-base record is one.
 // The emit kernel moves ~1.5 bytes in and 2 bytes out per base.  Output positions fall on every alignment, so each of the two
 // lines of a chunk is written as head bytes up to the next 16-byte boundary of the OUTPUT address, whole aligned 16-byte stores
 // (one lane each: 16 bases from 8 or 9 packed bytes through a 256-entry table of character pairs in LDS, 16 qualities clamped four
 // to a word), and tail bytes.  Loads take exactly the bytes they need at whatever address they lie (the hardware's unaligned
-// global loads): nothing outside a record is read, and a record was validated against its own range by k_bam_sizes.
+// global loads): nothing outside a record is read, and a record was validated against its own range by the layout pass.
 #include "flx_internal.h"
 #include "bam_record.h"
+#include "host_pieces.h"
+#include "record_pipeline.h"
 
 using namespace bam;
+using recpipe::kStateWords;
 
 namespace {
 
-constexpr int BAM_NT = 256;                  // threads per workgroup, records per tile
-constexpr uint32_t BAM_CHUNK = 16 * BAM_NT;  // bases per emit item: one 16-byte store per lane and line
-constexpr unsigned kEmitBlocksPerCU = 8;
+constexpr int BAM_NT = recpipe::NT;             // threads per workgroup
+constexpr uint32_t BAM_CHUNK = recpipe::CHUNK;  // bases per emit item: one 16-byte store per lane and line
 
-struct Sum3 {
-    unsigned long long bytes, items, skipped;
-};
-// the call's state on the device (zeroed before the launches): [0] text bytes, [1] emit items, [2] skipped records,
-// [3] n_records - the lowest bad record (0: none; an atomicMax over the bad records)
-constexpr int kStateWords = 4;
-
-__device__ __forceinline__ Sum3 add3(Sum3 a, Sum3 b) { return {a.bytes + b.bytes, a.items + b.items, a.skipped + b.skipped}; }
-
-// exclusive scan of one value per thread over the workgroup; *total gets the sum (every thread)
-__device__ __forceinline__ Sum3 block_excl_scan3(Sum3 v, Sum3 *total) {
-    __shared__ Sum3 buf[2][BAM_NT];
-    const int t = threadIdx.x;
-    int cur = 0;
-    buf[0][t] = v;
-    __syncthreads();
-    for (int d = 1; d < BAM_NT; d <<= 1) {
-        Sum3 x = buf[cur][t];
-        if (t >= d) x = add3(x, buf[cur][t - d]);
-        buf[cur ^ 1][t] = x;
-        cur ^= 1;
-        __syncthreads();
+// what record k of the index gives: zero sums and bad for a record that is not valid inside [off[k], off[k+1]) of in[0, n)
+struct Decode {
+    using Sums = recpipe::Sum3;
+    static size_t extra_bytes(uint64_t n_rec) { return (n_rec + 1) * 8; }  // text offsets of a call that has no array for them
+    const uint8_t *in;
+    uint64_t n;
+    const uint64_t *off;
+    __device__ __forceinline__ Sums measure(uint64_t k, bool *bad) const {
+        const uint64_t at = off[k], end = off[k + 1];
+        Rec r;
+        *bad = !(at <= end && end <= n) || read_record(in, end, at, r) != REC_OK || r.end != end;
+        if (*bad) return {0, 0, 0};
+        const uint64_t bytes = text_size(r);
+        return {bytes, bytes ? ((uint64_t)r.l_seq + BAM_CHUNK - 1) / BAM_CHUNK : 0, bytes ? 0ull : 1ull};
     }
-    const Sum3 incl = buf[cur][t];
-    *total = buf[cur][BAM_NT - 1];
-    __syncthreads();  // (the next call writes buf[0])
-    return {incl.bytes - v.bytes, incl.items - v.items, incl.skipped - v.skipped};
-}
-
-// what record k of the index gives: zero sums and *bad for a record that is not valid inside [off[k], off[k+1]) of in[0, n)
-__device__ __forceinline__ Sum3 record_sums(const uint8_t *in, uint64_t n, const uint64_t *off, uint64_t k, bool *bad) {
-    const uint64_t at = off[k], end = off[k + 1];
-    Rec r;
-    *bad = !(at <= end && end <= n) || read_record(in, end, at, r) != REC_OK || r.end != end;
-    if (*bad) return {0, 0, 0};
-    const uint64_t bytes = text_size(r);
-    return {bytes, bytes ? ((uint64_t)r.l_seq + BAM_CHUNK - 1) / BAM_CHUNK : 0, bytes ? 0ull : 1ull};
-}
-
-__global__ void __launch_bounds__(BAM_NT) k_bam_sizes(const uint8_t *in, uint64_t n, const uint64_t *off, uint64_t n_rec, Sum3 *tile_sums,
-                                                      unsigned long long *state) {
-    const uint64_t k = (uint64_t)blockIdx.x * BAM_NT + threadIdx.x;
-    Sum3 v = {0, 0, 0};
-    if (k < n_rec) {
+    __device__ __forceinline__ Sums recall(uint64_t k) const {
         bool bad;
-        v = record_sums(in, n, off, k, &bad);
-        if (bad) atomicMax(&state[3], (unsigned long long)(n_rec - k));
+        return measure(k, &bad);
     }
-    Sum3 total;
-    block_excl_scan3(v, &total);
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(BAM_NT) k_bam_scan_tiles(Sum3 *tile_sums, uint64_t n_tiles, unsigned long long *state) {
-    Sum3 carry = {0, 0, 0};
-    for (uint64_t base = 0; base < n_tiles; base += BAM_NT) {
-        const uint64_t i = base + threadIdx.x;
-        const Sum3 v = i < n_tiles ? tile_sums[i] : Sum3{0, 0, 0};
-        Sum3 total;
-        const Sum3 ex = block_excl_scan3(v, &total);
-        if (i < n_tiles) tile_sums[i] = add3(carry, ex);
-        carry = add3(carry, total);
-    }
-    if (threadIdx.x == 0) {
-        state[0] = carry.bytes;
-        state[1] = carry.items;
-        state[2] = carry.skipped;
-    }
-}
-
-__global__ void __launch_bounds__(BAM_NT) k_bam_offsets(const uint8_t *in, uint64_t n, const uint64_t *off, uint64_t n_rec, const Sum3 *tile_sums,
-                                                        const unsigned long long *state, uint64_t *out_off, uint64_t *item_off,
-                                                        uint32_t *item_rec, uint64_t item_cap) {
-    const uint64_t k = (uint64_t)blockIdx.x * BAM_NT + threadIdx.x;
-    Sum3 v = {0, 0, 0};
-    bool bad = true;
-    if (k < n_rec) v = record_sums(in, n, off, k, &bad);
-    Sum3 total;
-    const Sum3 ex = add3(tile_sums[blockIdx.x], block_excl_scan3(v, &total));
-    if (k >= n_rec) return;
-    out_off[k] = ex.bytes;
-    item_off[k] = ex.items;
-    if (k == n_rec - 1) {
-        out_off[n_rec] = state[0];
-        item_off[n_rec] = state[1];
-    }
-    // (item_cap is the host's bound of the item count, n_rec + bytes / BAM_CHUNK: records whose ranges do not overlap cannot
-    // exceed it, and the test keeps any others from writing outside the array)
-    for (uint64_t c = 0; c < v.items && ex.items + c < item_cap; ++c) item_rec[ex.items + c] = (uint32_t)k;
-}
+};
 
 // 16 bases whose first is base i of the record, as the 8 packed bytes that hold them in order (byte m: bases i + 2m, i + 2m + 1)
 __device__ __forceinline__ uint64_t load_bases16(const uint8_t *seq, uint64_t i) {
@@ -141,9 +71,7 @@ __device__ __forceinline__ void emit_line(const uint8_t *in, const Rec &r, uint6
     const uint32_t t = threadIdx.x;
     const bool rev = r.flag & FLAG_REVERSE;
     const uint64_t l = (uint64_t)r.l_seq;
-    uint32_t head = (uint32_t)(-(uintptr_t)dst & 15);
-    if (head > len) head = len;
-    const uint32_t groups = (len - head) / 16, tail = len - head - 16 * groups;
+    const auto [head, groups, tail] = recpipe::split16(dst, len);
     if (t < head) dst[t] = QUAL ? qual_char_at(in, r, b0 + t) : seq_char_at(in, r, b0 + t);
     if (t < tail) {
         const uint32_t j = head + 16 * groups + t;
@@ -177,9 +105,11 @@ __device__ __forceinline__ void emit_line(const uint8_t *in, const Rec &r, uint6
     *(uint4 *)(dst + head + 16 * (uint64_t)t) = o;
 }
 
-__global__ void __launch_bounds__(BAM_NT) k_bam_emit(const uint8_t *in, const uint64_t *off, uint64_t n_rec, const uint64_t *out_off,
-                                                     const uint64_t *item_off, const uint32_t *item_rec, uint64_t item_cap,
-                                                     const unsigned long long *state, uint8_t *out, uint64_t out_cap) {
+__global__ void __launch_bounds__(BAM_NT) k_bam_emit(Decode codec, uint64_t n_rec, const uint64_t *out_off, const uint64_t *item_off,
+                                                     const uint32_t *item_rec, uint64_t item_cap, unsigned long long *state, uint8_t *out,
+                                                     uint64_t out_cap) {
+    const uint8_t *in = codec.in;
+    const uint64_t *off = codec.off;
     __shared__ uint16_t lut[2][256];
     const uint32_t t = threadIdx.x;
     lut[0][t] = pair_chars(t, false);
@@ -189,7 +119,7 @@ __global__ void __launch_bounds__(BAM_NT) k_bam_emit(const uint8_t *in, const ui
     if (state[0] > out_cap) return;  // FLX_ERR_CAPACITY: nothing is written
     for (uint64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
         const uint64_t k = item_rec[w];
-        if (k >= n_rec || item_off[k] > w) continue;  // (cannot happen: k_bam_offsets wrote the item)
+        if (k >= n_rec || item_off[k] > w) continue;  // (cannot happen: k_offsets wrote the item)
         Rec r;
         if (read_record(in, off[k + 1], off[k], r) != REC_OK || !has_text(r)) continue;  // (cannot happen: the item exists)
         const uint64_t c = w - item_off[k];
@@ -214,57 +144,6 @@ __global__ void __launch_bounds__(BAM_NT) k_bam_emit(const uint8_t *in, const ui
     }
 }
 
-uint64_t item_bound(uint64_t n_rec, uint64_t bytes) { return n_rec + bytes / BAM_CHUNK; }
-
-struct BamWork {  // the device arrays of one call, carved out of one block
-    Sum3 *tile_sums;
-    unsigned long long *state;
-    uint64_t *item_off, *out_off;
-    uint32_t *item_rec;
-    uint64_t item_cap;
-};
-uint64_t n_tiles_of(uint64_t n_rec) { return (n_rec + BAM_NT - 1) / BAM_NT; }
-size_t work_bytes(uint64_t n_rec, uint64_t bytes) {
-    return (size_t)(n_tiles_of(n_rec) * sizeof(Sum3) + kStateWords * 8 + 2 * (n_rec + 1) * 8 + item_bound(n_rec, bytes) * 4 + 64);
-}
-BamWork carve(void *p, uint64_t n_rec, uint64_t bytes) {
-    BamWork w;
-    uint8_t *b = (uint8_t *)p;
-    w.tile_sums = (Sum3 *)b;
-    b += n_tiles_of(n_rec) * sizeof(Sum3);
-    w.state = (unsigned long long *)b;
-    b += kStateWords * 8;
-    w.item_off = (uint64_t *)b;
-    b += (n_rec + 1) * 8;
-    w.out_off = (uint64_t *)b;
-    b += (n_rec + 1) * 8;
-    w.item_rec = (uint32_t *)b;
-    w.item_cap = item_bound(n_rec, bytes);
-    return w;
-}
-
-// The launches of one call on `st` (n_rec >= 1): h_state (pinned, or read after a synchronisation) gets the four state words.
-// d_out_off may be the work block's own array.  emit == false: sizes only.
-hipError_t bam_launch(hipStream_t st, unsigned emit_blocks, const uint8_t *d_in, uint64_t n, const uint64_t *d_off, uint64_t n_rec,
-                      const BamWork &w, uint64_t *d_out_off, uint8_t *d_out, uint64_t out_cap, bool emit, uint64_t *h_state) {
-    hipError_t e = hipMemsetAsync(w.state, 0, kStateWords * 8, st);
-    if (e != hipSuccess) return e;
-    const uint64_t tiles = n_tiles_of(n_rec);
-    hipLaunchKernelGGL(k_bam_sizes, dim3((unsigned)tiles), dim3(BAM_NT), 0, st, d_in, n, d_off, n_rec, w.tile_sums, w.state);
-    hipLaunchKernelGGL(k_bam_scan_tiles, dim3(1), dim3(BAM_NT), 0, st, w.tile_sums, tiles, w.state);
-    hipLaunchKernelGGL(k_bam_offsets, dim3((unsigned)tiles), dim3(BAM_NT), 0, st, d_in, n, d_off, n_rec, w.tile_sums, w.state, d_out_off,
-                       w.item_off, w.item_rec, w.item_cap);
-    if (emit) {
-        const uint64_t blocks = w.item_cap < emit_blocks ? w.item_cap : emit_blocks;
-        hipLaunchKernelGGL(k_bam_emit, dim3((unsigned)(blocks ? blocks : 1)), dim3(BAM_NT), 0, st, d_in, d_off, n_rec, d_out_off, w.item_off,
-                           w.item_rec, w.item_cap, w.state, d_out, out_cap);
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    return hipMemcpyAsync(h_state, w.state, kStateWords * 8, hipMemcpyDeviceToHost, st);
-}
-
-unsigned emit_blocks_of(const flx_ctx *ctx) { return (unsigned)(ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256) * kEmitBlocksPerCU; }
-
 }  // namespace
 
 extern "C" int flx_bam_index(const void *bam, uint64_t n, uint64_t max_records, uint64_t *rec_off, uint64_t *n_records, int *end_state) {
@@ -284,24 +163,15 @@ extern "C" int flx_bam_to_fastq_dev(flx_ctx *ctx, const void *d_bam, uint64_t n,
     if (!d_bam || !d_rec_off || !d_out_off || (!d_out && out_cap) || n_records > 0xffffffffull)
         return flx_fail(ctx, FLX_ERR_INVALID, "flx_bam_to_fastq_dev: bad argument");
     void *work = nullptr;
-    FLX_CHECK(flx_scratch(ctx, work_bytes(n_records, n), &work));
-    const BamWork w = carve(work, n_records, n);
+    FLX_CHECK(flx_scratch(ctx, recpipe::work_bytes<Decode>(n_records, n), &work));
     uint64_t st[kStateWords] = {0, 0, 0, 0};
     flx_time_scope ts(ctx, "flx_bam");
-    hipError_t e = bam_launch(ctx->stream, emit_blocks_of(ctx), (const uint8_t *)d_bam, n, d_rec_off, n_records, w, d_out_off, (uint8_t *)d_out,
-                              out_cap, true, st);
+    const hipError_t e = recpipe::launch(ctx->stream, recpipe::emit_blocks_of(ctx), Decode{(const uint8_t *)d_bam, n, d_rec_off}, n_records,
+                                         recpipe::carve<Decode>(work, n_records, n), d_out_off, k_bam_emit, d_out, out_cap, st);
     ts.end();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return flx_fail(ctx, FLX_ERR_HIP, "flx_bam_to_fastq_dev: %s", hipGetErrorString(e));
-    *first_bad = n_records - (st[3] <= n_records ? st[3] : n_records);
-    *n_skipped = st[2];
-    if (st[0] > out_cap) {
-        *out_len = st[0];
-        return flx_fail(ctx, FLX_ERR_CAPACITY, "flx_bam_to_fastq_dev: %llu bytes needed, capacity %llu", (unsigned long long)st[0],
-                        (unsigned long long)out_cap);
-    }
-    *out_len = st[0];
-    return FLX_OK;
+    const int rc = recpipe::finish_dev(ctx, "flx_bam_to_fastq_dev", e, st, n_records, out_cap, out_len, first_bad);
+    if (rc == FLX_OK || rc == FLX_ERR_CAPACITY) *n_skipped = st[2];
+    return rc;
 }
 
 // ---- host to host: pieces of whole records through two pinned slots ------------------------------------------------------------
@@ -309,53 +179,26 @@ namespace {
 
 struct BamSlot {
     hipStream_t stream = nullptr;
-    uint8_t *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
-    uint64_t *h_tab = nullptr, *d_tab = nullptr;  // the piece's record offsets (relative to its first byte)
-    uint64_t *h_state = nullptr;
-    void *work = nullptr;
+    flx_pinned_buf h_in, h_out, h_tab, h_state;  // h_tab / d_tab: the piece's record offsets (relative to its first byte)
+    flx_dev_buf d_in, d_out, d_tab, work;
     uint64_t in_cap = 0, rec_cap = 0;
     // the piece in flight
     bool pending = false;
     uint64_t k0 = 0, k1 = 0, out_at = 0, want = 0, skipped = 0;
 
-    void release() {
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_out) (void)hipHostFree(h_out);
-        if (d_in) (void)hipFree(d_in);
-        if (d_out) (void)hipFree(d_out);
-        if (h_tab) (void)hipHostFree(h_tab);
-        if (d_tab) (void)hipFree(d_tab);
-        if (work) (void)hipFree(work);
-        h_in = h_out = d_in = d_out = nullptr;
-        h_tab = d_tab = nullptr;
-        work = nullptr;
-        in_cap = rec_cap = 0;
-    }
     // room for a piece of in_bytes and n_rec records (the slot is idle); the text of a piece is at most twice its bytes
     hipError_t reserve(uint64_t in_bytes, uint64_t n_rec) {
-        if (in_bytes <= in_cap && n_rec <= rec_cap) return hipSuccess;
         const uint64_t ib = in_bytes > in_cap ? in_bytes : in_cap, nr = n_rec > rec_cap ? n_rec : rec_cap;
-        release();
-        hipError_t e = hipHostMalloc((void **)&h_in, ib, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&h_out, 2 * ib, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_in, ib);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_out, 2 * ib);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&h_tab, (nr + 1) * 8, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_tab, (nr + 1) * 8);
-        if (e == hipSuccess) e = hipMalloc(&work, work_bytes(nr, ib));
-        if (e == hipSuccess) {
-            in_cap = ib;
-            rec_cap = nr;
-        }
+        const hipError_t e = flx_reserve_all(h_in, ib, h_out, 2 * ib, d_in, ib, d_out, 2 * ib, h_tab, (nr + 1) * 8, d_tab, (nr + 1) * 8,
+                                             work, recpipe::work_bytes<Decode>(nr, ib));
+        if (e == hipSuccess) in_cap = ib, rec_cap = nr;
         return e;
     }
-    ~BamSlot() {
+    ~BamSlot() {  // (the buffers are freed behind this: nothing of the stream still uses them)
         if (stream) {
             (void)hipStreamSynchronize(stream);
             (void)hipStreamDestroy(stream);
         }
-        release();
-        if (h_state) (void)hipHostFree(h_state);
     }
 };
 
@@ -390,24 +233,24 @@ extern "C" int flx_bam_to_fastq(flx_ctx *ctx, const void *bam, uint64_t n, const
         return flx_fail(ctx, FLX_ERR_CAPACITY, "flx_bam_to_fastq: %llu bytes needed, capacity %llu", (unsigned long long)need, (unsigned long long)out_cap);
     }
     if (piece_bytes == 0) piece_bytes = 32ull << 20;
-    constexpr uint64_t kPieceRecords = 1u << 20;
     FLX_HIP(ctx, hipSetDevice(ctx->device));
     BamSlot slots[2];
     for (BamSlot &s : slots) {
         FLX_HIP(ctx, hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-        FLX_HIP(ctx, hipHostMalloc((void **)&s.h_state, kStateWords * 8, hipHostMallocDefault));
+        FLX_HIP(ctx, s.h_state.reserve(kStateWords * 8));
     }
-    const unsigned emit_blocks = emit_blocks_of(ctx);
+    const unsigned emit_blocks = recpipe::emit_blocks_of(ctx);
     uint8_t *dst = (uint8_t *)out;
     // the piece of a slot comes back: its text to its place, and the device's word against the host's
     auto finish = [&](BamSlot &s) -> int {
         if (!s.pending) return FLX_OK;
         s.pending = false;
         FLX_HIP(ctx, hipStreamSynchronize(s.stream));
-        if (s.h_state[0] != s.want || s.h_state[2] != s.skipped || s.h_state[3] != 0)
+        const uint64_t *st = s.h_state.as<uint64_t>();
+        if (st[0] != s.want || st[2] != s.skipped || st[3] != 0)
             return flx_fail(ctx, FLX_ERR_STATE, "flx_bam_to_fastq: the device disagrees with the host about records %llu..%llu",
                             (unsigned long long)s.k0, (unsigned long long)s.k1);
-        if (s.want) memcpy(dst + s.out_at, s.h_out, (size_t)s.want);
+        if (s.want) memcpy(dst + s.out_at, s.h_out.p, (size_t)s.want);
         return FLX_OK;
     };
     uint64_t k = 0, out_at = 0;
@@ -415,22 +258,22 @@ extern "C" int flx_bam_to_fastq(flx_ctx *ctx, const void *bam, uint64_t n, const
     for (; k < good; ++p) {
         BamSlot &s = slots[p & 1];
         FLX_CHECK(finish(s));
-        uint64_t c = 1;  // at least one record: the staging grows to the largest
-        while (k + c < good && c < kPieceRecords && rec_off[k + c + 1] - rec_off[k] <= piece_bytes) ++c;
-        const uint64_t nin = rec_off[k + c] - rec_off[k];
-        hipError_t e = s.reserve(nin > piece_bytes ? nin : piece_bytes, c > 4096 ? c : 4096);
+        const uint64_t c = flx_piece_records(rec_off, k, good, piece_bytes), nin = rec_off[k + c] - rec_off[k];
+        hipError_t e = s.reserve(nin > piece_bytes ? nin : piece_bytes, c > kPieceMinTable ? c : kPieceMinTable);
         if (e != hipSuccess) return flx_fail(ctx, FLX_ERR_NOMEM, "flx_bam_to_fastq: %s", hipGetErrorString(e));
-        for (uint64_t j = 0; j <= c; ++j) s.h_tab[j] = rec_off[k + j] - rec_off[k];
-        memcpy(s.h_in, src + rec_off[k], (size_t)nin);
+        flx_piece_table(rec_off, k, c, s.h_tab.as<uint64_t>());
+        memcpy(s.h_in.p, src + rec_off[k], (size_t)nin);
         s.k0 = k;
         s.k1 = k + c;
         s.out_at = out_at;
         s.want = text_bytes_host(src, rec_off, k, k + c, &s.skipped);
-        const BamWork w = carve(s.work, s.rec_cap, s.in_cap);
-        e = hipMemcpyAsync(s.d_in, s.h_in, nin, hipMemcpyHostToDevice, s.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(s.d_tab, s.h_tab, (c + 1) * 8, hipMemcpyHostToDevice, s.stream);
-        if (e == hipSuccess) e = bam_launch(s.stream, emit_blocks, s.d_in, nin, s.d_tab, c, w, w.out_off, s.d_out, 2 * s.in_cap, true, s.h_state);
-        if (e == hipSuccess && s.want) e = hipMemcpyAsync(s.h_out, s.d_out, s.want, hipMemcpyDeviceToHost, s.stream);
+        const auto w = recpipe::carve<Decode>(s.work.p, s.rec_cap, s.in_cap);
+        e = hipMemcpyAsync(s.d_in.p, s.h_in.p, nin, hipMemcpyHostToDevice, s.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s.d_tab.p, s.h_tab.p, (c + 1) * 8, hipMemcpyHostToDevice, s.stream);
+        if (e == hipSuccess)
+            e = recpipe::launch(s.stream, emit_blocks, Decode{s.d_in.as(), nin, s.d_tab.as<uint64_t>()}, c, w, (uint64_t *)w.extra, k_bam_emit,
+                                s.d_out.p, 2 * s.in_cap, s.h_state.as<uint64_t>());
+        if (e == hipSuccess && s.want) e = hipMemcpyAsync(s.h_out.p, s.d_out.p, s.want, hipMemcpyDeviceToHost, s.stream);
         s.pending = true;  // (whatever was enqueued is waited for: finish, or the slot's destructor)
         if (e != hipSuccess) return flx_fail(ctx, FLX_ERR_HIP, "flx_bam_to_fastq: %s", hipGetErrorString(e));
         out_at += s.want;

@@ -12,6 +12,7 @@
 
 #include "flx_internal.h"
 #include "bgzf_member.h"
+#include "host_pieces.h"
 
 using namespace bgzf;
 
@@ -193,16 +194,14 @@ extern "C" int flx_bgzf_compress_dev(flx_ctx *ctx, const void *d_in, uint64_t n,
 // ---- host-to-host compressor with its own streams and pinned slots ---------------------------------------------------
 struct flx_bgzf_slot {
     hipStream_t stream = nullptr;
-    uint8_t *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
-    void *work = nullptr;
-    uint64_t *h_state = nullptr;
-    uint64_t *d_tab = nullptr, *h_tab = nullptr;  // inflate: the piece's offsets, its first bad member, its status words
+    flx_dev_buf d_in, d_out, work;
+    flx_pinned_buf h_in, h_out, h_state;
+    flx_dev_buf d_tab;  // d_tab / h_tab: inflate's piece offsets, its first bad member, its status words
+    flx_pinned_buf h_tab;
     // text -> BAM (flx_bgzf_bam_from_fastq): allocated by the first such call on the slot, each grown alone.  The text of a piece
     // goes through h_in / d_in like the compressor's input; e_h_text / e_d_text exist only behind a record larger than the slot.
-    uint8_t *e_h_text = nullptr, *e_d_text = nullptr, *e_d_bam = nullptr;
-    uint64_t *e_h_off = nullptr, *e_d_off = nullptr, *e_d_out_off = nullptr, *e_h_state = nullptr;
-    void *e_work = nullptr;
-    uint64_t e_text_cap = 0, e_rec_cap = 0, e_bam_cap = 0, e_work_cap = 0;
+    flx_pinned_buf e_h_text, e_h_off, e_h_state;
+    flx_dev_buf e_d_text, e_d_bam, e_d_off, e_d_out_off, e_work;
     bool busy = false;
 };
 
@@ -221,42 +220,15 @@ struct flx_bgzf {
     std::condition_variable cv;
 };
 
-static void free_encoder(flx_bgzf_slot &s) {
-    if (s.e_h_text) (void)hipHostFree(s.e_h_text);
-    if (s.e_d_text) (void)hipFree(s.e_d_text);
-    if (s.e_d_bam) (void)hipFree(s.e_d_bam);
-    if (s.e_h_off) (void)hipHostFree(s.e_h_off);
-    if (s.e_d_off) (void)hipFree(s.e_d_off);
-    if (s.e_d_out_off) (void)hipFree(s.e_d_out_off);
-    if (s.e_h_state) (void)hipHostFree(s.e_h_state);
-    if (s.e_work) (void)hipFree(s.e_work);
-    s.e_h_text = s.e_d_text = s.e_d_bam = nullptr;
-    s.e_h_off = s.e_d_off = s.e_d_out_off = s.e_h_state = nullptr;
-    s.e_work = nullptr;
-    s.e_text_cap = s.e_rec_cap = s.e_bam_cap = s.e_work_cap = 0;
-}
-
-static void free_slot(flx_bgzf_slot &s) {
-    free_encoder(s);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-    if (s.d_in) (void)hipFree(s.d_in);
-    if (s.d_out) (void)hipFree(s.d_out);
-    if (s.work) (void)hipFree(s.work);
-    if (s.h_in) (void)hipHostFree(s.h_in);
-    if (s.h_out) (void)hipHostFree(s.h_out);
-    if (s.h_state) (void)hipHostFree(s.h_state);
-    if (s.d_tab) (void)hipFree(s.d_tab);
-    if (s.h_tab) (void)hipHostFree(s.h_tab);
-    s = flx_bgzf_slot();
-}
-
+// (every stream is waited for and destroyed before the slots, and with them their buffers, go)
 extern "C" void flx_bgzf_destroy(flx_bgzf *z) {
     if (!z) return;
     (void)hipSetDevice(z->device);
-    for (auto &s : z->slots) {
-        if (s.stream) (void)hipStreamSynchronize(s.stream);
-        free_slot(s);
-    }
+    for (auto &s : z->slots)
+        if (s.stream) {
+            (void)hipStreamSynchronize(s.stream);
+            (void)hipStreamDestroy(s.stream);
+        }
     delete z;
 }
 
@@ -275,14 +247,9 @@ extern "C" int flx_bgzf_create(flx_ctx *ctx, uint64_t slot_bytes, unsigned slots
     const uint64_t ob = bound_of(sb, FLX_BGZF_EOF);
     for (auto &s : z->slots) {
         hipError_t e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMalloc(&s.d_in, sb + kSlotSlack);
-        if (e == hipSuccess) e = hipMalloc(&s.d_out, ob + kSlotSlack);
-        if (e == hipSuccess) e = hipMalloc(&s.work, work_bytes(sb));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_in, sb + kSlotSlack, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_out, ob + kSlotSlack, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_state, 16, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&s.d_tab, kTabBytes);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_tab, kTabBytes, hipHostMallocDefault);
+        if (e == hipSuccess)
+            e = flx_reserve_all(s.d_in, sb + kSlotSlack, s.d_out, ob + kSlotSlack, s.work, work_bytes(sb), s.h_in, sb + kSlotSlack, s.h_out,
+                                ob + kSlotSlack, s.h_state, 16, s.d_tab, kTabBytes, s.h_tab, kTabBytes);
         if (e != hipSuccess) {
             flx_bgzf_destroy(z);
             return flx_fail(ctx, FLX_ERR_NOMEM, "flx_bgzf_create: %s", hipGetErrorString(e));
@@ -336,27 +303,27 @@ extern "C" int flx_bgzf_inflate(flx_bgzf *z, const void *in, const uint64_t *in_
             break;
         }
         const uint64_t nin = in_off[k + c] - in_off[k], nout = out_off[k + c] - out_off[k];
-        uint64_t *h_in_off = s->h_tab, *h_out_off = s->h_tab + c + 1;
+        uint64_t *h_in_off = s->h_tab.as<uint64_t>(), *h_out_off = h_in_off + c + 1;
         for (uint64_t j = 0; j <= c; ++j) {
             h_in_off[j] = in_off[k + j] - in_off[k];
             h_out_off[j] = out_off[k + j] - out_off[k];
         }
-        uint64_t *d_first = s->d_tab + 2 * (kInflatePiece + 1);
+        uint64_t *d_tab = s->d_tab.as<uint64_t>(), *d_first = d_tab + 2 * (kInflatePiece + 1);
         uint32_t *d_status = (uint32_t *)(d_first + 1);
-        memcpy(s->h_in, (const uint8_t *)in + in_off[k], nin);
-        e = hipMemcpyAsync(s->d_in, s->h_in, nin, hipMemcpyHostToDevice, s->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->d_tab, s->h_tab, (2 * c + 2) * 8, hipMemcpyHostToDevice, s->stream);
+        memcpy(s->h_in.p, (const uint8_t *)in + in_off[k], nin);
+        e = hipMemcpyAsync(s->d_in.p, s->h_in.p, nin, hipMemcpyHostToDevice, s->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_tab, h_in_off, (2 * c + 2) * 8, hipMemcpyHostToDevice, s->stream);
         if (e == hipSuccess)
-            e = flx_bgzf_inflate_launch(s->stream, s->d_in, s->d_tab, s->d_tab + c + 1, c, s->d_out, d_status, d_first);
-        if (e == hipSuccess && nout) e = hipMemcpyAsync(s->h_out, s->d_out, nout, hipMemcpyDeviceToHost, s->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->h_state, d_first, 8, hipMemcpyDeviceToHost, s->stream);
+            e = flx_bgzf_inflate_launch(s->stream, s->d_in.p, d_tab, d_tab + c + 1, c, s->d_out.p, d_status, d_first);
+        if (e == hipSuccess && nout) e = hipMemcpyAsync(s->h_out.p, s->d_out.p, nout, hipMemcpyDeviceToHost, s->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->h_state.p, d_first, 8, hipMemcpyDeviceToHost, s->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
         if (e != hipSuccess) {  // what was enqueued in front of the failure may still read or write the slot's buffers
             (void)hipStreamSynchronize(s->stream);
             break;
         }
-        const uint64_t fb = s->h_state[0] < c ? s->h_state[0] : c;
-        memcpy((uint8_t *)out + out_off[k], s->h_out, (size_t)(h_out_off[fb]));
+        const uint64_t fb = *s->h_state.as<uint64_t>() < c ? *s->h_state.as<uint64_t>() : c;
+        memcpy((uint8_t *)out + out_off[k], s->h_out.p, (size_t)(h_out_off[fb]));
         if (fb < c) {
             bad = k + fb;
             break;
@@ -382,21 +349,21 @@ extern "C" int flx_bgzf_compress(flx_bgzf *z, const void *in, uint64_t n, int fl
         const uint64_t c = n - done < z->slot_bytes ? n - done : z->slot_bytes;
         const int f = (done + c == n) ? flags : 0;
         if (e == hipSuccess && c) {
-            memcpy(s->h_in, (const uint8_t *)in + done, c);
-            e = hipMemcpyAsync(s->d_in, s->h_in, c, hipMemcpyHostToDevice, s->stream);
+            memcpy(s->h_in.p, (const uint8_t *)in + done, c);
+            e = hipMemcpyAsync(s->d_in.p, s->h_in.p, c, hipMemcpyHostToDevice, s->stream);
         }
         const uint64_t cap = bound_of(c, f);
-        if (e == hipSuccess) e = bgzf_run(s->stream, s->d_in, c, f, s->d_out, cap, s->work, s->h_state);
+        if (e == hipSuccess) e = bgzf_run(s->stream, s->d_in.as(), c, f, s->d_out.as(), cap, s->work.p, s->h_state.as<uint64_t>());
         if (e != hipSuccess) break;
-        const uint64_t got = s->h_state[0];
+        const uint64_t got = *s->h_state.as<uint64_t>();
         if (got > out_cap - len) {
             rc = FLX_ERR_CAPACITY;
             break;
         }
-        if ((e = hipMemcpyAsync(s->h_out, s->d_out, got, hipMemcpyDeviceToHost, s->stream)) == hipSuccess)
+        if ((e = hipMemcpyAsync(s->h_out.p, s->d_out.p, got, hipMemcpyDeviceToHost, s->stream)) == hipSuccess)
             e = hipStreamSynchronize(s->stream);
         if (e != hipSuccess) break;
-        memcpy((uint8_t *)out + len, s->h_out, got);
+        memcpy((uint8_t *)out + len, s->h_out.p, got);
         len += got;
         done += c;
     } while (done < n);
@@ -410,44 +377,11 @@ extern "C" int flx_bgzf_compress(flx_bgzf *z, const void *in, uint64_t n, int fl
 // Room on the (idle) slot for a piece of text_bytes of text in n_rec records.  Every buffer grows alone, and only when it is too
 // small: a free synchronises the device under the other workers' streams.  Text of at most slot_bytes needs no buffer of its own.
 static hipError_t reserve_encoder(flx_bgzf_slot &s, uint64_t slot_bytes, uint64_t text_bytes, uint64_t n_rec) {
-    hipError_t e = hipSuccess;
-    if (!s.e_h_state) e = hipHostMalloc((void **)&s.e_h_state, 32, hipHostMallocDefault);
-    if (e == hipSuccess && text_bytes > slot_bytes && text_bytes > s.e_text_cap) {
-        if (s.e_h_text) (void)hipHostFree(s.e_h_text);
-        if (s.e_d_text) (void)hipFree(s.e_d_text);
-        s.e_h_text = s.e_d_text = nullptr;
-        s.e_text_cap = 0;
-        e = hipHostMalloc((void **)&s.e_h_text, text_bytes + 16, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&s.e_d_text, text_bytes + 16);
-        if (e == hipSuccess) s.e_text_cap = text_bytes;
-    }
-    if (e == hipSuccess && n_rec > s.e_rec_cap) {
-        if (s.e_h_off) (void)hipHostFree(s.e_h_off);
-        if (s.e_d_off) (void)hipFree(s.e_d_off);
-        if (s.e_d_out_off) (void)hipFree(s.e_d_out_off);
-        s.e_h_off = s.e_d_off = s.e_d_out_off = nullptr;
-        s.e_rec_cap = 0;
-        e = hipHostMalloc((void **)&s.e_h_off, (n_rec + 1) * 8, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&s.e_d_off, (n_rec + 1) * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&s.e_d_out_off, (n_rec + 1) * 8);
-        if (e == hipSuccess) s.e_rec_cap = n_rec;
-    }
     uint64_t bb = 0;
     (void)flx_bam_from_fastq_bound(text_bytes, n_rec, &bb);
-    if (e == hipSuccess && bb > s.e_bam_cap) {
-        if (s.e_d_bam) (void)hipFree(s.e_d_bam);
-        s.e_d_bam = nullptr;
-        s.e_bam_cap = 0;
-        if ((e = hipMalloc((void **)&s.e_d_bam, bb + kSlotSlack)) == hipSuccess) s.e_bam_cap = bb;
-    }
-    const uint64_t wb = flx_bam_encode_work_bytes(n_rec, text_bytes);
-    if (e == hipSuccess && wb > s.e_work_cap) {
-        if (s.e_work) (void)hipFree(s.e_work);
-        s.e_work = nullptr;
-        s.e_work_cap = 0;
-        if ((e = hipMalloc(&s.e_work, wb)) == hipSuccess) s.e_work_cap = wb;
-    }
-    return e;
+    const uint64_t own_text = text_bytes > slot_bytes ? text_bytes + 16 : 0;
+    return flx_reserve_all(s.e_h_state, 32, s.e_h_text, own_text, s.e_d_text, own_text, s.e_h_off, (n_rec + 1) * 8, s.e_d_off, (n_rec + 1) * 8,
+                           s.e_d_out_off, (n_rec + 1) * 8, s.e_d_bam, bb + kSlotSlack, s.e_work, flx_bam_encode_work_bytes(n_rec, text_bytes));
 }
 
 // Thread-safe like flx_bgzf_compress.  A piece is whole records of at most slot_bytes of text (one record when that record is
@@ -466,40 +400,38 @@ extern "C" int flx_bgzf_bam_from_fastq(flx_bgzf *z, const void *text, uint64_t n
             *first_bad = k;
             return FLX_OK;
         }
-    constexpr uint64_t kPieceRecords = 1u << 20;
     flx_bgzf_slot *s = take_slot(z);
     int rc = FLX_OK;
     hipError_t e = hipSetDevice(z->device);
     const unsigned emit_blocks = flx_bam_encode_blocks(z->ctx);
     uint64_t k = 0, len = 0, bad = n_records;
     while (e == hipSuccess && rc == FLX_OK && k < n_records) {
-        uint64_t c = 1;  // at least one record: the buffers grow to the largest
-        while (k + c < n_records && c < kPieceRecords && rec_off[k + c + 1] - rec_off[k] <= z->slot_bytes) ++c;
-        const uint64_t nin = rec_off[k + c] - rec_off[k];
+        const uint64_t c = flx_piece_records(rec_off, k, n_records, z->slot_bytes), nin = rec_off[k + c] - rec_off[k];
         // (sized for whole slots, so that the pieces of a run find room the first piece made)
-        if ((e = reserve_encoder(*s, z->slot_bytes, nin > z->slot_bytes ? nin : z->slot_bytes, c > 4096 ? c : 4096)) != hipSuccess) {
+        if ((e = reserve_encoder(*s, z->slot_bytes, nin > z->slot_bytes ? nin : z->slot_bytes, c > kPieceMinTable ? c : kPieceMinTable)) != hipSuccess) {
             rc = FLX_ERR_NOMEM;
             break;
         }
-        uint8_t *h_text = nin <= z->slot_bytes ? s->h_in : s->e_h_text, *d_text = nin <= z->slot_bytes ? s->d_in : s->e_d_text;
-        for (uint64_t j = 0; j <= c; ++j) s->e_h_off[j] = rec_off[k + j] - rec_off[k];
+        uint8_t *h_text = (nin <= z->slot_bytes ? s->h_in : s->e_h_text).as(), *d_text = (nin <= z->slot_bytes ? s->d_in : s->e_d_text).as();
+        const uint64_t bam_cap = s->e_d_bam.cap - kSlotSlack, *e_state = s->e_h_state.as<uint64_t>();
+        flx_piece_table(rec_off, k, c, s->e_h_off.as<uint64_t>());
         memcpy(h_text, (const uint8_t *)text + rec_off[k], (size_t)nin);
         if (nin) e = hipMemcpyAsync(d_text, h_text, nin, hipMemcpyHostToDevice, s->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->e_d_off, s->e_h_off, (c + 1) * 8, hipMemcpyHostToDevice, s->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->e_d_off.p, s->e_h_off.p, (c + 1) * 8, hipMemcpyHostToDevice, s->stream);
         if (e == hipSuccess)
-            e = flx_bam_encode_launch(s->stream, emit_blocks, d_text, nin, s->e_d_off, c, s->e_work, s->e_d_out_off, s->e_d_bam, s->e_bam_cap,
-                                      s->e_h_state);
+            e = flx_bam_encode_launch(s->stream, emit_blocks, d_text, nin, s->e_d_off.as<uint64_t>(), c, s->e_work.p, s->e_d_out_off.as<uint64_t>(),
+                                      s->e_d_bam.p, bam_cap, s->e_h_state.as<uint64_t>());
         if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
         if (e != hipSuccess) {
             (void)hipStreamSynchronize(s->stream);
             break;
         }
-        const uint64_t enc = s->e_h_state[0], nbad = s->e_h_state[3];
+        const uint64_t enc = e_state[0], nbad = e_state[3];
         if (nbad) {
             bad = k + (c - (nbad <= c ? nbad : c));
             break;
         }
-        if (enc > s->e_bam_cap) {  // (cannot happen: the buffer has the bound of the piece)
+        if (enc > bam_cap) {  // (cannot happen: the buffer has the bound of the piece)
             rc = FLX_ERR_STATE;
             break;
         }
@@ -507,15 +439,15 @@ extern "C" int flx_bgzf_bam_from_fastq(flx_bgzf *z, const void *text, uint64_t n
         for (uint64_t done = 0; done < enc && rc == FLX_OK;) {
             const uint64_t cb = enc - done < z->slot_bytes ? enc - done : z->slot_bytes;
             const int f = (last_piece && done + cb == enc) ? flags : 0;
-            if ((e = bgzf_run(s->stream, s->e_d_bam + done, cb, f, s->d_out, bound_of(cb, f), s->work, s->h_state)) != hipSuccess) break;
-            const uint64_t got = s->h_state[0];
+            if ((e = bgzf_run(s->stream, s->e_d_bam.as() + done, cb, f, s->d_out.as(), bound_of(cb, f), s->work.p, s->h_state.as<uint64_t>())) != hipSuccess) break;
+            const uint64_t got = *s->h_state.as<uint64_t>();
             if (got > out_cap - len) {
                 rc = FLX_ERR_CAPACITY;
                 break;
             }
-            if ((e = hipMemcpyAsync(s->h_out, s->d_out, got, hipMemcpyDeviceToHost, s->stream)) == hipSuccess) e = hipStreamSynchronize(s->stream);
+            if ((e = hipMemcpyAsync(s->h_out.p, s->d_out.p, got, hipMemcpyDeviceToHost, s->stream)) == hipSuccess) e = hipStreamSynchronize(s->stream);
             if (e != hipSuccess) break;
-            memcpy((uint8_t *)out + len, s->h_out, (size_t)got);
+            memcpy((uint8_t *)out + len, s->h_out.p, (size_t)got);
             len += got;
             done += cb;
         }

@@ -60,8 +60,10 @@ def to_fastq_dev(ctx, blob, rec_off, in_shift=0, out_shift=0, out_cap=None):
 
 
 def test_chunk_size_is_the_one_the_corpus_is_built_around():
-    src = open(os.path.join(ROOT, "filtlong_amd", "csrc", "bam.hip")).read()
-    assert re.search(r"BAM_NT = 256;", src) and re.search(r"BAM_CHUNK = 16 \* BAM_NT;", src) and cases.EMIT_CHUNK == 16 * 256
+    csrc = os.path.join(ROOT, "filtlong_amd", "csrc")
+    shared, src = open(os.path.join(csrc, "record_pipeline.h")).read(), open(os.path.join(csrc, "bam.hip")).read()
+    assert re.search(r"\bNT = 256;", shared) and re.search(r"\bCHUNK = 16 \* NT;", shared) and cases.EMIT_CHUNK == 16 * 256
+    assert re.search(r"BAM_NT = recpipe::NT;", src) and re.search(r"BAM_CHUNK = recpipe::CHUNK;", src)
 
 
 def test_corpus_dev(ctx, corpus, host_results):

@@ -76,8 +76,10 @@ def from_fastq_dev(ctx, text, rec_off, in_shift=0, out_shift=0, out_cap=None):
 
 
 def test_chunk_size_is_the_one_the_corpus_is_built_around():
-    src = open(os.path.join(ROOT, "filtlong_amd", "csrc", "bam_encode.hip")).read()
-    assert re.search(r"ENC_NT = 256;", src) and re.search(r"ENC_CHUNK = 16 \* ENC_NT;", src) and cases.ENC_CHUNK == 16 * 256
+    csrc = os.path.join(ROOT, "filtlong_amd", "csrc")
+    shared, src = open(os.path.join(csrc, "record_pipeline.h")).read(), open(os.path.join(csrc, "bam_encode.hip")).read()
+    assert re.search(r"\bNT = 256;", shared) and re.search(r"\bCHUNK = 16 \* NT;", shared) and cases.ENC_CHUNK == 16 * 256
+    assert re.search(r"ENC_NT = recpipe::NT;", src) and re.search(r"ENC_CHUNK = recpipe::CHUNK;", src)
 
 
 def test_corpus_dev(ctx, corpus, expected, host_results):
