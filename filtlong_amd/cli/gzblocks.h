@@ -34,7 +34,7 @@ struct MappedFile {  // read-only mapping of a regular file (the compressed inpu
         madvise(m, n, MADV_SEQUENTIAL);
         return true;
     }
-    bool gz() const { return n >= 2 && p[0] == 0x1f && p[1] == 0x8b; }
+    bool gz() const { return gzframe::magic_at(p, n, 0); }
 };
 
 // FLX_CLI_GPU_INFLATE=1: the process's device inflater of BGZF members.  run.h sets `make`; the object is created when the first

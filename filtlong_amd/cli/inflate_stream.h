@@ -10,10 +10,13 @@
 #pragma once
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include "../csrc/gzip_framing.h"
 
 struct GzPoint {
     uint64_t in = 0;    // compressed offset of the first whole byte of the block
@@ -44,6 +47,17 @@ static inline uint64_t gzread_delivered_before_error(uint64_t member_base, uint6
     return (member_base + j * call) / call * call;                // the gzread call that needed it starts here
 }
 
+// Raw inflate resumed inside a deflate stream (zran.c): the next block starts `bits` bits before byte `in` of data, in the top bits
+// of byte in - 1, and `window` (n bytes) is the output in front of it.  false: *z is not live.
+static inline bool inflate_resume(z_stream *z, const unsigned char *data, uint64_t in, int bits, const char *window, size_t n) {
+    memset(z, 0, sizeof *z);
+    if (inflateInit2(z, -15) != Z_OK) return false;
+    if ((bits == 0 || (in > 0 && inflatePrime(z, bits, data[in - 1] >> (8 - bits)) == Z_OK)) &&
+        (n == 0 || inflateSetDictionary(z, (const Bytef *)window, (uInt)n) == Z_OK)) return true;
+    inflateEnd(z);
+    return false;
+}
+
 class InflateStream {
 public:
     InflateStream() = default;
@@ -65,18 +79,15 @@ public:
         check_ = pt.raw && pt.check;
         crc_ = pt.raw && pt.check ? pt.crc : crc32(0L, Z_NULL, 0);
         if (!gz_) { eof_ = in_pos_ >= size_; return true; }
-        memset(&z_, 0, sizeof z_);
         raw_ = pt.raw;
-        if (inflateInit2(&z_, raw_ ? -15 : 47) != Z_OK) { error_ = true; return false; }
-        live_ = true;
         if (raw_) {
-            if (pt.bits > 0) {
-                if (pt.in == 0 || inflatePrime(&z_, pt.bits, data_[pt.in - 1] >> (8 - pt.bits)) != Z_OK) { error_ = true; return false; }
-            }
-            if (!pt.window.empty() &&
-                inflateSetDictionary(&z_, (const Bytef *)pt.window.data(), (uInt)pt.window.size()) != Z_OK) { error_ = true; return false; }
+            live_ = inflate_resume(&z_, data_, pt.in, pt.bits, pt.window.data(), pt.window.size());
+        } else {
+            memset(&z_, 0, sizeof z_);
+            live_ = inflateInit2(&z_, 47) == Z_OK;
         }
-        return true;
+        error_ = !live_;
+        return live_;
     }
     void close() {
         if (live_) inflateEnd(&z_);
@@ -120,13 +131,14 @@ public:
             if (ret == Z_STREAM_END) {
                 if (raw_) {  // raw inflate leaves the member's crc32 + isize: checked here when the point asks for it
                     if (check_) {
-                        if (in_pos_ + 8 > size_) { truncated_ = true; eof_ = true; break; }  // (gzread: unexpected end of file)
-                        auto le32 = [&](uint64_t p) { return (uint32_t)data_[p] | (uint32_t)data_[p + 1] << 8 | (uint32_t)data_[p + 2] << 16 | (uint32_t)data_[p + 3] << 24; };
-                        if (le32(in_pos_) != (uint32_t)crc_ || le32(in_pos_ + 4) != (uint32_t)(total_out_ - member_start_)) { fail(false); break; }
+                        size_t next = 0;
+                        const gzframe::End e = gzframe::member_end(data_, size_, (size_t)in_pos_, (uint32_t)crc_, (uint32_t)(total_out_ - member_start_), &next);
+                        if (e == gzframe::End::TRUNCATED) { truncated_ = true; eof_ = true; break; }  // (gzread: unexpected end of file)
+                        if (e == gzframe::End::MISMATCH) { fail(false); break; }
                     }
                     in_pos_ = std::min<uint64_t>(size_, in_pos_ + 8);
                 }
-                if (in_pos_ + 2 <= size_ && data_[in_pos_] == 0x1f && data_[in_pos_ + 1] == 0x8b) {  // next member, like gzread
+                if (gzframe::magic_at(data_, size_, (size_t)in_pos_)) {  // next member, like gzread
                     if (inflateReset2(&z_, 47) != Z_OK) { fail(false); break; }
                     raw_ = false; check_ = false;
                     member_start_ = total_out_;

@@ -8,6 +8,7 @@
 // memory and nothing reaches the output buffer before the member's CRC-32 has been checked.
 #include "flx_internal.h"
 #include "bgzf_inflate_member.h"
+#include "gzip_framing.h"
 
 using namespace bgzf_inf;
 
@@ -95,34 +96,10 @@ extern "C" int flx_bgzf_index(const void *in, uint64_t n, uint64_t max_members, 
     uint64_t at = 0, out = 0, m = 0;
     in_off[0] = 0;
     out_off[0] = 0;
-    while (m < max_members) {
-        // RFC 1952 header with the BC subfield (SAM specification 4.1), as the command line's reader takes it
-        if (at + 18 + 8 > n || d[at] != 0x1f || d[at + 1] != 0x8b || d[at + 2] != 8) break;
-        const unsigned flg = d[at + 3];
-        if ((flg & 0xe0) || !(flg & 4)) break;
-        uint64_t p = at + 12;
-        const uint64_t xlen = (uint64_t)d[at + 10] | (uint64_t)d[at + 11] << 8;
-        if (p + xlen > n) break;
-        uint64_t bsize = 0;
-        for (uint64_t q = p; q + 4 <= p + xlen;) {
-            const uint64_t slen = (uint64_t)d[q + 2] | (uint64_t)d[q + 3] << 8;
-            if (d[q] == 'B' && d[q + 1] == 'C' && slen == 2 && q + 6 <= p + xlen) bsize = ((uint64_t)d[q + 4] | (uint64_t)d[q + 5] << 8) + 1;
-            q += 4 + slen;
-        }
-        p += xlen;
-        for (unsigned f = 8; f <= 16; f <<= 1)
-            if (flg & f) {
-                while (p < n && d[p]) ++p;
-                ++p;
-            }
-        if (flg & 2) p += 2;
-        if (p + 8 >= n) break;
-        if (bsize == 0 || at + bsize > n || bsize < p - at + 8) break;
-        const uint8_t *t = d + at + bsize - 4;
-        const uint32_t isize = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
-        if (isize > 65536) break;
-        at += bsize;
-        out += isize;
+    gzframe::Member mem;
+    while (m < max_members && gzframe::member_at(d, (size_t)n, (size_t)at, &mem) == gzframe::Kind::BGZF) {
+        at += mem.size;
+        out += mem.isize;
         ++m;
         in_off[m] = at;
         out_off[m] = out;
