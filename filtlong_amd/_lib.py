@@ -32,6 +32,8 @@ ABI_SYMBOLS = [
     "flx_bam_header", "flx_bam_from_fastq_bound", "flx_bam_from_fastq_dev", "flx_bgzf_bam_from_fastq",
     "flx_summary_q_edges", "flx_summary_dev", "flx_summary",
     "flx_qsplit_table", "flx_qsplit_threshold", "flx_score_batch_qsplit", "flx_score_batch_qsplit_dev", "flx_pipeline_set_qsplit",
+    "flx_screen_threshold", "flx_screen_span", "flx_screen_set_add", "flx_screen_hits", "flx_screen_hits_dev", "flx_last_screen_filter",
+    "flx_pipeline_set_screen", "flx_pipeline_screen",
 ]
 
 
@@ -212,5 +214,15 @@ def load():
     L.flx_score_batch_qsplit.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.POINTER(Params), dbl, C.POINTER(Scores)]
     L.flx_score_batch_qsplit_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.POINTER(Params), dbl, C.POINTER(Scores)]
     L.flx_pipeline_set_qsplit.argtypes = [vp, dbl]
+    L.flx_screen_threshold.argtypes = [dbl, C.POINTER(u64)]
+    L.flx_screen_span.argtypes = []
+    L.flx_screen_span.restype = C.c_uint32
+    L.flx_screen_set_add.argtypes = [vp, vp, vp, vp, u64]
+    L.flx_screen_hits.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp]
+    L.flx_screen_hits_dev.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp]
+    L.flx_pipeline_set_screen.argtypes = [vp, vp, dbl]
+    L.flx_pipeline_screen.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.flx_last_screen_filter.argtypes = [vp]
+    L.flx_last_screen_filter.restype = C.c_char_p
     _lib = L
     return L

@@ -168,11 +168,14 @@ class Context:
         return out
 
     # ---- seam 2, streaming ----------------------------------------------------------------------
-    def score_stream(self, chunks, params, kmers=None, chunk_bytes=1 << 20, chunk_reads=1 << 12, grow=False, split_window_q=None):
+    def score_stream(self, chunks, params, kmers=None, chunk_bytes=1 << 20, chunk_reads=1 << 12, grow=False, split_window_q=None,
+                     exclude=None, exclude_percent=10.0):
         """flx_pipeline_*: `chunks` is an iterable of lists of byte strings (Phred mode: qualities, k-mer mode: sequences).
         Every chunk is packed into the pipeline's pinned buffer and submitted; returns the same dict as score_reads for
         all reads in submission order.  grow: enlarge the slots (flx_pipeline_reserve) for a chunk that does not fit.
-        split_window_q: flx_pipeline_set_qsplit before the first chunk."""
+        split_window_q: flx_pipeline_set_qsplit before the first chunk.  exclude (a Kmers filled with add_screen_fasta):
+        flx_pipeline_set_screen with exclude_percent; in Phred mode every chunk is then a PAIR (qualities, sequences) of lists, and
+        the result also has "hits" and "excluded"."""
         L = self.L
         pipe = C.c_void_p()
         self._check(L.flx_pipeline_create(self.h, kmers.h if kmers is not None else None, C.byref(params), chunk_bytes,
@@ -180,7 +183,14 @@ class Context:
         try:
             if split_window_q is not None:
                 self._check(L.flx_pipeline_set_qsplit(pipe, float(split_window_q)))
+            two_planes = exclude is not None and (kmers is None or kmers.empty())
+            if exclude is not None:
+                self._check(L.flx_pipeline_set_screen(pipe, exclude.h, float(exclude_percent)))
             for strings in chunks:
+                seqs = None
+                if two_planes:
+                    strings, seqs = strings
+                    assert [len(x) for x in strings] == [len(x) for x in seqs]
                 n = len(strings)
                 lengths = np.array([len(x) for x in strings], dtype=np.int32)
                 offsets = np.zeros(max(n, 1), dtype=np.uint64)
@@ -196,6 +206,13 @@ class Context:
                     for x, o in zip(strings, offsets):
                         if len(x):
                             view[int(o):int(o) + len(x)] = np.frombuffer(bytes(x), dtype=np.uint8)
+                    if seqs is not None and pb.value:  # the second plane: the sequences, at the same offsets
+                        second = C.cast(C.c_void_p(buf.value + pb.value), C.POINTER(C.c_uint8))
+                        view2 = np.ctypeslib.as_array(second, shape=(int(pb.value),))
+                        view2[:] = 0
+                        for x, o in zip(seqs, offsets):
+                            if len(x):
+                                view2[int(o):int(o) + len(x)] = np.frombuffer(bytes(x), dtype=np.uint8)
                 self._check(L.flx_pipeline_submit(pipe, pb.value, offsets.ctypes.data, lengths.ctypes.data, n))
             s, n_all = Scores(), C.c_uint64()
             self._check(L.flx_pipeline_finish(pipe, C.byref(s), C.byref(n_all)))
@@ -214,6 +231,10 @@ class Context:
                    "child_mean_q": take(s.child_mean_q, np.float64, nc),
                    "child_window_q": take(s.child_window_q, np.float64, nc),
                    "child_passed": take(s.child_passed, np.uint8, nc)}
+            if exclude is not None:
+                hp, ep = C.c_void_p(), C.c_void_p()
+                self._check(L.flx_pipeline_screen(pipe, C.byref(hp), C.byref(ep)))
+                out["hits"], out["excluded"] = take(hp, np.uint32, n), take(ep, np.uint8, n)
             return out
         finally:
             L.flx_pipeline_destroy(pipe)
@@ -361,6 +382,30 @@ class Context:
                                                      float(keep_percent or 0.0), int(total_bases), d_final_score, C.byref(rep)))
         return rep
 
+    # ---- the contaminant screen ------------------------------------------------------------------
+    def screen_hits(self, plane, offsets, lengths, kmers, order=None):
+        """flx_screen_hits: for every read of the SEQUENCE plane the number of its 16-mers that are members of `kmers` (a set
+        filled with Kmers.add_screen_fasta).  uint32 array in input order."""
+        n = len(lengths)
+        plane = np.ascontiguousarray(plane, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        hits = np.full(max(n, 1), 0xA5A5A5A5, dtype=np.uint32)
+        ordp = None
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.uint32)
+            ordp = order.ctypes.data
+        self._check(self.L.flx_screen_hits(self.h, kmers.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data,
+                                           ordp, n, hits.ctypes.data))
+        return hits[:n]
+
+    def screen_hits_dev(self, kmers, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_hits):
+        self._check(self.L.flx_screen_hits_dev(self.h, kmers.h, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_hits))
+
+    def last_screen_filter(self):
+        """"lds", "pre12" or "exact": the filter in front of the exact bitmap in the last screen_hits call."""
+        return self.L.flx_last_screen_filter(self.h).decode()
+
     def last_phred_kernel(self):
         return self.L.flx_last_phred_kernel(self.h).decode()
 
@@ -480,6 +525,30 @@ def qsplit_threshold(q):
     if rc:
         raise FlxError(rc, "split_window_q must be greater than 0 and less than 100")
     return int(t.value)
+
+
+def screen_threshold(percent):
+    """t of --exclude_percent P (flx_screen_threshold; no device needed)."""
+    t = C.c_uint64()
+    rc = _lib.load().flx_screen_threshold(float(percent), C.byref(t))
+    if rc:
+        raise FlxError(rc, "exclude_percent must be greater than 0 and at most 100")
+    return int(t.value)
+
+
+def screen_span():
+    """Window positions per work item of the screen kernel (flx_screen_span; no device needed)."""
+    return int(_lib.load().flx_screen_span())
+
+
+def screen_excluded(hits, lengths, percent):
+    """The decision of --exclude on integers: windows > 0 and (hits << 32) >= t * windows."""
+    t = screen_threshold(percent)
+    out = np.zeros(len(hits), dtype=np.uint8)
+    for i, (h, n) in enumerate(zip(hits, lengths)):
+        w = max(0, int(n) - 15)
+        out[i] = 1 if w > 0 and (int(h) << 32) >= t * w else 0
+    return out
 
 
 def summary_dict(s):
@@ -708,6 +777,11 @@ class Kmers:
     def add_assembly_fasta(self, seqs):
         """Kmers::add_assembly_fasta (src/kmers.cpp:61-72) on already-parsed contig sequences."""
         self._add(self.ctx.L.flx_kmerset_add_assembly, seqs)
+
+    def add_screen_fasta(self, seqs):
+        """flx_screen_set_add: the sequences of a contaminant for the screen — cut at every byte outside ACGTacgt, pieces of at
+        least 16 bases only, so that an N run puts no poly-A into the set."""
+        self._add(self.ctx.L.flx_screen_set_add, seqs)
 
     def add_read_fastqs(self, files_of_seqs):
         """Kmers::add_read_fastqs (src/kmers.cpp:50-58): one list of read sequences per file, -1 then -2."""

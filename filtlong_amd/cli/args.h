@@ -38,6 +38,8 @@ struct Args {
     bool bam = false;   // not a reference flag: --bam writes stdout as BGZF-compressed unaligned BAM, packed and compressed on the GPU
     bool report_set = false; std::string report;  // not a reference flag: --report FILE receives a JSON summary of the reads before and after
     bool split_window_q_set = false; double split_window_q = 0;  // not a reference flag: --split_window_q Q splits reads at windows below Q (Phred mode)
+    bool exclude_set = false; std::string exclude;  // not a reference flag: --exclude FILE drops the reads that match this contaminant (FASTA)
+    bool exclude_percent_set = false; double exclude_percent = 10.0; std::string exclude_percent_text = "10";  // --exclude_percent P: ... with at least P % of their 16-mers in it
 };
 enum ParsingResult { GOOD, BAD, HELP, VERSION };
 
@@ -109,7 +111,8 @@ static long long read_ll(const std::string &name, const std::string &value, long
 // terminal on STDOUT (TIOCGWINSZ; indent 1 / 2 / 3 / 4 for widths up to 60 / 80 / 120 / beyond).  When stdout is no terminal the
 // reference reads the width out of an untouched `struct winsize` — 0 in practice: the description comes out one word per line and,
 // the other widths being unsigned differences that wrap around, nothing else is wrapped at all.  Both cases are restated here.
-// (--gpus, --gzip, --bam, --report and --split_window_q, this binary's flags of its own, are documented in README.md: the menu is the reference's.)
+// (--gpus, --gzip, --bam, --report, --split_window_q, --exclude and --exclude_percent, this binary's flags of its own, are documented in
+// README.md: the menu is the reference's.)
 static std::vector<std::string> help_wrap(const std::string &in, size_t width, size_t first = 0) {  // src/args.h:94-149
     std::vector<std::string> out;
     size_t cur = first ? first : width, linesize = 0;
@@ -275,6 +278,12 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
             else if (flag == "bam") a.bam = true;
             else if (flag == "report") { a.report = need("report"); a.report_set = true; }
             else if (flag == "split_window_q") { a.split_window_q = read_double("float", need("split_window_q")); a.split_window_q_set = true; }
+            else if (flag == "exclude") { a.exclude = need("exclude"); a.exclude_set = true; }
+            else if (flag == "exclude_percent") {
+                a.exclude_percent_text = need("exclude_percent");
+                a.exclude_percent = read_double("float", a.exclude_percent_text);
+                a.exclude_percent_set = true;
+            }
             else throw ParseError("Error: flag could not be matched: " + flag);
         }
     } catch (const ParseError &e) {
@@ -299,7 +308,7 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     for (auto &f : files)
         if (!file_exists(f)) { std::cerr << "Error: cannot find file: " << f << "\n"; return BAD; }
     if (!a.trim && !a.split_set && !a.target_bases_set && !a.keep_percent_set && !a.min_length_set && !a.max_length_set &&
-        !a.min_mean_q_set && !a.min_window_q_set && !a.split_window_q_set) {
+        !a.min_mean_q_set && !a.min_window_q_set && !a.split_window_q_set && !a.exclude_set) {
         std::cerr << "Error: no thresholds set, you must use one of the following options:\n";
         std::cerr << "target_bases, keep_percent, min_length, max_length, min_mean_q, min_window_q, trim, split\n";
         return BAD;
@@ -324,6 +333,11 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     if (a.split_window_q_set && !(a.split_window_q > 0.0 && a.split_window_q < 100.0)) {
         std::cerr << "Error: the value for --split_window_q must be greater than 0 and less than 100\n"; return BAD; }
     if (a.split_window_q_set && some_reference) { std::cerr << "Error: --split_window_q cannot be used with an external reference\n"; return BAD; }
+    // --exclude / --exclude_percent: behind every check above, --split_window_q's included
+    if (a.exclude_set && !file_exists(a.exclude)) { std::cerr << "Error: cannot find file: " << a.exclude << "\n"; return BAD; }
+    if (a.exclude_percent_set && !(a.exclude_percent > 0.0 && a.exclude_percent <= 100.0)) {
+        std::cerr << "Error: the value for --exclude_percent must be greater than 0 and at most 100\n"; return BAD; }
+    if (a.exclude_percent_set && !a.exclude_set) { std::cerr << "Error: --exclude_percent needs --exclude\n"; return BAD; }
     return GOOD;
 }
 
@@ -337,6 +351,7 @@ static bool open_report_file(const Args &a) {
         std::vector<std::string> inputs = a.short_reads;
         inputs.push_back(a.input_reads);
         if (a.assembly_set) inputs.push_back(a.assembly);
+        if (a.exclude_set) inputs.push_back(a.exclude);
         for (const auto &f : inputs) {
             struct stat is;
             if (stat(f.c_str(), &is) == 0 && is.st_dev == rs.st_dev && is.st_ino == rs.st_ino) {

@@ -60,14 +60,19 @@ static int gather_reads2(const Run &run, const Pass1 &p, const flx_scores &res, 
 }
 
 // totals over all ranks (one rank: the local values), and the line of src/main.cpp:155-166
-static int exchange_totals(const Run &run, Reads2 &r2) {
+static int exchange_totals(const Run &run, const Pass1 &p, Reads2 &r2) {
     const Args &args = run.args;
     const int rank = run.rank, world = run.world;
     long long after_total = 0;
     for (auto v : r2.len) after_total += v;
     r2.n_total = r2.reads.size();
+    uint64_t excluded_reads = 0, excluded_bases = 0;  // --exclude: the input reads the screen took
+    if (run.screen_excluded)
+        for (size_t i = 0; i < p.lengths.size(); ++i)
+            if (run.screen_excluded[i]) { ++excluded_reads; excluded_bases += (uint64_t)p.lengths[i]; }
     if (world > 1) {
-        std::vector<uint64_t> sums(2 * (size_t)world + 1, 0);
+        std::vector<uint64_t> sums(2 * (size_t)world + 1 + (run.exclude ? 2 : 0), 0);
+        if (run.exclude) { sums[2 * (size_t)world + 1] = excluded_reads; sums[2 * (size_t)world + 2] = excluded_bases; }
         sums[rank] = r2.reads.size();
         sums[world] = (uint64_t)after_total;
         sums[(size_t)world + 1 + rank] = r2.longest_name;  // (the --verbose table pads every name to the longest of ALL reads2, main.cpp:199-201)
@@ -75,11 +80,14 @@ static int exchange_totals(const Run &run, Reads2 &r2) {
         r2.n_total = 0;
         for (int r = 0; r < world; ++r) { r2.n_total += sums[r]; r2.longest_name = std::max<size_t>(r2.longest_name, sums[(size_t)world + 1 + r]); }
         after_total = (long long)sums[world];
+        if (run.exclude) { excluded_reads = sums[2 * (size_t)world + 1]; excluded_bases = sums[2 * (size_t)world + 2]; }
         if (args.verbose && rank == 0) {
             if (!print_verbose_parts(run, "vblocks")) return 1;
             std::cerr << "\n";
         }
     }
+    if (run.exclude && rank == 0)
+        std::cerr << "  excluded by reference: " << int_to_string((long long)excluded_reads) << " reads (" << int_to_string((long long)excluded_bases) << " bp)\n";
     if ((args.trim || args.split_set || args.split_window_q_set) && rank == 0) {  // src/main.cpp:155-166 (--split_window_q: "after splitting")
         if (args.trim && args.split_set) std::cerr << "  after trimming and splitting: ";
         else if (args.trim) std::cerr << "  after trimming: ";
@@ -122,6 +130,7 @@ static int leave(Run &run, Scorer &scorer, const Report &report) {
         scorer.destroy();
         run.stage("pipeline teardown");
         if (run.kmers) flx_kmerset_destroy(run.kmers);
+        if (run.exclude) flx_kmerset_destroy(run.exclude);
         g_gpu_inflater.destroy();
         flx_ctx_destroy(run.ctx);
         run.stage("context teardown");
@@ -201,6 +210,7 @@ int main(int argc, char **argv) {
 
     // ---- reference 16-mers (src/main.cpp:51-59, src/kmers.cpp:50-72) --------------------------------------
     if (const int rc = build_reference_set(run); rc != kGoOn) return rc;
+    if (const int rc = build_exclude_set(run); rc != kGoOn) return rc;  // --exclude: the contaminant's set, on every rank
     run.stage("reference 16-mers");
 
     // ---- pass 1: parse, checks (src/main.cpp:63-130) -----------------------------------------------------
@@ -229,7 +239,7 @@ int main(int argc, char **argv) {
     Reads2 r2;
     if (const int rc = gather_reads2(run, p, res, r2); rc != kGoOn) return rc;
     if (const int rc = print_verbose_blocks(run, p, res); rc != kGoOn) return rc;
-    if (const int rc = exchange_totals(run, r2); rc != kGoOn) return rc;
+    if (const int rc = exchange_totals(run, p, r2); rc != kGoOn) return rc;
 
     // ---- global stage (src/main.cpp:169-261) ---------------------------------------------------------------
     flx_cut_report rep;

@@ -111,7 +111,10 @@ struct Scorer {
         if (pipe) return true;
         if (flx_pipeline_create(run.ctx, run.kmers_empty ? nullptr : run.kmers, &run.prm, chunk_bytes, chunk_reads, &pipe) != FLX_OK) return false;
         // --split_window_q: the pipeline then splits the reads at their low-quality windows and returns children, as --split does
-        return !run.args.split_window_q_set || flx_pipeline_set_qsplit(pipe, run.args.split_window_q) == FLX_OK;
+        if (run.args.split_window_q_set && flx_pipeline_set_qsplit(pipe, run.args.split_window_q) != FLX_OK) return false;
+        // --exclude: the pipeline also screens every chunk against the contaminant's set; in Phred mode a chunk then carries the sequences
+        // as a second plane behind the qualities
+        return !run.exclude || flx_pipeline_set_screen(pipe, run.exclude, run.args.exclude_percent) == FLX_OK;
     }
 
     // Pack records [lo, lo + cnt) of a batch chunk by chunk; their lengths are appended to `lengths`.
@@ -146,6 +149,7 @@ struct Scorer {
         }
         const int32_t *len = lengths.data() + base;
         const bool phred = run.kmers_empty;
+        const bool second_plane = phred && run.exclude != nullptr;
         for (uint64_t at = 0; at < cnt;) {
             // the next chunk: as many records as fit the slot (flx_plane_layout's rule: 16-byte slots, 128-byte starts for long reads)
             uint64_t end = at, bytes = 0;
@@ -175,6 +179,12 @@ struct Scorer {
                     const uint64_t tail = offsets[i] + src.size();  // the staging buffer is reused: clear the padding behind the read
                     const uint64_t next = i + 1 < m ? offsets[i + 1] : plane_bytes;
                     if (next > tail) memset(plane + tail, 0, next - tail);
+                    if (second_plane) {  // the sequences, at the same offsets behind the qualities
+                        uint8_t *plane2 = plane + plane_bytes;
+                        const size_t nseq = std::min<size_t>(r.seq.size(), (size_t)len[at + i]);
+                        if (nseq) memcpy(plane2 + offsets[i], r.seq.p, nseq);
+                        if (next > offsets[i] + nseq) memset(plane2 + offsets[i] + nseq, 0, next - (offsets[i] + nseq));
+                    }
                 }
             });
             if (flx_pipeline_submit(pipe, plane_bytes, offsets.data(), len + at, m) != FLX_OK) return run.fail("scoring");
@@ -189,6 +199,7 @@ struct Scorer {
         if (!create_pipe()) return report ? run.fail("pipeline") : 1;
         uint64_t n_scored = 0;
         if (flx_pipeline_finish(pipe, &res, &n_scored) != FLX_OK || n_scored != n) return report ? run.fail("scoring") : 1;
+        if (run.exclude && flx_pipeline_screen(pipe, &run.screen_hits, &run.screen_excluded) != FLX_OK) return report ? run.fail("scoring") : 1;
         return kGoOn;
     }
 };

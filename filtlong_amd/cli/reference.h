@@ -18,7 +18,7 @@ static void print_hash_progress(const std::string &filename, long long base_coun
 
 // hashes one reference file into sets[0 .. n_sets); returns the number of sequences (those shorter than 16 bases count too,
 // src/kmers.cpp:96-100); ok = false: the library refused a batch (flx_last_error says why)
-static int hash_reference(const std::string &filename, flx_kmerset *const *sets, int n_sets, bool short_reads, bool &ok) {
+static int hash_reference(const std::string &filename, flx_kmerset *const *sets, int n_sets, bool short_reads, bool &ok, bool screen = false) {
     int n = 0;
     long long bases = 0, last_progress = 0;
     size_t batch_bytes = (size_t)256 << 20;
@@ -30,8 +30,9 @@ static int hash_reference(const std::string &filename, flx_kmerset *const *sets,
     auto flush = [&]() {
         if (offsets.empty() || !ok) return;
         for (int k = 0; k < n_sets && ok; ++k) {
-            const int rc = short_reads ? flx_kmerset_add_short_reads(sets[k], pack.data(), offsets.data(), lengths.data(), offsets.size())
-                                       : flx_kmerset_add_assembly(sets[k], pack.data(), offsets.data(), lengths.data(), offsets.size());
+            const int rc = screen        ? flx_screen_set_add(sets[k], pack.data(), offsets.data(), lengths.data(), offsets.size())
+                           : short_reads ? flx_kmerset_add_short_reads(sets[k], pack.data(), offsets.data(), lengths.data(), offsets.size())
+                                         : flx_kmerset_add_assembly(sets[k], pack.data(), offsets.data(), lengths.data(), offsets.size());
             ok = rc == FLX_OK;
         }
         pack.clear();
@@ -110,5 +111,30 @@ static int build_reference_set(Run &run) {
         std::cerr << "  " << int_to_string(count) << " reads, " << int_to_string((long long)flx_kmerset_size(run.kmers)) << " 16-mers\n\n";
     }
     run.kmers_empty = flx_kmerset_size(run.kmers) == 0;
+    return kGoOn;
+}
+
+// ---- --exclude FILE: the contaminant's 16-mers, a set of its own beside the reference's.  Every rank builds it itself, through the
+// reader of -a (gzip included, in batches); flx_screen_set_add cuts the sequences at every byte outside ACGTacgt.  16-mers cannot
+// screen a large genome: an unrelated read keeps N / 2^32 of its windows, and once that background reaches half the threshold —
+// N * 200 >= P * 2^32 — the run is refused.
+static int build_exclude_set(Run &run) {
+    const Args &args = run.args;
+    if (!args.exclude_set) return kGoOn;
+    if (!run.ready()) return 1;
+    if (flx_kmerset_create(run.ctx, &run.exclude) != FLX_OK) return run.fail("exclude set");
+    std::cerr << "Hashing 16-mers to exclude\n";
+    std::cerr << "  " << args.exclude << "\n";
+    bool ok = true;
+    const int count = hash_reference(args.exclude, &run.exclude, 1, false, ok, true);
+    if (!ok) return run.fail("exclude");
+    if (flx_kmerset_finalize(run.exclude) != FLX_OK) return run.fail("exclude set");
+    const uint64_t n = flx_kmerset_size(run.exclude);
+    std::cerr << "  " << int_to_string(count) << " " << (count == 1 ? "sequence" : "sequences") << ", " << int_to_string((long long)n) << " 16-mers\n\n";
+    if ((long double)n * 200.0L >= (long double)args.exclude_percent * 4294967296.0L) {
+        std::cerr << "Error: the reference for --exclude holds too many 16-mers (" << n << ") for --exclude_percent " << args.exclude_percent_text << "\n";
+        return 1;
+    }
+    if (n == 0) { std::cerr << "Error: the reference for --exclude holds no 16-mer of ACGT\n"; return 1; }
     return kGoOn;
 }

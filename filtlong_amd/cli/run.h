@@ -40,6 +40,9 @@ struct Run {
     std::thread ctx_thread;
     flx_kmerset *kmers = nullptr;
     bool kmers_empty = true;
+    flx_kmerset *exclude = nullptr;            // --exclude: the contaminant's 16-mers (reference.h: build_exclude_set)
+    const uint32_t *screen_hits = nullptr;     // ... and, once the scores are in, every read's hits and whether it was excluded
+    const uint8_t *screen_excluded = nullptr;  // (owned by the pipeline; this rank's reads in submission order)
     flx_params prm;
 
     explicit Run(const Args &a) : args(a) {
@@ -85,7 +88,7 @@ struct Run {
         const char *dev = getenv("FLX_DEVICE");
         int ordinal = dev ? atoi(dev) : 0;
         if (!dev && world > 1) ordinal = getenv("LOCAL_RANK") ? atoi(getenv("LOCAL_RANK")) : rank;
-        if (world == 1 && !args.assembly_set && args.short_reads.empty() && !timing) {
+        if (world == 1 && !args.assembly_set && args.short_reads.empty() && !args.exclude_set && !timing) {
             ctx_thread = std::thread([this, ordinal] { ctx_rc = flx_ctx_create(ordinal, &ctx); });
         } else if (flx_ctx_create(ordinal, &ctx) != FLX_OK) {
             std::cerr << "Error: " << flx_last_error(nullptr) << "\n";

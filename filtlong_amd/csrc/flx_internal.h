@@ -31,6 +31,7 @@ struct flx_ctx {
     uint64_t last_kmer_redo_n = 0;            // ... and how many there are
     const char *last_kmer_cover = "";    // which coverage kernel the last k-mer scoring call ran: "q" (cover_queue.hip), "w", "v2"
     bool last_kmer_locus = false;        // the last k-mer scoring call ran with the assembly text (kmerset.h: flx_locus)
+    const char *last_screen_filter = ""; // which filter stood in front of the bitmap in the last flx_screen_hits call: "lds", "pre12", "exact"
     void *phred_pending = nullptr;       // score_phred.hip: the record (flx_phred::PhredPending) every Phred scoring call leaves for flx_phred_finish
     const char *last_phred_kernel = "";  // which Phred kernel the last scoring call launched (flx_last_phred_kernel)
 

@@ -16,6 +16,17 @@ constexpr int kPrefilterBits = 24;
 __host__ __device__ inline uint32_t flx_sub12(uint32_t kmer16, int d) { return (kmer16 >> (2 * d)) & 0xFFFFFFu; }  // d = 0: last 12 bases
 const uint32_t *flx_kmerset_prefilter(const flx_kmerset *set);
 
+// The screen's filter in front of that one (screen.hip): the presence bitmap of all 10-MERS that occur inside a 16-mer of the set
+// (4^10 bits = 128 KiB: it fits the LDS of a CU beside nothing else).  A 16-mer holds seven; built by finalize for a set that was
+// filled through flx_screen_set_add, under the switch of the 12-mer prefilter.  flx_kmerset_pre10 is NULL when there is none or when
+// it is too full to pay: more than kPre10FillNum / kPre10FillDen of its bits set.  Measured (profiles/screen.jsonl):
+// at 85 % full the LDS form still beats the 12-mer form alone (4.28 against 5.10 ms per Gbp), at 94 % it loses (5.69 against 5.19).
+constexpr uint64_t kPre10FillNum = 7, kPre10FillDen = 8;
+const uint32_t *flx_kmerset_pre10(const flx_kmerset *set);
+uint64_t flx_kmerset_pre10_bits(const flx_kmerset *set);
+flx_ctx *flx_kmerset_ctx(const flx_kmerset *set);
+void flx_kmerset_mark_screen(flx_kmerset *set);
+
 // ---- pair tables of the wave-level cover kernel (round 3) --------------------------------------------------------------
 // A random lookup is priced per distinct cache LINE an instruction touches, not per lane (tools/tabench: 261 G lines/s from
 // the L2 however many lanes share a line, 55 G/s beyond it), so both tables answer TWO consecutive positions with one byte:

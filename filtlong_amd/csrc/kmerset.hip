@@ -129,6 +129,25 @@ __global__ void __launch_bounds__(256) k_build_exact15(const uint32_t *bm, uint6
     }
 }
 
+// the screen's LDS table (screen.hip) from the 12-mer presence bits: a 10-mer inside a member lies inside one of the member's five
+// 12-mers, at offset 0, 1 or 2 of it, so every present 12-mer marks its three 10-mers (4^10 bits = 128 KiB)
+__global__ void __launch_bounds__(256) k_build_pre10(const uint32_t *pre12, uint32_t *pre10) {
+    const uint32_t n_words = 1u << (kPrefilterBits - 5);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += gridDim.x * blockDim.x) {
+        uint32_t w = pre12[i];
+        while (w) {
+            const int b = __ffs(w) - 1;
+            w &= w - 1;
+            const uint32_t y12 = (i << 5) | (uint32_t)b;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const uint32_t h = (y12 >> (2 * d)) & 0xFFFFFu;
+                atomicOr(&pre10[h >> 5], 1u << (h & 31));
+            }
+        }
+    }
+}
+
 __global__ void __launch_bounds__(256) k_popcount(const uint32_t *bm, uint64_t n_words, unsigned long long *out) {
     unsigned long long acc = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * blockDim.x)
@@ -270,6 +289,10 @@ struct flx_kmerset {
     uint32_t *seen1 = nullptr, *seen2 = nullptr, *seen3 = nullptr;
     uint32_t *prefilter = nullptr;      // 2 MiB, built at finalize (kmerset.h)
     uint32_t *pre11 = nullptr;          // 2 MiB: the same filter, two positions per byte (kmerset.h)
+    bool screen = false;                // filled through flx_screen_set_add: finalize builds the 10-mer table too
+    uint32_t *pre10 = nullptr;          // 128 KiB: the 10-mers inside members, the LDS table of the screen (kmerset.h)
+    uint64_t pre10_bits = 0;            // how many of its 2^20 bits are set
+    bool pre10_always = false;          // FLX_KMER_PREFILTER=10: the table is used however full it is (A/B measurements)
     uint32_t *exact15 = nullptr;        // 1 GiB: exact membership, two positions per byte
     // short-read sequences kept on the device until finalize (only replayed if Bloom candidates exist)
     struct Batch {
@@ -293,6 +316,12 @@ const uint32_t *flx_kmerset_prefilter(const flx_kmerset *set) { return set->pref
 const uint8_t *flx_kmerset_pre11(const flx_kmerset *set) { return (const uint8_t *)set->pre11; }
 const uint8_t *flx_kmerset_exact15(const flx_kmerset *set) { return (const uint8_t *)set->exact15; }
 const flx_locus *flx_kmerset_locus(const flx_kmerset *set) { return set->has_locus ? &set->locus : nullptr; }
+flx_ctx *flx_kmerset_ctx(const flx_kmerset *set) { return set->ctx; }
+void flx_kmerset_mark_screen(flx_kmerset *set) { set->screen = true; }
+const uint32_t *flx_kmerset_pre10(const flx_kmerset *set) {
+    return set->pre10 && (set->pre10_always || set->pre10_bits * kPre10FillDen <= ((uint64_t)kPre10FillNum << 20)) ? set->pre10 : nullptr;
+}
+uint64_t flx_kmerset_pre10_bits(const flx_kmerset *set) { return set->pre10_bits; }
 
 extern "C" int flx_kmerset_create(flx_ctx *ctx, flx_kmerset **out) {
     if (!ctx || !out) return FLX_ERR_INVALID;
@@ -324,7 +353,7 @@ extern "C" void flx_kmerset_destroy(flx_kmerset *s) {
     (void)hipStreamSynchronize(s->ctx->stream);
     free_batches(s->short_batches);
     free_batches(s->asm_batches);
-    for (uint32_t *p : {s->present, s->asm_only, s->seen1, s->seen2, s->seen3, s->prefilter, s->pre11, s->exact15, s->locus_text, s->locus_seed, s->locus_safe1})
+    for (uint32_t *p : {s->present, s->asm_only, s->seen1, s->seen2, s->seen3, s->prefilter, s->pre11, s->pre10, s->exact15, s->locus_text, s->locus_seed, s->locus_safe1})
         if (p) (void)hipFree(p);
     delete s;
 }
@@ -595,6 +624,23 @@ static int build_filters(flx_kmerset *s) {
         FLX_HIP(ctx, hipMemsetAsync(s->pre11, 0, (size_t)2 << 20, st));
         hipLaunchKernelGGL(k_build_pre11, dim3(2048), dim3(256), 0, st, s->prefilter, s->pre11);
         FLX_HIP(ctx, hipStreamSynchronize(st));
+        // the 10-mer table of the screen and how full it is (FLX_KMER_PREFILTER=12: the 12-mer filters alone, =10: the table whatever
+        // its fill — both for A/B measurements)
+        if (s->screen && !(pf_env && strcmp(pf_env, "12") == 0)) {
+            const size_t p10_bytes = (size_t)1 << 17;
+            void *scr;
+            FLX_CHECK(flx_scratch(ctx, 64, &scr));
+            FLX_HIP(ctx, hipMalloc((void **)&s->pre10, p10_bytes));
+            FLX_HIP(ctx, hipMemsetAsync(s->pre10, 0, p10_bytes, st));
+            FLX_HIP(ctx, hipMemsetAsync(scr, 0, 8, st));
+            hipLaunchKernelGGL(k_build_pre10, dim3(2048), dim3(256), 0, st, s->prefilter, s->pre10);
+            hipLaunchKernelGGL(k_popcount, dim3(32), dim3(256), 0, st, s->pre10, (uint64_t)(p10_bytes / 4), (unsigned long long *)scr);
+            unsigned long long bits = 0;
+            FLX_HIP(ctx, hipMemcpyAsync(&bits, scr, 8, hipMemcpyDeviceToHost, st));
+            FLX_HIP(ctx, hipStreamSynchronize(st));
+            s->pre10_bits = bits;
+            s->pre10_always = pf_env && strcmp(pf_env, "10") == 0;
+        }
     }
     if (s->size > 0) {  // the pair form of the exact bitmap (what the cover kernel asks)
         // (no room for it: the set works without — scoring then takes the kernel that asks the 512 MiB bitmap, cover_wave.hip: k_kmer_cover)

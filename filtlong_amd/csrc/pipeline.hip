@@ -15,6 +15,11 @@
 
 #include "flx_internal.h"
 #include "kmerset.h"
+#include "screen.h"
+
+// screen.hip: passed[i] = 0 and child_passed = 0 for the children of every read the screen excludes; excluded[i] says which
+int flx_screen_apply_dev(flx_ctx *ctx, uint64_t n_reads, const int32_t *d_lengths, const uint32_t *d_hits, uint64_t t, uint8_t *d_passed,
+                         const uint64_t *d_child_offsets, uint8_t *d_child_passed, uint8_t *d_excluded);
 
 namespace {
 
@@ -31,6 +36,8 @@ struct Slot {
     uint8_t *d_pass = nullptr;
     int32_t *d_first = nullptr, *d_last = nullptr;
     uint64_t *d_coff = nullptr;
+    uint32_t *d_hits = nullptr;  // with a screen only
+    uint8_t *d_excl = nullptr;
     hipEvent_t copied = nullptr;
     uint64_t n = 0, plane_bytes = 0;
     bool busy = false;  // submitted, not yet scored
@@ -44,6 +51,9 @@ struct flx_pipeline {
     flx_params params;
     bool qsplit = false;     // flx_pipeline_set_qsplit: Phred mode, reads split at their low-quality windows
     double qsplit_q = 0;
+    const flx_kmerset *screen_set = nullptr;  // flx_pipeline_set_screen: reads that match this set fail
+    uint64_t screen_t = 0;
+    int planes = 1;          // 2: a Phred-mode pipeline with a screen — qualities, then sequences, plane_bytes each
     bool submitted = false;  // a chunk has been submitted
     uint64_t cap_bytes = 0, cap_reads = 0;
     Slot slot[2];
@@ -69,6 +79,8 @@ struct flx_pipeline {
     std::vector<uint8_t> passed, child_passed;
     std::vector<int32_t> first, last, child_ranges;
     std::vector<uint64_t> child_offsets;  // global CSR: [n + 1]
+    std::vector<uint32_t> hits;           // with a screen: 16-mers of every read in the set, and who was excluded
+    std::vector<uint8_t> excluded;
     double h2d_s = 0, score_s = 0;
 };
 
@@ -77,11 +89,11 @@ namespace {
 int alloc_slot(flx_pipeline *p, Slot &s) {
     flx_ctx *ctx = p->ctx;
     const uint64_t nr = p->cap_reads;
-    FLX_HIP(ctx, hipHostMalloc((void **)&s.h_plane, p->cap_bytes, hipHostMallocDefault));
+    FLX_HIP(ctx, hipHostMalloc((void **)&s.h_plane, p->cap_bytes * p->planes, hipHostMallocDefault));
     FLX_HIP(ctx, hipHostMalloc((void **)&s.h_off, nr * 16 + 64, hipHostMallocDefault));
     s.h_len = (int32_t *)(s.h_off + nr);
     s.h_ord = (uint32_t *)(s.h_len + nr);
-    FLX_HIP(ctx, hipMalloc((void **)&s.d_plane, p->cap_bytes));
+    FLX_HIP(ctx, hipMalloc((void **)&s.d_plane, p->cap_bytes * p->planes));
     FLX_HIP(ctx, hipMalloc((void **)&s.d_off, nr * 16 + 64));
     s.d_len = (int32_t *)(s.d_off + nr);
     s.d_ord = (uint32_t *)(s.d_len + nr);
@@ -91,6 +103,10 @@ int alloc_slot(flx_pipeline *p, Slot &s) {
     FLX_HIP(ctx, hipMalloc((void **)&s.d_first, nr * 4));
     FLX_HIP(ctx, hipMalloc((void **)&s.d_last, nr * 4));
     FLX_HIP(ctx, hipMalloc((void **)&s.d_coff, (nr + 1) * 8));
+    if (p->screen_set) {
+        FLX_HIP(ctx, hipMalloc((void **)&s.d_hits, nr * 4));
+        FLX_HIP(ctx, hipMalloc((void **)&s.d_excl, nr));
+    }
     FLX_HIP(ctx, hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
     return FLX_OK;
 }
@@ -99,7 +115,7 @@ void free_slot(Slot &s) {
     if (s.h_plane) (void)hipHostFree(s.h_plane);
     if (s.h_off) (void)hipHostFree(s.h_off);
     for (void *d : {(void *)s.d_plane, (void *)s.d_off, (void *)s.d_mean, (void *)s.d_win, (void *)s.d_pass, (void *)s.d_first,
-                    (void *)s.d_last, (void *)s.d_coff})
+                    (void *)s.d_last, (void *)s.d_coff, (void *)s.d_hits, (void *)s.d_excl})
         if (d) (void)hipFree(d);
     if (s.copied) (void)hipEventDestroy(s.copied);
     s = Slot();
@@ -146,6 +162,12 @@ int score_slot(flx_pipeline *p, Slot &s) {
         FLX_CHECK(rc);
         break;
     }
+    if (p->screen_set && n) {  // behind the scoring, on the same stream: the sequences are the chunk's last plane
+        const uint8_t *d_seq = s.d_plane + (uint64_t)(p->planes - 1) * s.plane_bytes;
+        FLX_CHECK(flx_screen_hits_dev(ctx, p->screen_set, d_seq, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, s.d_hits));
+        FLX_CHECK(flx_screen_apply_dev(ctx, n, s.d_len, s.d_hits, p->screen_t, s.d_pass, want_children ? s.d_coff : nullptr,
+                                       want_children ? p->d_cpass : nullptr, s.d_excl));
+    }
     const size_t at = p->mean_q.size();
     p->mean_q.resize(at + n); p->window_q.resize(at + n); p->passed.resize(at + n);
     p->first.resize(at + n); p->last.resize(at + n);
@@ -156,6 +178,13 @@ int score_slot(flx_pipeline *p, Slot &s) {
         FLX_HIP(ctx, hipMemcpyAsync(&p->passed[at], s.d_pass, n, hipMemcpyDeviceToHost, st));
         FLX_HIP(ctx, hipMemcpyAsync(&p->first[at], s.d_first, n * 4, hipMemcpyDeviceToHost, st));
         FLX_HIP(ctx, hipMemcpyAsync(&p->last[at], s.d_last, n * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (p->screen_set) {
+        p->hits.resize(at + n); p->excluded.resize(at + n);
+        if (n) {
+            FLX_HIP(ctx, hipMemcpyAsync(&p->hits[at], s.d_hits, n * 4, hipMemcpyDeviceToHost, st));
+            FLX_HIP(ctx, hipMemcpyAsync(&p->excluded[at], s.d_excl, n, hipMemcpyDeviceToHost, st));
+        }
     }
     const uint64_t nc = want_children ? dev.n_children : 0;
     const uint64_t cbase = p->child_offsets.back();
@@ -255,6 +284,35 @@ extern "C" int flx_pipeline_set_qsplit(flx_pipeline *p, double q) {
     return FLX_OK;
 }
 
+extern "C" int flx_pipeline_set_screen(flx_pipeline *p, const flx_kmerset *exclude_set, double percent) {
+    if (!p) return FLX_ERR_INVALID;
+    flx_ctx *ctx = p->ctx;
+    if (p->submitted || p->handed_out) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_screen after flx_pipeline_next_buffer / flx_pipeline_submit");
+    if (!exclude_set) return flx_fail(ctx, FLX_ERR_INVALID, "flx_pipeline_set_screen: set must not be NULL");
+    if (!flx_kmerset_is_final(exclude_set)) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is not finalized");
+    if (flx_kmerset_size(exclude_set) == 0) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is empty (no run of 16 bases of ACGT in it)");
+    uint64_t t = 0;
+    if (flx_screen_threshold(percent, &t) != FLX_OK) return flx_fail(ctx, FLX_ERR_INVALID, "exclude_percent must be greater than 0 and at most 100");
+    FLX_HIP(ctx, hipSetDevice(ctx->device));
+    const bool kmer_mode = p->set && flx_kmerset_size(p->set) > 0;
+    for (int k = 0; k < 2; ++k) free_slot(p->slot[k]);  // the slots again, with the screen's arrays and (Phred mode) room for the sequences
+    p->screen_set = exclude_set;
+    p->screen_t = t;
+    p->planes = kmer_mode ? 1 : 2;
+    for (int k = 0; k < 2; ++k) FLX_CHECK(alloc_slot(p, p->slot[k]));
+    return FLX_OK;
+}
+
+extern "C" int flx_pipeline_screen(flx_pipeline *p, const uint32_t **hits, const uint8_t **excluded) {
+    if (!p) return FLX_ERR_INVALID;
+    if (!p->screen_set) return flx_fail(p->ctx, FLX_ERR_STATE, "flx_pipeline_screen on a pipeline without a screen");
+    std::unique_lock<std::mutex> lk(p->mu);
+    if (!p->queue.empty()) return flx_fail(p->ctx, FLX_ERR_STATE, "flx_pipeline_screen before flx_pipeline_finish");
+    if (hits) *hits = p->hits.data();
+    if (excluded) *excluded = p->excluded.data();
+    return FLX_OK;
+}
+
 extern "C" int flx_pipeline_reserve(flx_pipeline *p, uint64_t chunk_plane_bytes, uint64_t chunk_reads) {
     if (!p) return FLX_ERR_INVALID;
     flx_ctx *ctx = p->ctx;
@@ -322,7 +380,7 @@ extern "C" int flx_pipeline_submit(flx_pipeline *p, uint64_t plane_bytes, const 
         flx_length_order(s.h_len, n_reads, s.h_ord);  // longest first: the 64 reads of a wavefront finish together
     }
     (void)hipSetDevice(ctx->device);
-    if (plane_bytes) FLX_HIP(ctx, hipMemcpyAsync(s.d_plane, s.h_plane, plane_bytes, hipMemcpyHostToDevice, p->copy_stream));
+    if (plane_bytes) FLX_HIP(ctx, hipMemcpyAsync(s.d_plane, s.h_plane, plane_bytes * p->planes, hipMemcpyHostToDevice, p->copy_stream));
     if (n_reads) {
         FLX_HIP(ctx, hipMemcpyAsync(s.d_off, s.h_off, n_reads * 8, hipMemcpyHostToDevice, p->copy_stream));
         FLX_HIP(ctx, hipMemcpyAsync(s.d_len, s.h_len, n_reads * 4, hipMemcpyHostToDevice, p->copy_stream));

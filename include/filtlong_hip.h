@@ -196,6 +196,38 @@ int flx_score_batch_qsplit_dev(flx_ctx *ctx, const void *d_plane, uint64_t plane
                                double split_window_q, flx_scores *out_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * the contaminant screen (added under version 4; the reference has no counterpart: its users run NanoLyse or chopper --contam over
+ * the whole file in front of it): how many 16-mers of every read are members of a set X built from a contaminant — the lambda control
+ * strand, a vector, a phage, an organelle.  Defined on integers, so every decomposition gives the same answer:
+ *   X          every 16-mer of both strands of the contaminant that consists of ACGTacgt only.  flx_screen_set_add cuts every
+ *              sequence at each byte outside ACGTacgt and hands the pieces of at least 16 bases to flx_kmerset_add_assembly as
+ *              sequences of their own (flx_kmerset_add_assembly encodes any other byte as A, like the reference: an N run would put
+ *              poly-A into X); flx_kmerset_finalize follows as usual.  16-mers cannot screen a large genome: an unrelated read
+ *              keeps |X| / 2^32 of its windows.
+ *   hits[i]    with windows = max(0, L - 15) for a read of L bases: the number of positions p in [0, windows) whose 16 bytes are all
+ *              in ACGTacgt and whose forward 2-bit code (A 0, C 1, G 2, T 3, first base on top: flx_kmerset_contains) is in X
+ *   t          flx_screen_threshold: (uint64_t)ceil(P / 100 * 2^32) in IEEE double; FLX_ERR_INVALID unless 0 < P <= 100.  Host only.
+ *   excluded   iff windows > 0 and ((uint64_t)hits << 32) >= t * windows
+ * flx_screen_hits(_dev): the plane holds SEQUENCES, laid out as for flx_score_batch; `order` may be NULL; hits has n_reads entries
+ * (_dev: every pointer is a device pointer and the call returns with the work queued on the context's stream).  FLX_ERR_STATE for a
+ * set that is empty or not finalized.  The work item is a span of flx_screen_span() window positions of one read (host only: tests
+ * place lengths on its edges), so one very long read spreads over the whole device.  Timed as "flx_screen".
+ * flx_last_screen_filter: which filter stood in front of the exact bitmap in the last call — "lds" (the 10-mers of X in the LDS of
+ * every CU, then the 12-mer prefilter: sets filled through flx_screen_set_add whose 10-mer table is at most seven eighths full),
+ * "pre12" (the 12-mer prefilter alone; FLX_KMER_PREFILTER=12 asks for it, =10 for "lds" however full the table) or "exact" (no
+ * prefilter: FLX_KMER_PREFILTER=0, or a set too large for one).  The hits are the
+ * same whichever runs.
+ * ---------------------------------------------------------------------------------------- */
+int flx_screen_threshold(double percent, uint64_t *t);
+uint32_t flx_screen_span(void);
+int flx_screen_set_add(flx_kmerset *set, const uint8_t *bases, const uint64_t *offsets, const int64_t *lengths, uint64_t n_seqs);
+int flx_screen_hits(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets,
+                    const int32_t *lengths, const uint32_t *order, uint64_t n_reads, uint32_t *hits);
+int flx_screen_hits_dev(flx_ctx *ctx, const flx_kmerset *set, const void *d_plane, uint64_t plane_bytes, const void *d_offsets,
+                        const void *d_lengths, const void *d_order, uint64_t n_reads, uint32_t *d_hits);
+const char *flx_last_screen_filter(const flx_ctx *ctx);
+
+/* ------------------------------------------------------------------------------------------
  * between seam 2 and seam 3 — the reads2 gather     (replaces src/main.cpp:138-147)
  *
  * reads2 = file order with every trimmed / split parent replaced IN PLACE by its children.  Gathers what the global
@@ -295,6 +327,18 @@ int flx_pipeline_create(flx_ctx *ctx, const flx_kmerset *set /* NULL or empty: P
  * flx_pipeline_finish returns the children in its global CSR.  Before the first submit; FLX_ERR_STATE on a pipeline with a non-empty
  * set or after a submit, FLX_ERR_INVALID unless 0 < q < 100. */
 int flx_pipeline_set_qsplit(flx_pipeline *p, double q);
+/* --exclude for a pipeline (added under version 4): every chunk also goes through flx_screen_hits_dev against `exclude_set` (filled
+ * with flx_screen_set_add, finalized, not empty: FLX_ERR_STATE otherwise), on the context's stream behind the scoring; a read with
+ * windows > 0 and (hits << 32) >= t * windows, t = flx_screen_threshold(percent), is treated like a read that fails a hard cut-off: its
+ * pass flag and those of all its children are cleared on the device before the results come back.  It stays an entry.  Before the
+ * first flx_pipeline_next_buffer; FLX_ERR_STATE afterwards, FLX_ERR_INVALID unless 0 < percent <= 100.  In a k-mer-mode pipeline the
+ * one plane (sequences) serves the scoring and the screen.  In a Phred-mode pipeline a chunk then carries TWO planes with the same
+ * offsets: the qualities at [0, plane_bytes) and the sequences at [plane_bytes, 2 plane_bytes) of the staging buffer; plane_bytes,
+ * chunk_plane_bytes, capacity_bytes and flx_pipeline_reserve keep meaning ONE plane, the buffer has room for two.
+ * flx_pipeline_screen: the hits and the excluded flags (1 / 0) of all reads in submission order, host arrays owned by the pipeline,
+ * after flx_pipeline_finish. */
+int flx_pipeline_set_screen(flx_pipeline *p, const flx_kmerset *exclude_set, double percent);
+int flx_pipeline_screen(flx_pipeline *p, const uint32_t **hits, const uint8_t **excluded);
 int flx_pipeline_next_buffer(flx_pipeline *p, uint8_t **plane, uint64_t *capacity_bytes, uint64_t *capacity_reads);
 /* Grow both slots to at least this capacity (never shrinks; waits for the chunks in flight first).  For callers that learn
  * the longest read only while streaming.  Not between next_buffer and submit. */
