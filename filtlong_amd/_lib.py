@@ -34,6 +34,8 @@ ABI_SYMBOLS = [
     "flx_qsplit_table", "flx_qsplit_threshold", "flx_score_batch_qsplit", "flx_score_batch_qsplit_dev", "flx_pipeline_set_qsplit",
     "flx_screen_threshold", "flx_screen_span", "flx_screen_set_add", "flx_screen_hits", "flx_screen_hits_dev", "flx_last_screen_filter",
     "flx_pipeline_set_screen", "flx_pipeline_screen",
+    "flx_adapters_create", "flx_adapters_destroy", "flx_adapters_patterns", "flx_adapter_cuts", "flx_adapter_cuts_dev",
+    "flx_score_batch_adapters", "flx_score_batch_adapters_dev", "flx_pipeline_set_adapters", "flx_pipeline_adapters",
 ]
 
 
@@ -224,5 +226,22 @@ def load():
     L.flx_pipeline_screen.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.flx_last_screen_filter.argtypes = [vp]
     L.flx_last_screen_filter.restype = C.c_char_p
+    if hasattr(L, "flx_adapters_create") or not os.environ.get("FLX_LIB_PATH"):  # (an experiment build of an older tree may lack them)
+        _declare_adapters(L)
     _lib = L
     return L
+
+
+def _declare_adapters(L):
+    vp, u64, i32 = C.c_void_p, C.c_uint64, C.c_int
+    L.flx_adapters_create.argtypes = [vp, vp, vp, u64, i32, i32, C.POINTER(vp)]
+    L.flx_adapters_destroy.argtypes = [vp]
+    L.flx_adapters_destroy.restype = None
+    L.flx_adapters_patterns.argtypes = [vp]
+    L.flx_adapters_patterns.restype = C.c_uint32
+    L.flx_adapter_cuts.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp]
+    L.flx_adapter_cuts_dev.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp]
+    L.flx_score_batch_adapters.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(Params), C.POINTER(Scores)]
+    L.flx_score_batch_adapters_dev.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(Params), C.POINTER(Scores)]
+    L.flx_pipeline_set_adapters.argtypes = [vp, vp]
+    L.flx_pipeline_adapters.argtypes = [vp, C.POINTER(vp)]

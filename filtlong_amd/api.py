@@ -118,11 +118,19 @@ class Context:
         return ms.value, n.value
 
     # ---- seam 2: per-read scoring (host buffers) -----------------------------------------------
-    def score_reads(self, plane, offsets, lengths, params, kmers=None, order=None, child_capacity=None, split_window_q=None):
+    def score_reads(self, plane, offsets, lengths, params, kmers=None, order=None, child_capacity=None, split_window_q=None,
+                    adapters=None, seq_plane=None):
         """Batched Read::Read.  Returns a dict of numpy arrays in input order.  split_window_q (Phred mode only): the reads are
-        split at their low-quality windows (flx_score_batch_qsplit)."""
+        split at their low-quality windows (flx_score_batch_qsplit).  adapters (an Adapters, Phred mode only) with seq_plane, the
+        sequences at the offsets of the qualities: the adapters are cut off the read ends (flx_score_batch_adapters)."""
         if split_window_q is not None and kmers is not None:
             raise ValueError("split_window_q is for Phred mode")
+        if adapters is not None:
+            if kmers is not None or split_window_q is not None:
+                raise ValueError("adapters are for Phred mode, and not with split_window_q")
+            seq_plane = np.ascontiguousarray(seq_plane, dtype=np.uint8)
+            if seq_plane.nbytes != np.asarray(plane).nbytes:
+                raise ValueError("the sequence plane must have the size of the quality plane")
         n = len(lengths)
         plane = np.ascontiguousarray(plane, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -150,7 +158,10 @@ class Context:
             s.child_ranges, s.child_mean_q, s.child_window_q, s.child_passed = (cr.ctypes.data, cm.ctypes.data,
                                                                               cw.ctypes.data, cp.ctypes.data)
             s.child_capacity = child_capacity
-            if split_window_q is not None:
+            if adapters is not None:
+                rc = self.L.flx_score_batch_adapters(self.h, adapters.h, plane.ctypes.data, seq_plane.ctypes.data, plane.nbytes,
+                                                     offsets.ctypes.data, lengths.ctypes.data, ordp, n, C.byref(params), C.byref(s))
+            elif split_window_q is not None:
                 rc = self.L.flx_score_batch_qsplit(self.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data,
                                                    ordp, n, C.byref(params), float(split_window_q), C.byref(s))
             else:
@@ -169,13 +180,14 @@ class Context:
 
     # ---- seam 2, streaming ----------------------------------------------------------------------
     def score_stream(self, chunks, params, kmers=None, chunk_bytes=1 << 20, chunk_reads=1 << 12, grow=False, split_window_q=None,
-                     exclude=None, exclude_percent=10.0):
+                     exclude=None, exclude_percent=10.0, adapters=None):
         """flx_pipeline_*: `chunks` is an iterable of lists of byte strings (Phred mode: qualities, k-mer mode: sequences).
         Every chunk is packed into the pipeline's pinned buffer and submitted; returns the same dict as score_reads for
         all reads in submission order.  grow: enlarge the slots (flx_pipeline_reserve) for a chunk that does not fit.
         split_window_q: flx_pipeline_set_qsplit before the first chunk.  exclude (a Kmers filled with add_screen_fasta):
         flx_pipeline_set_screen with exclude_percent; in Phred mode every chunk is then a PAIR (qualities, sequences) of lists, and
-        the result also has "hits" and "excluded"."""
+        the result also has "hits" and "excluded".  adapters (an Adapters, Phred mode): flx_pipeline_set_adapters; every chunk is
+        such a PAIR as well and the result also has "adapter_keys" (n x 2: head, tail)."""
         L = self.L
         pipe = C.c_void_p()
         self._check(L.flx_pipeline_create(self.h, kmers.h if kmers is not None else None, C.byref(params), chunk_bytes,
@@ -183,9 +195,11 @@ class Context:
         try:
             if split_window_q is not None:
                 self._check(L.flx_pipeline_set_qsplit(pipe, float(split_window_q)))
-            two_planes = exclude is not None and (kmers is None or kmers.empty())
+            two_planes = (exclude is not None or adapters is not None) and (kmers is None or kmers.empty())
             if exclude is not None:
                 self._check(L.flx_pipeline_set_screen(pipe, exclude.h, float(exclude_percent)))
+            if adapters is not None:
+                self._check(L.flx_pipeline_set_adapters(pipe, adapters.h))
             for strings in chunks:
                 seqs = None
                 if two_planes:
@@ -235,6 +249,10 @@ class Context:
                 hp, ep = C.c_void_p(), C.c_void_p()
                 self._check(L.flx_pipeline_screen(pipe, C.byref(hp), C.byref(ep)))
                 out["hits"], out["excluded"] = take(hp, np.uint32, n), take(ep, np.uint8, n)
+            if adapters is not None:
+                kp = C.c_void_p()
+                self._check(L.flx_pipeline_adapters(pipe, C.byref(kp)))
+                out["adapter_keys"] = take(kp, np.uint32, 2 * n).reshape(-1, 2)
             return out
         finally:
             L.flx_pipeline_destroy(pipe)
@@ -401,6 +419,26 @@ class Context:
 
     def screen_hits_dev(self, kmers, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_hits):
         self._check(self.L.flx_screen_hits_dev(self.h, kmers.h, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_hits))
+
+    # ---- adapter trimming -------------------------------------------------------------------------
+    def adapter_cuts(self, plane, offsets, lengths, adapters, order=None):
+        """flx_adapter_cuts: for every read of the SEQUENCE plane its two keys, (jbest << 8) | pattern of the adapter occurrence that
+        reaches furthest into the read at the head and at the tail, 0 without a hit.  uint32 array (n, 2) in input order."""
+        n = len(lengths)
+        plane = np.ascontiguousarray(plane, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        keys = np.full(2 * max(n, 1), 0xA5A5A5A5, dtype=np.uint32)
+        ordp = None
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.uint32)
+            ordp = order.ctypes.data
+        self._check(self.L.flx_adapter_cuts(self.h, adapters.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data,
+                                            ordp, n, keys.ctypes.data))
+        return keys[:2 * n].reshape(-1, 2)
+
+    def adapter_cuts_dev(self, adapters, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_keys):
+        self._check(self.L.flx_adapter_cuts_dev(self.h, adapters.h, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_keys))
 
     def last_screen_filter(self):
         """"lds", "pre12" or "exact": the filter in front of the exact bitmap in the last screen_hits call."""
@@ -744,6 +782,43 @@ class Bgzf:
         if self.h:
             if self.ctx.h:  # destroyed before its context (Context.close() closes it first)
                 self.ctx.L.flx_bgzf_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Adapters:
+    """flx_adapters: the sequences of --trim_adapters (12 to 64 bases of ACGT each, at most 128), each with its reverse complement;
+    errors: the edits a pattern may carry, percent of its length (0..40); window: the bases at either read end that are searched
+    (1..1024).  Belongs to no context."""
+
+    def __init__(self, seqs, errors=20, window=150):
+        seqs = [bytes(s) for s in seqs]
+        n = len(seqs)
+        lengths = np.array([len(s) for s in seqs], dtype=np.int64)
+        offsets = np.zeros(max(n, 1), dtype=np.uint64)
+        if n:
+            offsets[1:n] = np.cumsum(lengths[:-1])
+        bases = np.frombuffer(b"".join(seqs) or b"\0", dtype=np.uint8)
+        self.L = _lib.load()
+        h = C.c_void_p()
+        rc = self.L.flx_adapters_create(bases.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, n, int(errors), int(window), C.byref(h))
+        if rc != _lib.FLX_OK:
+            raise FlxError(rc, "flx_adapters_create: 1 to 128 sequences of 12 to 64 bases of ACGT, errors 0..40, window 1..1024")
+        self.h = h
+        self.errors, self.window = int(errors), int(window)
+
+    def __len__(self):
+        """the number of patterns: two per sequence"""
+        return int(self.L.flx_adapters_patterns(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.flx_adapters_destroy(self.h)
             self.h = None
 
     def __del__(self):

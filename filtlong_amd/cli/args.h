@@ -39,6 +39,9 @@ struct Args {
     bool report_set = false; std::string report;  // not a reference flag: --report FILE receives a JSON summary of the reads before and after
     bool split_window_q_set = false; double split_window_q = 0;  // not a reference flag: --split_window_q Q splits reads at windows below Q (Phred mode)
     bool exclude_set = false; std::string exclude;  // not a reference flag: --exclude FILE drops the reads that match this contaminant (FASTA)
+    bool trim_adapters_set = false; std::string trim_adapters;  // not a reference flag: --trim_adapters FILE cuts the adapters of this FASTA off the read ends (Phred mode)
+    bool adapter_errors_set = false; long long adapter_errors = 20;   // --adapter_errors E: edits a pattern may carry, percent of its length (-1: not an integer)
+    bool adapter_window_set = false; long long adapter_window = 150;  // --adapter_window W: the bases at either end that are searched (-1: not an integer)
     bool exclude_percent_set = false; double exclude_percent = 10.0; std::string exclude_percent_text = "10";  // --exclude_percent P: ... with at least P % of their 16-mers in it
 };
 enum ParsingResult { GOOD, BAD, HELP, VERSION };
@@ -106,13 +109,21 @@ static long long read_ll(const std::string &name, const std::string &value, long
     return v;
 }
 
+// --adapter_errors / --adapter_window: a decimal integer of at most six digits, or -1 (the range check then names the flag)
+static long long whole_number(const std::string &value) {
+    if (value.empty() || value.size() > 6) return -1;
+    for (char c : value)
+        if (!isdigit((unsigned char)c)) return -1;
+    return atoll(value.c_str());
+}
+
 // The help menu of the reference, byte for byte: src/arguments.cpp:126-221 declares the flags and groups and hands them to the
 // formatter of the vendored src/args.h (Help(), 1065-1218, and Wrap(), 94-149), whose layout is a function of the width of the
 // terminal on STDOUT (TIOCGWINSZ; indent 1 / 2 / 3 / 4 for widths up to 60 / 80 / 120 / beyond).  When stdout is no terminal the
 // reference reads the width out of an untouched `struct winsize` — 0 in practice: the description comes out one word per line and,
 // the other widths being unsigned differences that wrap around, nothing else is wrapped at all.  Both cases are restated here.
-// (--gpus, --gzip, --bam, --report, --split_window_q, --exclude and --exclude_percent, this binary's flags of its own, are documented in
-// README.md: the menu is the reference's.)
+// (--gpus, --gzip, --bam, --report, --split_window_q, --exclude, --exclude_percent, --trim_adapters, --adapter_errors and
+// --adapter_window, this binary's flags of its own, are documented in README.md: the menu is the reference's.)
 static std::vector<std::string> help_wrap(const std::string &in, size_t width, size_t first = 0) {  // src/args.h:94-149
     std::vector<std::string> out;
     size_t cur = first ? first : width, linesize = 0;
@@ -284,6 +295,9 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
                 a.exclude_percent = read_double("float", a.exclude_percent_text);
                 a.exclude_percent_set = true;
             }
+            else if (flag == "trim_adapters") { a.trim_adapters = need("trim_adapters"); a.trim_adapters_set = true; }
+            else if (flag == "adapter_errors") { a.adapter_errors = whole_number(need("adapter_errors")); a.adapter_errors_set = true; }
+            else if (flag == "adapter_window") { a.adapter_window = whole_number(need("adapter_window")); a.adapter_window_set = true; }
             else throw ParseError("Error: flag could not be matched: " + flag);
         }
     } catch (const ParseError &e) {
@@ -308,7 +322,7 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     for (auto &f : files)
         if (!file_exists(f)) { std::cerr << "Error: cannot find file: " << f << "\n"; return BAD; }
     if (!a.trim && !a.split_set && !a.target_bases_set && !a.keep_percent_set && !a.min_length_set && !a.max_length_set &&
-        !a.min_mean_q_set && !a.min_window_q_set && !a.split_window_q_set && !a.exclude_set) {
+        !a.min_mean_q_set && !a.min_window_q_set && !a.split_window_q_set && !a.exclude_set && !a.trim_adapters_set) {
         std::cerr << "Error: no thresholds set, you must use one of the following options:\n";
         std::cerr << "target_bases, keep_percent, min_length, max_length, min_mean_q, min_window_q, trim, split\n";
         return BAD;
@@ -338,6 +352,16 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     if (a.exclude_percent_set && !(a.exclude_percent > 0.0 && a.exclude_percent <= 100.0)) {
         std::cerr << "Error: the value for --exclude_percent must be greater than 0 and at most 100\n"; return BAD; }
     if (a.exclude_percent_set && !a.exclude_set) { std::cerr << "Error: --exclude_percent needs --exclude\n"; return BAD; }
+    // --trim_adapters / --adapter_errors / --adapter_window: behind every check above
+    if (a.trim_adapters_set && !file_exists(a.trim_adapters)) { std::cerr << "Error: cannot find file: " << a.trim_adapters << "\n"; return BAD; }
+    if (a.adapter_errors_set && (a.adapter_errors < 0 || a.adapter_errors > 40)) {
+        std::cerr << "Error: the value for --adapter_errors must be an integer between 0 and 40\n"; return BAD; }
+    if (a.adapter_window_set && (a.adapter_window < 1 || a.adapter_window > 1024)) {
+        std::cerr << "Error: the value for --adapter_window must be between 1 and 1024\n"; return BAD; }
+    if (a.adapter_errors_set && !a.trim_adapters_set) { std::cerr << "Error: --adapter_errors needs --trim_adapters\n"; return BAD; }
+    if (a.adapter_window_set && !a.trim_adapters_set) { std::cerr << "Error: --adapter_window needs --trim_adapters\n"; return BAD; }
+    if (a.trim_adapters_set && some_reference) { std::cerr << "Error: --trim_adapters cannot be used with an external reference\n"; return BAD; }
+    if (a.trim_adapters_set && a.split_window_q_set) { std::cerr << "Error: --trim_adapters cannot be used with --split_window_q\n"; return BAD; }
     return GOOD;
 }
 
@@ -352,6 +376,7 @@ static bool open_report_file(const Args &a) {
         inputs.push_back(a.input_reads);
         if (a.assembly_set) inputs.push_back(a.assembly);
         if (a.exclude_set) inputs.push_back(a.exclude);
+        if (a.trim_adapters_set) inputs.push_back(a.trim_adapters);
         for (const auto &f : inputs) {
             struct stat is;
             if (stat(f.c_str(), &is) == 0 && is.st_dev == rs.st_dev && is.st_ino == rs.st_ino) {

@@ -88,8 +88,9 @@ static int exchange_totals(const Run &run, const Pass1 &p, Reads2 &r2) {
     }
     if (run.exclude && rank == 0)
         std::cerr << "  excluded by reference: " << int_to_string((long long)excluded_reads) << " reads (" << int_to_string((long long)excluded_bases) << " bp)\n";
-    if ((args.trim || args.split_set || args.split_window_q_set) && rank == 0) {  // src/main.cpp:155-166 (--split_window_q: "after splitting")
-        if (args.trim && args.split_set) std::cerr << "  after trimming and splitting: ";
+    if ((args.trim || args.split_set || args.split_window_q_set || args.trim_adapters_set) && rank == 0) {  // src/main.cpp:155-166 (--split_window_q: "after splitting")
+        if (args.trim_adapters_set) std::cerr << "  after adapter trimming: ";
+        else if (args.trim && args.split_set) std::cerr << "  after trimming and splitting: ";
         else if (args.trim) std::cerr << "  after trimming: ";
         else std::cerr << "  after splitting: ";
         std::cerr << int_to_string((long long)r2.n_total) << " reads (" << int_to_string(after_total) << " bp)\n";
@@ -131,6 +132,7 @@ static int leave(Run &run, Scorer &scorer, const Report &report) {
         run.stage("pipeline teardown");
         if (run.kmers) flx_kmerset_destroy(run.kmers);
         if (run.exclude) flx_kmerset_destroy(run.exclude);
+        if (run.adapters) flx_adapters_destroy(run.adapters);
         g_gpu_inflater.destroy();
         flx_ctx_destroy(run.ctx);
         run.stage("context teardown");
@@ -211,6 +213,7 @@ int main(int argc, char **argv) {
     // ---- reference 16-mers (src/main.cpp:51-59, src/kmers.cpp:50-72) --------------------------------------
     if (const int rc = build_reference_set(run); rc != kGoOn) return rc;
     if (const int rc = build_exclude_set(run); rc != kGoOn) return rc;  // --exclude: the contaminant's set, on every rank
+    if (const int rc = build_adapters(run); rc != kGoOn) return rc;    // --trim_adapters: the adapters' patterns, on every rank
     run.stage("reference 16-mers");
 
     // ---- pass 1: parse, checks (src/main.cpp:63-130) -----------------------------------------------------

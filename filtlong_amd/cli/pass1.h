@@ -50,7 +50,7 @@ static int open_reads_input(Run &run, ReadsInput &in) {
             if (file.open(args.input_reads) && bam_detect(file.p, file.n)) in.streamed = false;
         }
         in.data.bam = &kBamHooks;
-        in.data.keep_bam = args.bam && !args.trim && !args.split_set && !args.split_window_q_set;  // (--bam: the reads go out whole, as their original records)
+        in.data.keep_bam = args.bam && !args.trim && !args.split_set && !args.split_window_q_set && !args.trim_adapters_set;  // (--bam: the reads go out whole, as their original records)
     }
     if (in.streamed ? !in.blocks.open(args.input_reads, true) : !in.data.open(args.input_reads)) {
         if (!in.streamed && !in.data.bam_error.empty()) std::cerr << "Error: could not read BAM input " << args.input_reads << ": " << in.data.bam_error << "\n";
@@ -114,7 +114,9 @@ struct Scorer {
         if (run.args.split_window_q_set && flx_pipeline_set_qsplit(pipe, run.args.split_window_q) != FLX_OK) return false;
         // --exclude: the pipeline also screens every chunk against the contaminant's set; in Phred mode a chunk then carries the sequences
         // as a second plane behind the qualities
-        return !run.exclude || flx_pipeline_set_screen(pipe, run.exclude, run.args.exclude_percent) == FLX_OK;
+        if (run.exclude && flx_pipeline_set_screen(pipe, run.exclude, run.args.exclude_percent) != FLX_OK) return false;
+        // --trim_adapters: the pipeline cuts the adapters off the read ends and returns at most one child per read; the same second plane
+        return !run.adapters || flx_pipeline_set_adapters(pipe, run.adapters) == FLX_OK;
     }
 
     // Pack records [lo, lo + cnt) of a batch chunk by chunk; their lengths are appended to `lengths`.
@@ -149,7 +151,7 @@ struct Scorer {
         }
         const int32_t *len = lengths.data() + base;
         const bool phred = run.kmers_empty;
-        const bool second_plane = phred && run.exclude != nullptr;
+        const bool second_plane = phred && (run.exclude != nullptr || run.adapters != nullptr);
         for (uint64_t at = 0; at < cnt;) {
             // the next chunk: as many records as fit the slot (flx_plane_layout's rule: 16-byte slots, 128-byte starts for long reads)
             uint64_t end = at, bytes = 0;
@@ -200,6 +202,7 @@ struct Scorer {
         uint64_t n_scored = 0;
         if (flx_pipeline_finish(pipe, &res, &n_scored) != FLX_OK || n_scored != n) return report ? run.fail("scoring") : 1;
         if (run.exclude && flx_pipeline_screen(pipe, &run.screen_hits, &run.screen_excluded) != FLX_OK) return report ? run.fail("scoring") : 1;
+        if (run.adapters && flx_pipeline_adapters(pipe, &run.adapter_keys) != FLX_OK) return report ? run.fail("scoring") : 1;
         return kGoOn;
     }
 };

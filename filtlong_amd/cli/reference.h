@@ -138,3 +138,54 @@ static int build_exclude_set(Run &run) {
     if (n == 0) { std::cerr << "Error: the reference for --exclude holds no 16-mer of ACGT\n"; return 1; }
     return kGoOn;
 }
+
+// ---- --trim_adapters FILE: the adapters' sequences, through the reader of -a (gzip included).  Every rank reads the file itself; the
+// patterns belong to no device until the first chunk asks for them.
+static int build_adapters(Run &run) {
+    const Args &args = run.args;
+    if (!args.trim_adapters_set) return kGoOn;
+    std::cerr << "Reading adapters\n";
+    std::cerr << "  " << args.trim_adapters << "\n";
+    std::vector<uint8_t> pack;
+    std::vector<uint64_t> offsets;
+    std::vector<int64_t> lengths;
+    auto take = [&](const Record &r) {
+        run.adapter_names.push_back(std::string(r.name.sv()));
+        offsets.push_back(pack.size());
+        lengths.push_back((int64_t)r.seq.size());
+        pack.insert(pack.end(), (const uint8_t *)r.seq.p, (const uint8_t *)r.seq.p + r.seq.size());
+    };
+    BlockReader blocks;
+    if (!getenv("FLX_CLI_NO_STREAM") && blocks.open(args.trim_adapters, false)) {
+        Parsed batch;
+        while (blocks.next(batch)) {
+            for (const Record &r : batch.recs) take(r);
+            if (batch.status <= -2) break;
+        }
+    } else {
+        Input data;
+        std::deque<std::string> arena;
+        if (data.open(args.trim_adapters)) {
+            Parser p(data, arena);
+            Record r;
+            while (p.next(r) >= 0) {
+                take(r);
+                arena.clear();
+            }
+        }
+    }
+    const size_t count = offsets.size();
+    std::cerr << "  " << int_to_string((long long)count) << " " << (count == 1 ? "sequence" : "sequences") << "\n\n";
+    for (size_t i = 0; i < count; ++i) {
+        bool good = lengths[i] >= 12 && lengths[i] <= 64;
+        for (int64_t k = 0; good && k < lengths[i]; ++k) good = strchr("ACGTacgt", (char)pack[offsets[i] + (uint64_t)k]) != nullptr && pack[offsets[i] + (uint64_t)k] != 0;
+        if (!good) { std::cerr << "Error: adapter " << run.adapter_names[i] << " must have 12 to 64 bases of ACGT\n"; return 1; }
+    }
+    if (count == 0) { std::cerr << "Error: the file for --trim_adapters holds no sequence\n"; return 1; }
+    if (count > 128) { std::cerr << "Error: the file for --trim_adapters holds more than 128 sequences\n"; return 1; }
+    if (flx_adapters_create(pack.data(), offsets.data(), lengths.data(), count, (int)args.adapter_errors, (int)args.adapter_window, &run.adapters) != FLX_OK) {
+        std::cerr << "Error: the adapters of " << args.trim_adapters << " were refused\n";
+        return 1;
+    }
+    return kGoOn;
+}

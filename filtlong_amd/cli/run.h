@@ -43,6 +43,9 @@ struct Run {
     flx_kmerset *exclude = nullptr;            // --exclude: the contaminant's 16-mers (reference.h: build_exclude_set)
     const uint32_t *screen_hits = nullptr;     // ... and, once the scores are in, every read's hits and whether it was excluded
     const uint8_t *screen_excluded = nullptr;  // (owned by the pipeline; this rank's reads in submission order)
+    flx_adapters *adapters = nullptr;          // --trim_adapters: the patterns (reference.h: build_adapters) ...
+    std::vector<std::string> adapter_names;    // ... the names of their sequences (pattern p belongs to sequence p / 2) ...
+    const uint32_t *adapter_keys = nullptr;    // ... and, once the scores are in, every read's head and tail key (owned by the pipeline)
     flx_params prm;
 
     explicit Run(const Args &a) : args(a) {

@@ -36,6 +36,8 @@ static void print_read_blocks(std::ostream &os, const Run &run, const Pass1 &p, 
             bad.push_back({0, lengths[i]});
         } else if (args.split_window_q_set && res.first[i] == -1 && lengths[i] > 0) {  // --split_window_q: every base lies in a bad window
             bad.push_back({0, lengths[i]});
+        } else if (run.adapter_keys && res.first[i] == -1 && lengths[i] > 0) {  // --trim_adapters: the two cuts leave nothing
+            bad.push_back({0, lengths[i]});
         }
         if (!bad.empty()) {
             os << "        bad ranges = ";
@@ -46,6 +48,11 @@ static void print_read_blocks(std::ostream &os, const Run &run, const Pass1 &p, 
             os << "      child ranges = ";
             for (uint64_t k = a; k < b; ++k) os << c_ranges[2 * k] << "-" << c_ranges[2 * k + 1] << (k + 1 < b ? ", " : "");
             os << "\n";
+        }
+        if (run.adapter_keys) {  // --trim_adapters: the cut lengths and whose adapter reached furthest, behind the lines of the parent's block
+            const uint32_t kh = run.adapter_keys[2 * i], kt = run.adapter_keys[2 * i + 1];
+            os << "          adapters = start " << (kh >> 8) << " (" << (kh ? run.adapter_names[(kh & 255u) >> 1] : std::string("none")) << "), end "
+               << (kt >> 8) << " (" << (kt ? run.adapter_names[(kt & 255u) >> 1] : std::string("none")) << ")\n";
         }
         if (run.screen_hits)  // --exclude: behind the lines of the parent's block
             os << "          excluded = " << (run.screen_excluded[i] ? "yes" : "no") << " (" << run.screen_hits[i] << " of "

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -143,6 +144,13 @@ int flx_ensure_lut_d(flx_ctx *ctx, int window_size);
 // After the synchronisation that ends a Phred scoring call: names the table variant the device chose, and scores the batch's long
 // reads (then synchronises once more) if the detection found any.  A no-op when nothing is pending.
 int flx_phred_finish(flx_ctx *ctx);
+
+// qsplit.hip: the rest of a Phred-mode call with children, whoever produced them (--split_window_q, --trim_adapters).  The caller has
+// filled first / last and out->child_offsets, knows the children's number nc (at most out->child_capacity) and has synchronised;
+// `emit` is called once, when nc > 0, and launches what writes out->child_ranges and the parent of every child into d_parent.
+int flx_phred_children(flx_ctx *ctx, const void *d_plane, uint64_t plane_bytes, const void *d_offsets, const void *d_lengths, const void *d_order,
+                       uint64_t n_reads, const flx_params *params, flx_scores *out, const int32_t *first, uint64_t nc,
+                       const std::function<int(uint32_t *d_parent)> &emit);
 
 int flx_launch_score_phred(flx_ctx *ctx, const uint8_t *d_plane, uint64_t plane_bytes, const uint64_t *d_offsets,
                            const int32_t *d_lengths, const uint32_t *d_order, uint64_t n_reads,

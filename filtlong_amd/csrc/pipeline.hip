@@ -21,6 +21,10 @@
 int flx_screen_apply_dev(flx_ctx *ctx, uint64_t n_reads, const int32_t *d_lengths, const uint32_t *d_hits, uint64_t t, uint8_t *d_passed,
                          const uint64_t *d_child_offsets, uint8_t *d_child_passed, uint8_t *d_excluded);
 
+// adapters.hip: flx_score_batch_adapters_dev that also leaves the keys [2 n] in d_keys (NULL: in a workspace of its own)
+int flx_adapters_score_dev(flx_ctx *ctx, flx_adapters *ad, const void *d_plane, const void *d_seq_plane, uint64_t plane_bytes, const void *d_offsets,
+                           const void *d_lengths, const void *d_order, uint64_t n_reads, const flx_params *params, flx_scores *out, uint32_t *d_keys);
+
 namespace {
 
 struct Slot {
@@ -38,6 +42,7 @@ struct Slot {
     uint64_t *d_coff = nullptr;
     uint32_t *d_hits = nullptr;  // with a screen only
     uint8_t *d_excl = nullptr;
+    uint32_t *d_keys = nullptr;  // with adapters only: [2 n]
     hipEvent_t copied = nullptr;
     uint64_t n = 0, plane_bytes = 0;
     bool busy = false;  // submitted, not yet scored
@@ -53,7 +58,8 @@ struct flx_pipeline {
     double qsplit_q = 0;
     const flx_kmerset *screen_set = nullptr;  // flx_pipeline_set_screen: reads that match this set fail
     uint64_t screen_t = 0;
-    int planes = 1;          // 2: a Phred-mode pipeline with a screen — qualities, then sequences, plane_bytes each
+    flx_adapters *adapters = nullptr;         // flx_pipeline_set_adapters: Phred mode, adapters cut off the read ends
+    int planes = 1;          // 2: a Phred-mode pipeline with a screen or adapters — qualities, then sequences, plane_bytes each
     bool submitted = false;  // a chunk has been submitted
     uint64_t cap_bytes = 0, cap_reads = 0;
     Slot slot[2];
@@ -81,6 +87,7 @@ struct flx_pipeline {
     std::vector<uint64_t> child_offsets;  // global CSR: [n + 1]
     std::vector<uint32_t> hits;           // with a screen: 16-mers of every read in the set, and who was excluded
     std::vector<uint8_t> excluded;
+    std::vector<uint32_t> adapter_keys;   // with adapters: head and tail key of every read
     double h2d_s = 0, score_s = 0;
 };
 
@@ -107,6 +114,7 @@ int alloc_slot(flx_pipeline *p, Slot &s) {
         FLX_HIP(ctx, hipMalloc((void **)&s.d_hits, nr * 4));
         FLX_HIP(ctx, hipMalloc((void **)&s.d_excl, nr));
     }
+    if (p->adapters) FLX_HIP(ctx, hipMalloc((void **)&s.d_keys, nr * 8 + 8));
     FLX_HIP(ctx, hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
     return FLX_OK;
 }
@@ -115,7 +123,7 @@ void free_slot(Slot &s) {
     if (s.h_plane) (void)hipHostFree(s.h_plane);
     if (s.h_off) (void)hipHostFree(s.h_off);
     for (void *d : {(void *)s.d_plane, (void *)s.d_off, (void *)s.d_mean, (void *)s.d_win, (void *)s.d_pass, (void *)s.d_first,
-                    (void *)s.d_last, (void *)s.d_coff, (void *)s.d_hits, (void *)s.d_excl})
+                    (void *)s.d_last, (void *)s.d_coff, (void *)s.d_hits, (void *)s.d_excl, (void *)s.d_keys})
         if (d) (void)hipFree(d);
     if (s.copied) (void)hipEventDestroy(s.copied);
     s = Slot();
@@ -141,7 +149,8 @@ int score_slot(flx_pipeline *p, Slot &s) {
     const uint64_t n = s.n;
     FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, s.copied, 0));
     const bool kmer_mode = p->set && flx_kmerset_size(p->set) > 0;
-    const bool want_children = (kmer_mode && (p->params.trim || p->params.split_set)) || p->qsplit;
+    const bool want_children = (kmer_mode && (p->params.trim || p->params.split_set)) || p->qsplit || p->adapters;
+    const uint8_t *d_seq = s.d_plane + (uint64_t)(p->planes - 1) * s.plane_bytes;  // the sequences are the chunk's last plane
     flx_scores dev;
     for (;;) {
         memset(&dev, 0, sizeof dev);
@@ -153,7 +162,8 @@ int score_slot(flx_pipeline *p, Slot &s) {
             dev.child_ranges = p->d_crng; dev.child_mean_q = p->d_cmean; dev.child_window_q = p->d_cwin;
             dev.child_passed = p->d_cpass; dev.child_capacity = p->child_cap;
         }
-        const int rc = p->qsplit ? flx_score_batch_qsplit_dev(ctx, s.d_plane, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, &p->params, p->qsplit_q, &dev)
+        const int rc = p->adapters ? flx_adapters_score_dev(ctx, p->adapters, s.d_plane, d_seq, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, &p->params, &dev, s.d_keys)
+                       : p->qsplit ? flx_score_batch_qsplit_dev(ctx, s.d_plane, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, &p->params, p->qsplit_q, &dev)
                                  : flx_score_batch_dev(ctx, p->set, s.d_plane, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, &p->params, &dev);
         if (rc == FLX_ERR_CAPACITY && dev.n_children > p->child_cap) {
             FLX_CHECK(grow_children(p, dev.n_children + dev.n_children / 4));
@@ -162,8 +172,7 @@ int score_slot(flx_pipeline *p, Slot &s) {
         FLX_CHECK(rc);
         break;
     }
-    if (p->screen_set && n) {  // behind the scoring, on the same stream: the sequences are the chunk's last plane
-        const uint8_t *d_seq = s.d_plane + (uint64_t)(p->planes - 1) * s.plane_bytes;
+    if (p->screen_set && n) {  // behind the scoring, on the same stream
         FLX_CHECK(flx_screen_hits_dev(ctx, p->screen_set, d_seq, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, s.d_hits));
         FLX_CHECK(flx_screen_apply_dev(ctx, n, s.d_len, s.d_hits, p->screen_t, s.d_pass, want_children ? s.d_coff : nullptr,
                                        want_children ? p->d_cpass : nullptr, s.d_excl));
@@ -185,6 +194,10 @@ int score_slot(flx_pipeline *p, Slot &s) {
             FLX_HIP(ctx, hipMemcpyAsync(&p->hits[at], s.d_hits, n * 4, hipMemcpyDeviceToHost, st));
             FLX_HIP(ctx, hipMemcpyAsync(&p->excluded[at], s.d_excl, n, hipMemcpyDeviceToHost, st));
         }
+    }
+    if (p->adapters) {
+        p->adapter_keys.resize(2 * (at + n));
+        if (n) FLX_HIP(ctx, hipMemcpyAsync(&p->adapter_keys[2 * at], s.d_keys, n * 8, hipMemcpyDeviceToHost, st));
     }
     const uint64_t nc = want_children ? dev.n_children : 0;
     const uint64_t cbase = p->child_offsets.back();
@@ -276,6 +289,7 @@ extern "C" int flx_pipeline_set_qsplit(flx_pipeline *p, double q) {
     flx_ctx *ctx = p->ctx;
     if (p->set && flx_kmerset_size(p->set) > 0) return flx_fail(ctx, FLX_ERR_STATE, "split_window_q is for Phred mode: the pipeline has a k-mer set");
     if (p->submitted) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_qsplit after flx_pipeline_submit");
+    if (p->adapters) return flx_fail(ctx, FLX_ERR_STATE, "split_window_q and adapters do not compose: the pipeline has adapters");
     uint64_t t = 0;
     if (flx_qsplit_threshold(q, &t) != FLX_OK) return flx_fail(ctx, FLX_ERR_INVALID, "split_window_q must be greater than 0 and less than 100");
     if (p->params.trim || p->params.split_set) return flx_fail(ctx, FLX_ERR_INVALID, "trim/split need a k-mer set: not with split_window_q");
@@ -300,6 +314,31 @@ extern "C" int flx_pipeline_set_screen(flx_pipeline *p, const flx_kmerset *exclu
     p->screen_t = t;
     p->planes = kmer_mode ? 1 : 2;
     for (int k = 0; k < 2; ++k) FLX_CHECK(alloc_slot(p, p->slot[k]));
+    return FLX_OK;
+}
+
+extern "C" int flx_pipeline_set_adapters(flx_pipeline *p, flx_adapters *adapters) {
+    if (!p) return FLX_ERR_INVALID;
+    flx_ctx *ctx = p->ctx;
+    if (p->submitted || p->handed_out) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_adapters after flx_pipeline_next_buffer / flx_pipeline_submit");
+    if (p->set && flx_kmerset_size(p->set) > 0) return flx_fail(ctx, FLX_ERR_STATE, "adapters are for Phred mode: the pipeline has a k-mer set");
+    if (p->qsplit) return flx_fail(ctx, FLX_ERR_STATE, "adapters and split_window_q do not compose: the pipeline splits at low-quality windows");
+    if (!adapters) return flx_fail(ctx, FLX_ERR_INVALID, "flx_pipeline_set_adapters: adapters must not be NULL");
+    if (p->params.trim || p->params.split_set) return flx_fail(ctx, FLX_ERR_INVALID, "trim/split need a k-mer set: not with adapters");
+    FLX_HIP(ctx, hipSetDevice(ctx->device));
+    for (int k = 0; k < 2; ++k) free_slot(p->slot[k]);  // the slots again, with the keys and room for the sequences
+    p->adapters = adapters;
+    p->planes = 2;  // (with a screen as well there is still ONE sequence plane)
+    for (int k = 0; k < 2; ++k) FLX_CHECK(alloc_slot(p, p->slot[k]));
+    return FLX_OK;
+}
+
+extern "C" int flx_pipeline_adapters(flx_pipeline *p, const uint32_t **keys) {
+    if (!p) return FLX_ERR_INVALID;
+    if (!p->adapters) return flx_fail(p->ctx, FLX_ERR_STATE, "flx_pipeline_adapters on a pipeline without adapters");
+    std::unique_lock<std::mutex> lk(p->mu);
+    if (!p->queue.empty()) return flx_fail(p->ctx, FLX_ERR_STATE, "flx_pipeline_adapters before flx_pipeline_finish");
+    if (keys) *keys = p->adapter_keys.data();
     return FLX_OK;
 }
 

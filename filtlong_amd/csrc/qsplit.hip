@@ -343,6 +343,30 @@ extern "C" int flx_score_batch_qsplit_dev(flx_ctx *ctx, const void *d_plane, uin
     if (nc && (!out->child_ranges || !out->child_mean_q || !out->child_window_q || !out->child_passed))
         return flx_fail(ctx, FLX_ERR_INVALID, "child outputs are NULL");
 
+    a.child_offsets = out->child_offsets;
+    a.child_ranges = out->child_ranges;
+    a.capacity = nc;
+    return flx_phred_children(ctx, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n_reads, params, out, first, nc, [&](uint32_t *d_parent) {
+        a.child_parent = d_parent;
+        flx_time_scope ti(ctx, "flx_qsplit_detect.emit");
+        hipLaunchKernelGGL(k_qsplit_detect<true>, dim3(grid), dim3(kWaves * 64), 0, st, a);
+        ti.end();
+        FLX_HIP(ctx, hipGetLastError());
+        return (int)FLX_OK;
+    });
+}
+
+// What a Phred-mode call with children does once the producer of the children has filled first / last and out->child_offsets and knows
+// their number: the parents' scoring, the producer's emit pass (child_ranges and the parent of every child), then the child plane and
+// the children's scoring.  Shared by --split_window_q above and --trim_adapters (adapters.hip).
+int flx_phred_children(flx_ctx *ctx, const void *d_plane, uint64_t plane_bytes, const void *d_offsets, const void *d_lengths, const void *d_order,
+                       uint64_t n_reads, const flx_params *params, flx_scores *out, const int32_t *first, uint64_t nc,
+                       const std::function<int(uint32_t *d_parent)> &emit) {
+    hipStream_t st = ctx->stream;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    char *wp = nullptr;
+    auto carve = [&](size_t bytes) { void *p = wp; wp += up(bytes); return p; };
+
     // ---- the parents: today's scoring, untouched; a read with no base left fails ----
     flx_score_out_dev po{out->mean_q, out->window_q, out->passed};
     FLX_CHECK(flx_launch_score_phred(ctx, (const uint8_t *)d_plane, plane_bytes, (const uint64_t *)d_offsets, (const int32_t *)d_lengths,
@@ -368,15 +392,7 @@ extern "C" int flx_score_batch_qsplit_dev(flx_ctx *ctx, const void *d_plane, uin
     uint32_t *d_parent = (uint32_t *)carve(nc * 4);
     int32_t *d_clen = (int32_t *)carve(nc * 4);
     void *d_sortws = carve(sort_ws);
-    a.child_offsets = out->child_offsets;
-    a.child_ranges = out->child_ranges;
-    a.child_parent = d_parent;
-    a.capacity = nc;
-    {
-        flx_time_scope ti(ctx, "flx_qsplit_detect.emit");
-        hipLaunchKernelGGL(k_qsplit_detect<true>, dim3(grid), dim3(kWaves * 64), 0, st, a);
-    }
-    FLX_HIP(ctx, hipGetLastError());
+    FLX_CHECK(emit(d_parent));
     const unsigned cgrid = (unsigned)((nc + 1 + 255) / 256);
     uint64_t child_plane_bytes = 0;
     uint64_t *skeys = nullptr;

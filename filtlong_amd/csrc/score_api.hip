@@ -58,10 +58,12 @@ extern "C" int flx_score_batch_dev(flx_ctx *ctx, const flx_kmerset *set, const v
 }
 
 // the host-array form of a scoring call: everything staged through device buffers of the call's own.  split_window_q (not NULL:
-// flx_score_batch_qsplit) sends the batch through flx_score_batch_qsplit_dev instead of flx_score_batch_dev.
+// flx_score_batch_qsplit) sends the batch through flx_score_batch_qsplit_dev instead of flx_score_batch_dev; adapters (not NULL:
+// flx_score_batch_adapters, with the sequences in seq_plane) through flx_score_batch_adapters_dev.
 static int score_batch_host(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *plane, uint64_t plane_bytes,
                             const uint64_t *offsets, const int32_t *lengths, const uint32_t *order,
-                            uint64_t n_reads, const flx_params *params, const double *split_window_q, flx_scores *out) {
+                            uint64_t n_reads, const flx_params *params, const double *split_window_q, flx_scores *out,
+                            flx_adapters *adapters = nullptr, const uint8_t *seq_plane = nullptr) {
     FLX_CHECK(validate_common(ctx, n_reads, plane_bytes, params, out));
     if (n_reads == 0) {
         out->n_children = 0;
@@ -79,11 +81,11 @@ static int score_batch_host(flx_ctx *ctx, const flx_kmerset *set, const uint8_t 
     pt.mark("validate");
     FLX_HIP(ctx, hipSetDevice(ctx->device));
     const bool kmer_mode = set && flx_kmerset_size(set) > 0;
-    const bool want_children = (kmer_mode && (params->trim || params->split_set)) || split_window_q;
+    const bool want_children = (kmer_mode && (params->trim || params->split_set)) || split_window_q || adapters;
     if (want_children && !out->child_offsets)
         return flx_fail(ctx, FLX_ERR_INVALID, "trim/split requested but child outputs are NULL");
 
-    flx_dbuf d_plane, d_off, d_len, d_ord, d_mean, d_win, d_pass, d_first, d_last;
+    flx_dbuf d_plane, d_seq, d_off, d_len, d_ord, d_mean, d_win, d_pass, d_first, d_last;
     flx_dbuf d_coff, d_crng, d_cmean, d_cwin, d_cpass;
     FLX_CHECK(flx_dalloc(ctx, d_plane, plane_bytes));
     FLX_CHECK(flx_dalloc(ctx, d_off, n_reads * 8));
@@ -97,6 +99,10 @@ static int score_batch_host(flx_ctx *ctx, const flx_kmerset *set, const uint8_t 
     FLX_HIP(ctx, hipMemcpyAsync(d_plane.p, plane, plane_bytes, hipMemcpyHostToDevice, ctx->stream));
     FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pt.mark("plane upload");
+    if (adapters) {
+        FLX_CHECK(flx_dalloc(ctx, d_seq, plane_bytes));
+        FLX_HIP(ctx, hipMemcpyAsync(d_seq.p, seq_plane, plane_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
     FLX_HIP(ctx, hipMemcpyAsync(d_off.p, offsets, n_reads * 8, hipMemcpyHostToDevice, ctx->stream));
     FLX_HIP(ctx, hipMemcpyAsync(d_len.p, lengths, n_reads * 4, hipMemcpyHostToDevice, ctx->stream));
     if (order) {
@@ -150,10 +156,13 @@ static int score_batch_host(flx_ctx *ctx, const flx_kmerset *set, const uint8_t 
         }
     }
     pt.mark("small uploads + alloc");
-    int rc = split_window_q ? flx_score_batch_qsplit_dev(ctx, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr, n_reads,
-                                                         params, *split_window_q, &dev)
-                            : flx_score_batch_dev(ctx, set, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr,
-                                                  n_reads, params, &dev);
+    int rc;
+    if (adapters)
+        rc = flx_score_batch_adapters_dev(ctx, adapters, d_plane.p, d_seq.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr, n_reads, params, &dev);
+    else if (split_window_q)
+        rc = flx_score_batch_qsplit_dev(ctx, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr, n_reads, params, *split_window_q, &dev);
+    else
+        rc = flx_score_batch_dev(ctx, set, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr, n_reads, params, &dev);
     pt.mark("kernels");
     if (rc != FLX_OK) {
         out->n_children = dev.n_children;  // on FLX_ERR_CAPACITY this is the required capacity
@@ -196,4 +205,21 @@ extern "C" int flx_score_batch_qsplit(flx_ctx *ctx, const uint8_t *plane, uint64
     if (ctx && flx_qsplit_threshold(split_window_q, &t) != FLX_OK)
         return flx_fail(ctx, FLX_ERR_INVALID, "split_window_q must be greater than 0 and less than 100");
     return score_batch_host(ctx, nullptr, plane, plane_bytes, offsets, lengths, order, n_reads, params, &split_window_q, out);
+}
+
+extern "C" int flx_score_batch_adapters(flx_ctx *ctx, flx_adapters *adapters, const uint8_t *plane, const uint8_t *seq_plane, uint64_t plane_bytes,
+                                        const uint64_t *offsets, const int32_t *lengths, const uint32_t *order, uint64_t n_reads,
+                                        const flx_params *params, flx_scores *out) {
+    if (!ctx) return FLX_ERR_INVALID;
+    if (!adapters) return flx_fail(ctx, FLX_ERR_INVALID, "flx_score_batch_adapters: adapters must not be NULL");
+    if (n_reads && !seq_plane) return flx_fail(ctx, FLX_ERR_INVALID, "the sequence plane must not be NULL");
+    if (params && (params->trim || params->split_set)) return flx_fail(ctx, FLX_ERR_INVALID, "trim/split need a k-mer set: not with adapters");
+    if (order) {  // a permutation: every key is written by exactly the patterns of its own read end
+        std::vector<uint8_t> seen(n_reads, 0);
+        for (uint64_t i = 0; i < n_reads; ++i) {
+            if (order[i] >= n_reads || seen[order[i]]) return flx_fail(ctx, FLX_ERR_INVALID, "order is not a permutation of the reads");
+            seen[order[i]] = 1;
+        }
+    }
+    return score_batch_host(ctx, nullptr, plane, plane_bytes, offsets, lengths, order, n_reads, params, nullptr, out, adapters, seq_plane);
 }

@@ -60,6 +60,7 @@ enum flx_status {
 
 typedef struct flx_ctx flx_ctx;
 typedef struct flx_kmerset flx_kmerset;
+typedef struct flx_adapters flx_adapters;
 
 /* Hot-path parameters: the fields of the reference's Arguments that Read::Read consults
  * (src/arguments.h:59-91; read in src/read.cpp:61-73,86-117).  *_set mirrors the reference's
@@ -228,6 +229,45 @@ int flx_screen_hits_dev(flx_ctx *ctx, const flx_kmerset *set, const void *d_plan
 const char *flx_last_screen_filter(const flx_ctx *ctx);
 
 /* ------------------------------------------------------------------------------------------
+ * adapter trimming (added under version 4; the reference has no counterpart: its users run an adapter trimmer over the whole file
+ * in front of it): known adapters are cut off the two ends of every read.  Defined on integers, so every decomposition gives the
+ * same answer:
+ *   patterns   every sequence handed to flx_adapters_create, upper-cased, and its reverse complement: pattern 2 i is sequence i,
+ *              pattern 2 i + 1 its reverse complement.  12 to 64 bases of ACGT each, at most 128 sequences.  A pattern of m bases may
+ *              carry k = m * E / 100 edits (integer division), E = errors_percent, 0..40.
+ *   texts      W = window, 1..1024; n = min(L, W) for a read of L bases.  The head text is read[0, n); the tail text is
+ *              read[L - n, L) reversed, matched against the patterns reversed.  Lower case is folded; a byte outside ACGTacgt
+ *              equals no pattern base.
+ *   match      unit-cost edit distance of the whole pattern against any substring of the text: D[0][j] = 0, D[i][0] = i,
+ *              d(j) = D[m][j], 1 <= j <= n; dmin = min d(j), jbest the largest j with d(j) = dmin; a hit iff n >= 1 and dmin <= k.
+ *   keys       per read end, max over the hitting patterns of (jbest << 8) | pattern; 0 without a hit.  cut = key >> 8.
+ *   children   s = cut_head, e = L - cut_tail.  No hit at either end: the read goes on as itself, no children, first = 0, last = L.
+ *              s < e: one child [s, e).  s >= e: no children, first = last = -1 and passed = 0.
+ * flx_adapters_create: FLX_ERR_INVALID for a sequence outside 12..64 bases or not ACGT, no sequence or more than 128, E outside
+ * 0..40 or W outside 1..1024.  The object belongs to no context; a device gets its copy of the patterns with the first call there.
+ * flx_adapter_cuts(_dev): the plane holds SEQUENCES, laid out as for flx_score_batch; `order` may be NULL; keys has 2 * n_reads
+ * entries, head and tail of read i at 2 i and 2 i + 1 (_dev: every pointer is a device pointer and the call returns with the work
+ * queued on the context's stream).  Timed as "flx_adapters".
+ * flx_score_batch_adapters(_dev): the quality plane and the sequence plane share offsets and lengths.  A read keeps the mean_q /
+ * window_q of flx_score_batch; a child gets the bits flx_score_batch gives its quality substring and its own hard cut-offs.
+ * first / last, child_offsets and FLX_ERR_CAPACITY as for flx_score_batch_qsplit.  params->trim and params->split_set must be 0.
+ * ---------------------------------------------------------------------------------------- */
+int flx_adapters_create(const uint8_t *bases, const uint64_t *offsets, const int64_t *lengths, uint64_t n_seqs, int errors_percent,
+                        int window, flx_adapters **out);
+void flx_adapters_destroy(flx_adapters *adapters);
+uint32_t flx_adapters_patterns(const flx_adapters *adapters); /* 2 * n_seqs */
+int flx_adapter_cuts(flx_ctx *ctx, flx_adapters *adapters, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets,
+                     const int32_t *lengths, const uint32_t *order, uint64_t n_reads, uint32_t *keys);
+int flx_adapter_cuts_dev(flx_ctx *ctx, flx_adapters *adapters, const void *d_plane, uint64_t plane_bytes, const void *d_offsets,
+                         const void *d_lengths, const void *d_order, uint64_t n_reads, uint32_t *d_keys);
+int flx_score_batch_adapters(flx_ctx *ctx, flx_adapters *adapters, const uint8_t *plane, const uint8_t *seq_plane, uint64_t plane_bytes,
+                             const uint64_t *offsets, const int32_t *lengths, const uint32_t *order, uint64_t n_reads,
+                             const flx_params *params, flx_scores *out);
+int flx_score_batch_adapters_dev(flx_ctx *ctx, flx_adapters *adapters, const void *d_plane, const void *d_seq_plane, uint64_t plane_bytes,
+                                 const void *d_offsets, const void *d_lengths, const void *d_order, uint64_t n_reads,
+                                 const flx_params *params, flx_scores *out_dev);
+
+/* ------------------------------------------------------------------------------------------
  * between seam 2 and seam 3 — the reads2 gather     (replaces src/main.cpp:138-147)
  *
  * reads2 = file order with every trimmed / split parent replaced IN PLACE by its children.  Gathers what the global
@@ -339,6 +379,15 @@ int flx_pipeline_set_qsplit(flx_pipeline *p, double q);
  * after flx_pipeline_finish. */
 int flx_pipeline_set_screen(flx_pipeline *p, const flx_kmerset *exclude_set, double percent);
 int flx_pipeline_screen(flx_pipeline *p, const uint32_t **hits, const uint8_t **excluded);
+/* --trim_adapters for a Phred-mode pipeline (added under version 4): every chunk then goes through flx_score_batch_adapters_dev.
+ * The chunk carries the second plane exactly as flx_pipeline_set_screen arranged it (qualities, then the sequences at the same
+ * offsets; with both a screen and adapters there is still ONE sequence plane).  The screen keeps looking at the whole parent; an
+ * excluded parent's child fails.  Before the first flx_pipeline_next_buffer; FLX_ERR_STATE afterwards, on a pipeline with a non-empty
+ * set, or together with flx_pipeline_set_qsplit (in either order).
+ * flx_pipeline_adapters: the keys (head, tail) of all reads in submission order, a host array of 2 n entries owned by the pipeline,
+ * valid after flx_pipeline_finish until the pipeline is destroyed. */
+int flx_pipeline_set_adapters(flx_pipeline *p, flx_adapters *adapters);
+int flx_pipeline_adapters(flx_pipeline *p, const uint32_t **keys);
 int flx_pipeline_next_buffer(flx_pipeline *p, uint8_t **plane, uint64_t *capacity_bytes, uint64_t *capacity_reads);
 /* Grow both slots to at least this capacity (never shrinks; waits for the chunks in flight first).  For callers that learn
  * the longest read only while streaming.  Not between next_buffer and submit. */
