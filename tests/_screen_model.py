@@ -60,6 +60,21 @@ def hits(x, read):
     return int(np.count_nonzero(np.isin(codes, x) & valid))
 
 
+def hits_many(x, reads):
+    """hits() of every read in one pass: the rolling codes over the concatenation, every read followed by one byte outside ACGT (a
+    window that reaches it is not valid, so no window belongs to two reads), then one sum per read: uint32 array"""
+    n = len(reads)
+    if n == 0:
+        return np.zeros(0, dtype=np.uint32)
+    starts = np.zeros(n, dtype=np.int64)
+    starts[1:] = np.cumsum([len(r) + 1 for r in reads[:-1]])
+    cat = b"\0".join(bytes(r) for r in reads) + b"\0"
+    codes, valid = window_codes(cat)
+    hit = np.zeros(len(cat), dtype=np.int64)  # (the last 15 bytes start no window)
+    hit[:len(codes)] = np.isin(codes, x) & valid
+    return np.add.reduceat(hit, starts).astype(np.uint32)  # (no segment is empty: a read of no base still has its separator)
+
+
 def windows(length):
     return max(0, int(length) - 15)
 
