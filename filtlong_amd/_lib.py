@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "flx_pipeline_set_screen", "flx_pipeline_screen",
     "flx_adapters_create", "flx_adapters_destroy", "flx_adapters_patterns", "flx_adapter_cuts", "flx_adapter_cuts_dev",
     "flx_score_batch_adapters", "flx_score_batch_adapters_dev", "flx_pipeline_set_adapters", "flx_pipeline_adapters",
+    "flx_adapters_set_split", "flx_adapters_split", "flx_adapter_marks", "flx_adapter_marks_dev",
 ]
 
 
@@ -245,3 +246,8 @@ def _declare_adapters(L):
     L.flx_score_batch_adapters_dev.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(Params), C.POINTER(Scores)]
     L.flx_pipeline_set_adapters.argtypes = [vp, vp]
     L.flx_pipeline_adapters.argtypes = [vp, C.POINTER(vp)]
+    if hasattr(L, "flx_adapters_set_split") or not os.environ.get("FLX_LIB_PATH"):
+        L.flx_adapters_set_split.argtypes = [vp, i32]
+        L.flx_adapters_split.argtypes = [vp]
+        L.flx_adapter_marks.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp]
+        L.flx_adapter_marks_dev.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp]

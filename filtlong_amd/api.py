@@ -440,6 +440,29 @@ class Context:
     def adapter_cuts_dev(self, adapters, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_keys):
         self._check(self.L.flx_adapter_cuts_dev(self.h, adapters.h, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_keys))
 
+    def adapter_marks(self, plane, offsets, lengths, adapters, order=None, bitmap=False):
+        """flx_adapter_marks (adapters with split_errors set): the bases of every read that lie in an adapter occurrence inside it.
+        A list of boolean arrays, one per read in input order; bitmap=True: the uint32 words over the plane as the library returns
+        them, bit offsets[i] + b for base b of read i."""
+        n = len(lengths)
+        plane = np.ascontiguousarray(plane, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        words = np.full(max((plane.nbytes + 31) // 32, 1), 0xA5A5A5A5, dtype=np.uint32)
+        ordp = None
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.uint32)
+            ordp = order.ctypes.data
+        self._check(self.L.flx_adapter_marks(self.h, adapters.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data,
+                                             ordp, n, words.ctypes.data))
+        if bitmap:
+            return words
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little")
+        return [bits[int(o):int(o) + int(l)].astype(bool) for o, l in zip(offsets, lengths)]
+
+    def adapter_marks_dev(self, adapters, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_marks):
+        self._check(self.L.flx_adapter_marks_dev(self.h, adapters.h, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_marks))
+
     def last_screen_filter(self):
         """"lds", "pre12" or "exact": the filter in front of the exact bitmap in the last screen_hits call."""
         return self.L.flx_last_screen_filter(self.h).decode()
@@ -794,9 +817,10 @@ class Bgzf:
 class Adapters:
     """flx_adapters: the sequences of --trim_adapters (12 to 64 bases of ACGT each, at most 128), each with its reverse complement;
     errors: the edits a pattern may carry, percent of its length (0..40); window: the bases at either read end that are searched
-    (1..1024).  Belongs to no context."""
+    (1..1024).  split_errors (0..40, None: off): the adapters INSIDE the reads are searched as well, with that many edits percent, and
+    the reads are split there (flx_adapters_set_split).  Belongs to no context."""
 
-    def __init__(self, seqs, errors=20, window=150):
+    def __init__(self, seqs, errors=20, window=150, split_errors=None):
         seqs = [bytes(s) for s in seqs]
         n = len(seqs)
         lengths = np.array([len(s) for s in seqs], dtype=np.int64)
@@ -811,6 +835,16 @@ class Adapters:
             raise FlxError(rc, "flx_adapters_create: 1 to 128 sequences of 12 to 64 bases of ACGT, errors 0..40, window 1..1024")
         self.h = h
         self.errors, self.window = int(errors), int(window)
+        self.split_errors = None
+        if split_errors is not None:
+            self.set_split(split_errors)
+
+    def set_split(self, split_errors):
+        """flx_adapters_set_split: 0..40 turns the search inside the reads on, None (or -1) off"""
+        v = -1 if split_errors is None else int(split_errors)
+        if self.L.flx_adapters_set_split(self.h, v) != _lib.FLX_OK:
+            raise FlxError(1, "flx_adapters_set_split: split_errors 0..40, or None")
+        self.split_errors = None if v < 0 else v
 
     def __len__(self):
         """the number of patterns: two per sequence"""

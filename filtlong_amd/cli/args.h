@@ -42,6 +42,8 @@ struct Args {
     bool trim_adapters_set = false; std::string trim_adapters;  // not a reference flag: --trim_adapters FILE cuts the adapters of this FASTA off the read ends (Phred mode)
     bool adapter_errors_set = false; long long adapter_errors = 20;   // --adapter_errors E: edits a pattern may carry, percent of its length (-1: not an integer)
     bool adapter_window_set = false; long long adapter_window = 150;  // --adapter_window W: the bases at either end that are searched (-1: not an integer)
+    bool split_adapters = false;  // --split_adapters: reads are also split at the adapters inside them (chimeras); needs --trim_adapters
+    bool adapter_split_errors_set = false; long long adapter_split_errors = 10;  // --adapter_split_errors E2: edits a pattern may carry inside a read, percent (-1: not an integer)
     bool exclude_percent_set = false; double exclude_percent = 10.0; std::string exclude_percent_text = "10";  // --exclude_percent P: ... with at least P % of their 16-mers in it
 };
 enum ParsingResult { GOOD, BAD, HELP, VERSION };
@@ -109,7 +111,7 @@ static long long read_ll(const std::string &name, const std::string &value, long
     return v;
 }
 
-// --adapter_errors / --adapter_window: a decimal integer of at most six digits, or -1 (the range check then names the flag)
+// --adapter_errors / --adapter_window / --adapter_split_errors: a decimal integer of at most six digits, or -1 (the range check then names the flag)
 static long long whole_number(const std::string &value) {
     if (value.empty() || value.size() > 6) return -1;
     for (char c : value)
@@ -122,8 +124,9 @@ static long long whole_number(const std::string &value) {
 // terminal on STDOUT (TIOCGWINSZ; indent 1 / 2 / 3 / 4 for widths up to 60 / 80 / 120 / beyond).  When stdout is no terminal the
 // reference reads the width out of an untouched `struct winsize` — 0 in practice: the description comes out one word per line and,
 // the other widths being unsigned differences that wrap around, nothing else is wrapped at all.  Both cases are restated here.
-// (--gpus, --gzip, --bam, --report, --split_window_q, --exclude, --exclude_percent, --trim_adapters, --adapter_errors and
-// --adapter_window, this binary's flags of its own, are documented in README.md: the menu is the reference's.)
+// (--gpus, --gzip, --bam, --report, --split_window_q, --exclude, --exclude_percent, --trim_adapters, --adapter_errors,
+// --adapter_window, --split_adapters and --adapter_split_errors, this binary's flags of its own, are documented in README.md: the
+// menu is the reference's.)
 static std::vector<std::string> help_wrap(const std::string &in, size_t width, size_t first = 0) {  // src/args.h:94-149
     std::vector<std::string> out;
     size_t cur = first ? first : width, linesize = 0;
@@ -298,6 +301,8 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
             else if (flag == "trim_adapters") { a.trim_adapters = need("trim_adapters"); a.trim_adapters_set = true; }
             else if (flag == "adapter_errors") { a.adapter_errors = whole_number(need("adapter_errors")); a.adapter_errors_set = true; }
             else if (flag == "adapter_window") { a.adapter_window = whole_number(need("adapter_window")); a.adapter_window_set = true; }
+            else if (flag == "split_adapters") a.split_adapters = true;
+            else if (flag == "adapter_split_errors") { a.adapter_split_errors = whole_number(need("adapter_split_errors")); a.adapter_split_errors_set = true; }
             else throw ParseError("Error: flag could not be matched: " + flag);
         }
     } catch (const ParseError &e) {
@@ -362,6 +367,11 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     if (a.adapter_window_set && !a.trim_adapters_set) { std::cerr << "Error: --adapter_window needs --trim_adapters\n"; return BAD; }
     if (a.trim_adapters_set && some_reference) { std::cerr << "Error: --trim_adapters cannot be used with an external reference\n"; return BAD; }
     if (a.trim_adapters_set && a.split_window_q_set) { std::cerr << "Error: --trim_adapters cannot be used with --split_window_q\n"; return BAD; }
+    // --split_adapters / --adapter_split_errors: behind the adapter checks above
+    if (a.adapter_split_errors_set && (a.adapter_split_errors < 0 || a.adapter_split_errors > 40)) {
+        std::cerr << "Error: the value for --adapter_split_errors must be an integer between 0 and 40\n"; return BAD; }
+    if (a.split_adapters && !a.trim_adapters_set) { std::cerr << "Error: --split_adapters needs --trim_adapters\n"; return BAD; }
+    if (a.adapter_split_errors_set && !a.split_adapters) { std::cerr << "Error: --adapter_split_errors needs --split_adapters\n"; return BAD; }
     return GOOD;
 }
 

@@ -60,7 +60,7 @@ static int gather_reads2(const Run &run, const Pass1 &p, const flx_scores &res, 
 }
 
 // totals over all ranks (one rank: the local values), and the line of src/main.cpp:155-166
-static int exchange_totals(const Run &run, const Pass1 &p, Reads2 &r2) {
+static int exchange_totals(const Run &run, const Pass1 &p, const flx_scores &res, Reads2 &r2) {
     const Args &args = run.args;
     const int rank = run.rank, world = run.world;
     long long after_total = 0;
@@ -70,8 +70,13 @@ static int exchange_totals(const Run &run, const Pass1 &p, Reads2 &r2) {
     if (run.screen_excluded)
         for (size_t i = 0; i < p.lengths.size(); ++i)
             if (run.screen_excluded[i]) { ++excluded_reads; excluded_bases += (uint64_t)p.lengths[i]; }
+    uint64_t split_reads = 0;  // --split_adapters: the input reads that went on as two children or more
+    if (args.split_adapters && res.child_offsets)
+        for (size_t i = 0; i < p.lengths.size(); ++i)
+            if (res.child_offsets[i + 1] - res.child_offsets[i] >= 2) ++split_reads;
     if (world > 1) {
-        std::vector<uint64_t> sums(2 * (size_t)world + 1 + (run.exclude ? 2 : 0), 0);
+        std::vector<uint64_t> sums(2 * (size_t)world + 1 + (run.exclude ? 2 : 0) + (args.split_adapters ? 1 : 0), 0);
+        if (args.split_adapters) sums.back() = split_reads;
         if (run.exclude) { sums[2 * (size_t)world + 1] = excluded_reads; sums[2 * (size_t)world + 2] = excluded_bases; }
         sums[rank] = r2.reads.size();
         sums[world] = (uint64_t)after_total;
@@ -81,6 +86,7 @@ static int exchange_totals(const Run &run, const Pass1 &p, Reads2 &r2) {
         for (int r = 0; r < world; ++r) { r2.n_total += sums[r]; r2.longest_name = std::max<size_t>(r2.longest_name, sums[(size_t)world + 1 + r]); }
         after_total = (long long)sums[world];
         if (run.exclude) { excluded_reads = sums[2 * (size_t)world + 1]; excluded_bases = sums[2 * (size_t)world + 2]; }
+        if (args.split_adapters) split_reads = sums.back();
         if (args.verbose && rank == 0) {
             if (!print_verbose_parts(run, "vblocks")) return 1;
             std::cerr << "\n";
@@ -89,6 +95,7 @@ static int exchange_totals(const Run &run, const Pass1 &p, Reads2 &r2) {
     if (run.exclude && rank == 0)
         std::cerr << "  excluded by reference: " << int_to_string((long long)excluded_reads) << " reads (" << int_to_string((long long)excluded_bases) << " bp)\n";
     if ((args.trim || args.split_set || args.split_window_q_set || args.trim_adapters_set) && rank == 0) {  // src/main.cpp:155-166 (--split_window_q: "after splitting")
+        if (args.split_adapters) std::cerr << "  split at adapters: " << int_to_string((long long)split_reads) << " reads\n";
         if (args.trim_adapters_set) std::cerr << "  after adapter trimming: ";
         else if (args.trim && args.split_set) std::cerr << "  after trimming and splitting: ";
         else if (args.trim) std::cerr << "  after trimming: ";
@@ -242,7 +249,7 @@ int main(int argc, char **argv) {
     Reads2 r2;
     if (const int rc = gather_reads2(run, p, res, r2); rc != kGoOn) return rc;
     if (const int rc = print_verbose_blocks(run, p, res); rc != kGoOn) return rc;
-    if (const int rc = exchange_totals(run, p, r2); rc != kGoOn) return rc;
+    if (const int rc = exchange_totals(run, p, res, r2); rc != kGoOn) return rc;
 
     // ---- global stage (src/main.cpp:169-261) ---------------------------------------------------------------
     flx_cut_report rep;

@@ -187,5 +187,10 @@ static int build_adapters(Run &run) {
         std::cerr << "Error: the adapters of " << args.trim_adapters << " were refused\n";
         return 1;
     }
+    // --split_adapters: the same patterns are also searched inside the reads
+    if (args.split_adapters && flx_adapters_set_split(run.adapters, (int)args.adapter_split_errors) != FLX_OK) {
+        std::cerr << "Error: the adapters of " << args.trim_adapters << " were refused\n";
+        return 1;
+    }
     return kGoOn;
 }

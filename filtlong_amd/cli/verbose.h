@@ -53,6 +53,20 @@ static void print_read_blocks(std::ostream &os, const Run &run, const Pass1 &p, 
             const uint32_t kh = run.adapter_keys[2 * i], kt = run.adapter_keys[2 * i + 1];
             os << "          adapters = start " << (kh >> 8) << " (" << (kh ? run.adapter_names[(kh & 255u) >> 1] : std::string("none")) << "), end "
                << (kt >> 8) << " (" << (kt ? run.adapter_names[(kt & 255u) >> 1] : std::string("none")) << ")\n";
+            if (args.split_adapters) {  // --split_adapters: the adapter occurrences inside [s, e) — what the children leave of it
+                const long long s = (long long)(kh >> 8), e = (long long)lengths[i] - (long long)(kt >> 8);
+                long long ranges = 0, bp = 0, from = s;
+                if (a != b) {
+                    for (uint64_t k = a; k < b; ++k) {
+                        if (c_ranges[2 * k] > from) { ++ranges; bp += c_ranges[2 * k] - from; }
+                        from = c_ranges[2 * k + 1];
+                    }
+                    if (from < e) { ++ranges; bp += e - from; }
+                } else if (res.first[i] == -1 && s < e) {
+                    ranges = 1; bp = e - s;
+                }
+                os << "          middle adapters = " << ranges << " ranges (" << bp << " bp)\n";
+            }
         }
         if (run.screen_hits)  // --exclude: behind the lines of the parent's block
             os << "          excluded = " << (run.screen_excluded[i] ? "yes" : "no") << " (" << run.screen_hits[i] << " of "

@@ -16,6 +16,21 @@
 //                 s = cut_head, e = L - cut_tail.  No hit at either end: no child, first = 0, last = L.  s < e: one child [s, e).
 //                 s >= e: no child, first = last = -1 — the read stays one failing entry, like a wholly bad read of qsplit.h.
 //
+// --split_adapters: chimeras are split at the adapters INSIDE a read (adapters_split.hip).  The same patterns over the whole read.
+//   hit ends      the text is the whole read, positions 1..L; pattern p of m bases may carry k2 = m * E2 / 100 edits, E2 =
+//                 --adapter_split_errors, 0..40.  With the recurrence above d_p(j) = D[m][j]; j is a HIT END of p iff d_p(j) <= k2.
+//   marks         every hit end (p, j) marks the bases [max(0, j - m), j); B is the union of all marks.  (Up to k2 bases more than
+//                 the occurrence on either side: the price of a rule that needs no start position.)
+//   children      [s, e) is what the ends rule leaves, unchanged.  No end hit and B empty: no child, first = 0, last = L.  Otherwise
+//                 the children are the maximal runs of bases of [s, e) outside B, ascending; first is the first child's start, last
+//                 the last child's end.  No base left: no child, first = last = -1.
+//   pieces        A column started fresh (D[i][a'] = i) at text position a' computes the minimum over substrings that start at or
+//                 behind a', so it never lies below the true d_p(j).  A substring within k2 edits of the pattern has at most m + k2
+//                 bases, so for every j >= a' + m + k2 the fresh column gives d_p(j) <= k2 exactly when the true one does (values
+//                 above k2 may differ and are never used).  k2 <= 40 % of m: the warm-up is at most 64 + 25 = 89 bases.  A piece
+//                 [a, b) of a read is therefore settled by a walk from max(0, a - kWarmup) to b that reports only the hit ends j
+//                 in (a, b]; its marks may reach back into the piece in front.
+//
 // The column walk is Myers' bit-vector form (J. ACM 46, 1999; the search variant, whose row 0 is all zero): m <= 64 is one word, bit
 // m - 1 of the horizontal deltas carries the change of D[m][j].  Bits above m - 1 hold whatever: carries only travel upwards.
 #pragma once
@@ -37,6 +52,7 @@ constexpr int kMaxSeqs = 128;                  // 256 patterns: the pattern inde
 constexpr int kMaxErrors = 40;                 // E, percent
 constexpr int kMaxWindow = 1024;               // W
 constexpr uint32_t kNoBase = 4;                // the code of a text byte outside ACGTacgt
+constexpr int kWarmup = 96;                    // bases a piece's walk starts in front of it: >= m + k2 (89 at most), a multiple of 4
 
 ADAPTERS_FN bool is_acgt(uint8_t c) {
     const uint32_t d = (uint32_t)(c | 0x20u) - 0x61u;  // a 0, c 2, g 6, t 19
@@ -69,8 +85,9 @@ ADAPTERS_FN void column_start(Column *s, uint32_t m) {
     s->jbest = 0;
 }
 
-// text base j (1-based) whose match mask against the pattern is eq; top = 1 << (m - 1)
-ADAPTERS_FN void column_step(Column *s, uint64_t eq, uint64_t top, int32_t j) {
+// one text base whose match mask against the pattern is eq; top = 1 << (m - 1): pv, mv and the score at row m, nothing else (the
+// middle search only asks whether the score is within k2)
+ADAPTERS_FN void column_advance(Column *s, uint64_t eq, uint64_t top) {
     const uint64_t pv = s->pv, mv = s->mv;
     const uint64_t xv = eq | mv;
     const uint64_t xh = (((eq & pv) + pv) ^ pv) | eq;
@@ -82,6 +99,11 @@ ADAPTERS_FN void column_step(Column *s, uint64_t eq, uint64_t top, int32_t j) {
     mh <<= 1;
     s->pv = mh | ~(xv | ph);
     s->mv = ph & xv;
+}
+
+// text base j (1-based): the column's step and the minimum's bookkeeping of the ends rule
+ADAPTERS_FN void column_step(Column *s, uint64_t eq, uint64_t top, int32_t j) {
+    column_advance(s, eq, top);
     if (s->score <= s->dmin) {  // <=: the largest j wins a tie
         s->dmin = s->score;
         s->jbest = j;
@@ -113,6 +135,61 @@ ADAPTERS_FN int child_of(uint32_t key_head, uint32_t key_tail, int64_t L, int32_
     *first = -1;
     *last = -1;
     return 0;
+}
+
+// The marks of one (piece, pattern) walk come as runs: hit ends at consecutive j give overlapping marks.  A walk keeps the current run
+// [lo, hi) and hands a finished one to `flush`; hit ends arrive with ascending j.
+struct MarkRun {
+    int32_t lo = -1, hi = -1;  // hi < 0: no run
+};
+template <class Flush>
+ADAPTERS_FN void mark_hit(MarkRun *r, int32_t j, int32_t m, Flush &&flush) {
+    const int32_t lo = j > m ? j - m : 0;
+    if (r->hi >= 0 && lo <= r->hi) {
+        r->hi = j;
+        return;
+    }
+    if (r->hi >= 0) flush(r->lo, r->hi);
+    r->lo = lo;
+    r->hi = j;
+}
+template <class Flush>
+ADAPTERS_FN void mark_end(MarkRun *r, Flush &&flush) {
+    if (r->hi >= 0) flush(r->lo, r->hi);
+    r->hi = -1;
+}
+
+// The mark bitmap: bit (offset + i) says base i of the read at `offset` of the plane lies in B; 32-bit words, bit b of word w is
+// bit 32 w + b.  A plane of plane_bytes has mark_words(plane_bytes) words.
+ADAPTERS_FN uint64_t mark_words(uint64_t plane_bytes) { return (plane_bytes + 31) / 32; }
+
+// [s, e) of a read of L bases from its two keys; false: s >= e, nothing is left
+ADAPTERS_FN bool kept_range(uint32_t key_head, uint32_t key_tail, int64_t L, int64_t *s, int64_t *e) {
+    *s = (int64_t)(key_head >> 8);
+    *e = L - (int64_t)(key_tail >> 8);
+    return *s < *e;
+}
+
+// One 32-bit word of the child walk.  `free_bits`: the bases of this word that lie in [s, e) and outside B; `carry`: whether the base
+// in front of the word was such a base.  A child starts at every bit of *starts and ends in front of every bit of *ends; the
+// k-th start and the k-th end of a read belong to one child.  (A child that reaches e ends at the bit of e, which is never free.)
+ADAPTERS_FN void child_edges(uint32_t free_bits, uint32_t carry, uint32_t *starts, uint32_t *ends) {
+    const uint32_t before = (free_bits << 1) | (carry & 1u);
+    *starts = free_bits & ~before;
+    *ends = ~free_bits & before;
+}
+
+// What the child walk of a read comes to: n children found, whether an end hit or a mark inside [s, e) was seen
+ADAPTERS_FN int64_t split_summary(bool end_hit, bool any_mark, int64_t n, int64_t L, int32_t first_start, int32_t last_end, int32_t *first,
+                                  int32_t *last) {
+    if (!end_hit && !any_mark) {
+        *first = 0;
+        *last = (int32_t)L;
+        return 0;
+    }
+    *first = n ? first_start : -1;
+    *last = n ? last_end : -1;
+    return n;
 }
 
 // ---- host only from here --------------------------------------------------------------------------------------------------------
@@ -177,6 +254,87 @@ inline uint32_t end_key(const uint8_t *read, int64_t L, int side, int64_t W, con
         }
     }
     return key;
+}
+
+// The serial walk of --split_adapters for one read: the kernel's oracle.  Sets marked[i] = 1 for every base of B (marked has L
+// entries, zero before).  Reads read[0, L) and nothing else.
+inline void middle_marks(const uint8_t *read, int64_t L, const Pattern *patterns, uint32_t n_patterns, uint32_t split_errors_percent,
+                         uint8_t *marked) {
+    for (uint32_t p = 0; p < n_patterns; ++p) {
+        const Pattern &pat = patterns[p];
+        const int32_t k2 = (int32_t)edits_allowed(pat.m, split_errors_percent);
+        const uint64_t top = 1ull << (pat.m - 1);
+        Column col;
+        column_start(&col, pat.m);
+        MarkRun run;
+        auto flush = [&](int32_t lo, int32_t hi) {
+            for (int32_t i = lo; i < hi; ++i) marked[i] = 1;
+        };
+        for (int64_t j = 0; j < L; ++j) {
+            column_advance(&col, select_eq(pat.peq_head, code_of(read[j])), top);
+            if (col.score <= k2) mark_hit(&run, (int32_t)(j + 1), (int32_t)pat.m, flush);
+        }
+        mark_end(&run, flush);
+    }
+}
+
+// The same marks piece by piece, pieces of S bases: every piece walks from max(0, a - kWarmup) and reports the hit ends in (a, b].
+// What the kernel does, serially; equal to middle_marks by the argument at the top.
+inline void middle_marks_pieces(const uint8_t *read, int64_t L, int64_t S, const Pattern *patterns, uint32_t n_patterns,
+                                uint32_t split_errors_percent, uint8_t *marked) {
+    for (int64_t a = 0; a < L; a += S) {
+        const int64_t b = a + S < L ? a + S : L, from = a > kWarmup ? a - kWarmup : 0;
+        for (uint32_t p = 0; p < n_patterns; ++p) {
+            const Pattern &pat = patterns[p];
+            const int32_t k2 = (int32_t)edits_allowed(pat.m, split_errors_percent);
+            const uint64_t top = 1ull << (pat.m - 1);
+            Column col;
+            column_start(&col, pat.m);
+            MarkRun run;
+            auto flush = [&](int32_t lo, int32_t hi) {
+                for (int32_t i = lo; i < hi; ++i) marked[i] = 1;
+            };
+            for (int64_t j = from; j < b; ++j) {
+                column_advance(&col, select_eq(pat.peq_head, code_of(read[j])), top);
+                if (j >= a && col.score <= k2) mark_hit(&run, (int32_t)(j + 1), (int32_t)pat.m, flush);
+            }
+            mark_end(&run, flush);
+        }
+    }
+}
+
+// The children of one read from its keys and its marks (marked[0, L)), by the word walk the kernel makes: ranges gets (start, end)
+// pairs appended; returns their number and sets first / last.
+inline int64_t split_children(uint32_t key_head, uint32_t key_tail, int64_t L, const uint8_t *marked, std::vector<int32_t> *ranges, int32_t *first,
+                              int32_t *last) {
+    int64_t s, e;
+    const bool end_hit = (key_head | key_tail) != 0u;
+    if (!kept_range(key_head, key_tail, L, &s, &e)) return split_summary(end_hit, false, 0, L, -1, -1, first, last);  // (no end hit: L = 0)
+    std::vector<int32_t> st, en;
+    bool any_mark = false;
+    uint32_t carry = 0;
+    for (int64_t w = s >> 5; w <= e >> 5; ++w) {  // (the word of e too: a child that reaches e ends there)
+        uint32_t free_bits = 0;
+        for (int b = 0; b < 32; ++b) {
+            const int64_t i = 32 * w + b;
+            if (i < s || i >= e) continue;
+            if (marked[i]) any_mark = true;
+            else free_bits |= 1u << b;
+        }
+        uint32_t starts, ends;
+        child_edges(free_bits, carry, &starts, &ends);
+        for (int b = 0; b < 32; ++b) {
+            if ((starts >> b) & 1u) st.push_back((int32_t)(32 * w + b));
+            if ((ends >> b) & 1u) en.push_back((int32_t)(32 * w + b));
+        }
+        carry = free_bits >> 31;
+    }
+    const int64_t n = split_summary(end_hit, any_mark, (int64_t)st.size(), L, st.empty() ? -1 : st.front(), en.empty() ? -1 : en.back(), first, last);
+    for (int64_t k = 0; k < n; ++k) {
+        ranges->push_back(st[(size_t)k]);
+        ranges->push_back(en[(size_t)k]);
+    }
+    return n;
 }
 
 }  // namespace adapters

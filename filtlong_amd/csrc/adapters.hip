@@ -15,21 +15,14 @@
 //   children         k_adapter_children turns the two keys into the child CSR's count, first and last (the rule: adapters.h);
 //                    k_adapter_emit writes the one range.  Everything behind that — the child plane, the children's scoring — is
 //                    the code --split_window_q runs (qsplit.hip: flx_phred_children).
+//   --split_adapters an object with the middle search on (flx_adapters_set_split) takes its children from adapters_split.hip
+//                    instead: the keys as before, then the marks over the whole read and the child walk over both.
 #include <algorithm>
-#include <mutex>
 
-#include "flx_internal.h"
-#include "adapters.h"
+#include "adapters_internal.h"
 #include "rank_internal.h"
 
 using adapters::Pattern;
-
-struct flx_adapters {
-    std::vector<Pattern> patterns;
-    int errors_percent = 0, window = 0;
-    std::mutex mu;
-    std::vector<std::pair<int, Pattern *>> on_device;  // the pattern table, uploaded once per device that asks for it
-};
 
 namespace {
 
@@ -149,8 +142,10 @@ __global__ void __launch_bounds__(256) k_adapter_emit(uint64_t n_reads, const ui
     child_parent[at] = (uint32_t)r;
 }
 
+}  // namespace
+
 // the adapters' pattern table on the context's device
-int table_on_device(flx_ctx *ctx, flx_adapters *ad, const Pattern **out) {
+int flx_adapters_table(flx_ctx *ctx, flx_adapters *ad, const Pattern **out) {
     std::lock_guard<std::mutex> lk(ad->mu);
     for (auto &d : ad->on_device)
         if (d.first == ctx->device) {
@@ -170,7 +165,7 @@ int table_on_device(flx_ctx *ctx, flx_adapters *ad, const Pattern **out) {
     return FLX_OK;
 }
 
-int check_reads(flx_ctx *ctx, uint64_t plane_bytes, const uint64_t *offsets, const int32_t *lengths, const uint32_t *order, uint64_t n_reads) {
+int flx_adapters_check_reads(flx_ctx *ctx, uint64_t plane_bytes, const uint64_t *offsets, const int32_t *lengths, const uint32_t *order, uint64_t n_reads) {
     for (uint64_t i = 0; i < n_reads; ++i) {
         if (lengths[i] < 0 || (offsets[i] & 15) || offsets[i] + (((uint64_t)lengths[i] + 15) & ~15ull) > plane_bytes)
             return flx_fail(ctx, FLX_ERR_INVALID, "read %llu: offset must be 16-byte aligned and inside the plane", (unsigned long long)i);
@@ -184,8 +179,6 @@ int check_reads(flx_ctx *ctx, uint64_t plane_bytes, const uint64_t *offsets, con
     }
     return FLX_OK;
 }
-
-}  // namespace
 
 extern "C" int flx_adapters_create(const uint8_t *bases, const uint64_t *offsets, const int64_t *lengths, uint64_t n_seqs, int errors_percent,
                                    int window, flx_adapters **out) {
@@ -222,7 +215,7 @@ extern "C" int flx_adapter_cuts_dev(flx_ctx *ctx, flx_adapters *ad, const void *
     FLX_HIP(ctx, hipSetDevice(ctx->device));
     CutArgs a;
     memset(&a, 0, sizeof a);
-    FLX_CHECK(table_on_device(ctx, ad, &a.patterns));
+    FLX_CHECK(flx_adapters_table(ctx, ad, &a.patterns));
     a.plane = (const uint8_t *)d_plane;
     a.offsets = (const uint64_t *)d_offsets;
     a.lengths = (const int32_t *)d_lengths;
@@ -250,7 +243,7 @@ extern "C" int flx_adapter_cuts(flx_ctx *ctx, flx_adapters *ad, const uint8_t *p
     if (plane_bytes & 15) return flx_fail(ctx, FLX_ERR_INVALID, "plane_bytes must be a multiple of 16");
     if (n_reads == 0) return FLX_OK;
     if (!plane || !offsets || !lengths || !keys) return flx_fail(ctx, FLX_ERR_INVALID, "plane/offsets/lengths/keys must not be NULL");
-    FLX_CHECK(check_reads(ctx, plane_bytes, offsets, lengths, order, n_reads));
+    FLX_CHECK(flx_adapters_check_reads(ctx, plane_bytes, offsets, lengths, order, n_reads));
     FLX_HIP(ctx, hipSetDevice(ctx->device));
     flx_dbuf d_plane, d_off, d_len, d_ord, d_keys;
     FLX_CHECK(flx_dalloc(ctx, d_plane, plane_bytes ? plane_bytes : 16));
@@ -298,21 +291,33 @@ int flx_adapters_score_dev(flx_ctx *ctx, flx_adapters *ad, const void *d_plane, 
     // ---- per-read arrays (workspace 0) ----
     const size_t scan_ws = flx_radix_sort_workspace(n_reads + 1);
     void *small = nullptr;
-    FLX_CHECK(flx_workspace(ctx, 0, up((n_reads + 1) * 8) + 2 * up(n_reads * 4) + up(n_reads * 8) + up(scan_ws), &small));
+    // (an object with the middle search on: the mark bitmap and the scratch of its kernels behind the rest)
+    const int e2 = ad->split_errors_percent;
+    const size_t mark_bytes = e2 >= 0 ? adapters::mark_words(plane_bytes) * 4 : 0;
+    const size_t split_room = e2 >= 0 ? up(mark_bytes) + up(flx_adapter_marks_scratch(n_reads)) : 0;
+    FLX_CHECK(flx_workspace(ctx, 0, up((n_reads + 1) * 8) + 2 * up(n_reads * 4) + up(n_reads * 8) + up(scan_ws) + split_room, &small));
     wp = (char *)small;
     int64_t *d_nchild = (int64_t *)carve((n_reads + 1) * 8);
     int32_t *d_first_tmp = (int32_t *)carve(n_reads * 4), *d_last_tmp = (int32_t *)carve(n_reads * 4);
     uint32_t *d_keys = (uint32_t *)carve(n_reads * 8);
     if (d_keys_out) d_keys = d_keys_out;
     void *d_scanws = carve(scan_ws);
+    uint32_t *d_marks = e2 >= 0 ? (uint32_t *)carve(mark_bytes) : nullptr;
+    void *d_mark_scratch = e2 >= 0 ? carve(flx_adapter_marks_scratch(n_reads)) : nullptr;
     int32_t *first = out->first ? out->first : d_first_tmp, *last = out->last ? out->last : d_last_tmp;
 
-    // ---- the cuts -> child_offsets ----
+    // ---- the cuts (and the marks) -> child_offsets ----
     FLX_CHECK(flx_adapter_cuts_dev(ctx, ad, d_seq_plane, plane_bytes, d_offsets, d_lengths, d_order, n_reads, d_keys));
     const unsigned grid = (unsigned)((n_reads + 1 + 255) / 256);
-    hipLaunchKernelGGL(k_adapter_children, dim3(grid), dim3(256), 0, st, n_reads, (const int32_t *)d_lengths, (const uint32_t *)d_keys, d_nchild,
-                       first, last);
-    FLX_HIP(ctx, hipGetLastError());
+    if (e2 >= 0) {
+        FLX_CHECK(flx_adapter_marks_launch(ctx, ad, e2, d_seq_plane, plane_bytes, d_offsets, d_lengths, d_order, n_reads, d_marks, d_mark_scratch));
+        FLX_CHECK(flx_adapter_split_launch(ctx, false, n_reads, d_offsets, d_lengths, d_keys, d_marks, d_nchild, first, last, nullptr, 0, nullptr,
+                                           nullptr));
+    } else {
+        hipLaunchKernelGGL(k_adapter_children, dim3(grid), dim3(256), 0, st, n_reads, (const int32_t *)d_lengths, (const uint32_t *)d_keys, d_nchild,
+                           first, last);
+        FLX_HIP(ctx, hipGetLastError());
+    }
     FLX_CHECK(flx_exclusive_scan_i64(ctx, n_reads + 1, d_nchild, (int64_t *)out->child_offsets, d_scanws, scan_ws));
     int64_t total = 0;
     FLX_HIP(ctx, hipMemcpyAsync(&total, (int64_t *)out->child_offsets + n_reads, 8, hipMemcpyDeviceToHost, st));
@@ -326,6 +331,9 @@ int flx_adapters_score_dev(flx_ctx *ctx, flx_adapters *ad, const void *d_plane, 
         return flx_fail(ctx, FLX_ERR_INVALID, "child outputs are NULL");
 
     return flx_phred_children(ctx, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n_reads, params, out, first, nc, [&](uint32_t *d_parent) {
+        if (e2 >= 0)
+            return flx_adapter_split_launch(ctx, true, n_reads, d_offsets, d_lengths, d_keys, d_marks, nullptr, nullptr, nullptr,
+                                            (const uint64_t *)out->child_offsets, nc, out->child_ranges, d_parent);
         hipLaunchKernelGGL(k_adapter_emit, dim3(grid), dim3(256), 0, st, n_reads, (const uint64_t *)out->child_offsets, (const int32_t *)first,
                            (const int32_t *)last, nc, out->child_ranges, d_parent);
         FLX_HIP(ctx, hipGetLastError());

@@ -266,6 +266,25 @@ int flx_score_batch_adapters(flx_ctx *ctx, flx_adapters *adapters, const uint8_t
 int flx_score_batch_adapters_dev(flx_ctx *ctx, flx_adapters *adapters, const void *d_plane, const void *d_seq_plane, uint64_t plane_bytes,
                                  const void *d_offsets, const void *d_lengths, const void *d_order, uint64_t n_reads,
                                  const flx_params *params, flx_scores *out_dev);
+/* Adapters INSIDE the reads (chimeras; added under version 4).  The same patterns over the whole read, positions 1..L:
+ *   hit ends   pattern p of m bases may carry k2 = m * E2 / 100 edits, E2 = split_errors_percent, 0..40; with the recurrence above
+ *              d_p(j) = D[m][j], and j is a hit end of p iff d_p(j) <= k2.
+ *   marks      every hit end (p, j) marks the bases [max(0, j - m), j); B is the union of all marks.
+ *   children   [s, e) is what the ends rule leaves.  No end hit and B empty: no children, first = 0, last = L.  Otherwise the
+ *              children are the maximal runs of bases of [s, e) outside B, ascending; first is the first child's start, last the
+ *              last child's end.  No base left: no children, first = last = -1 and passed = 0.
+ * flx_adapters_set_split: 0..40 turns the middle search on for that object, -1 off (the state after flx_adapters_create); anything
+ * else is FLX_ERR_INVALID.  flx_adapters_split: the value set, -1 while off.  flx_score_batch_adapters(_dev) and a pipeline with
+ * flx_pipeline_set_adapters follow the object: with the search on a read may have any number of children.
+ * flx_adapter_marks(_dev): B as a bitmap over the sequence plane, bit (offsets[i] + b) of it for base b of read i, bit x in
+ * 32-bit word x / 32 at x % 32; marks has (plane_bytes + 31) / 32 words, every one written.  Arguments and checks as for
+ * flx_adapter_cuts; FLX_ERR_INVALID on an object with the search off.  Timed as "flx_adapter_marks". */
+int flx_adapters_set_split(flx_adapters *adapters, int split_errors_percent);
+int flx_adapters_split(const flx_adapters *adapters);
+int flx_adapter_marks(flx_ctx *ctx, flx_adapters *adapters, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets,
+                      const int32_t *lengths, const uint32_t *order, uint64_t n_reads, uint32_t *marks);
+int flx_adapter_marks_dev(flx_ctx *ctx, flx_adapters *adapters, const void *d_plane, uint64_t plane_bytes, const void *d_offsets,
+                          const void *d_lengths, const void *d_order, uint64_t n_reads, uint32_t *d_marks);
 
 /* ------------------------------------------------------------------------------------------
  * between seam 2 and seam 3 — the reads2 gather     (replaces src/main.cpp:138-147)
