@@ -34,6 +34,8 @@ ABI_SYMBOLS = [
     "flx_qsplit_table", "flx_qsplit_threshold", "flx_score_batch_qsplit", "flx_score_batch_qsplit_dev", "flx_pipeline_set_qsplit",
     "flx_screen_threshold", "flx_screen_span", "flx_screen_set_add", "flx_screen_hits", "flx_screen_hits_dev", "flx_last_screen_filter",
     "flx_pipeline_set_screen", "flx_pipeline_screen",
+    "flx_screenset_create", "flx_screenset_add", "flx_screenset_finalize", "flx_screenset_size", "flx_screenset_k", "flx_screenset_capacity",
+    "flx_screenset_destroy", "flx_screenset_hits", "flx_screenset_hits_dev", "flx_pipeline_set_screenset",
     "flx_adapters_create", "flx_adapters_destroy", "flx_adapters_patterns", "flx_adapter_cuts", "flx_adapter_cuts_dev",
     "flx_score_batch_adapters", "flx_score_batch_adapters_dev", "flx_pipeline_set_adapters", "flx_pipeline_adapters",
     "flx_adapters_set_split", "flx_adapters_split", "flx_adapter_marks", "flx_adapter_marks_dev",
@@ -227,6 +229,20 @@ def load():
     L.flx_pipeline_screen.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.flx_last_screen_filter.argtypes = [vp]
     L.flx_last_screen_filter.restype = C.c_char_p
+    if hasattr(L, "flx_screenset_create") or not os.environ.get("FLX_LIB_PATH"):  # (an experiment build of an older tree may lack them)
+        L.flx_screenset_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
+        L.flx_screenset_add.argtypes = [vp, vp, vp, vp, u64]
+        L.flx_screenset_finalize.argtypes = [vp]
+        L.flx_screenset_size.argtypes = [vp]
+        L.flx_screenset_size.restype = u64
+        L.flx_screenset_k.argtypes = [vp]
+        L.flx_screenset_capacity.argtypes = [vp]
+        L.flx_screenset_capacity.restype = u64
+        L.flx_screenset_destroy.argtypes = [vp]
+        L.flx_screenset_destroy.restype = None
+        L.flx_screenset_hits.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp]
+        L.flx_screenset_hits_dev.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp]
+        L.flx_pipeline_set_screenset.argtypes = [vp, vp, dbl]
     if hasattr(L, "flx_adapters_create") or not os.environ.get("FLX_LIB_PATH"):  # (an experiment build of an older tree may lack them)
         _declare_adapters(L)
     _lib = L

@@ -184,8 +184,8 @@ class Context:
         """flx_pipeline_*: `chunks` is an iterable of lists of byte strings (Phred mode: qualities, k-mer mode: sequences).
         Every chunk is packed into the pipeline's pinned buffer and submitted; returns the same dict as score_reads for
         all reads in submission order.  grow: enlarge the slots (flx_pipeline_reserve) for a chunk that does not fit.
-        split_window_q: flx_pipeline_set_qsplit before the first chunk.  exclude (a Kmers filled with add_screen_fasta):
-        flx_pipeline_set_screen with exclude_percent; in Phred mode every chunk is then a PAIR (qualities, sequences) of lists, and
+        split_window_q: flx_pipeline_set_qsplit before the first chunk.  exclude (a Kmers filled with add_screen_fasta, or a
+        ScreenSet): flx_pipeline_set_screen / flx_pipeline_set_screenset with exclude_percent; in Phred mode every chunk is then a PAIR (qualities, sequences) of lists, and
         the result also has "hits" and "excluded".  adapters (an Adapters, Phred mode): flx_pipeline_set_adapters; every chunk is
         such a PAIR as well and the result also has "adapter_keys" (n x 2: head, tail)."""
         L = self.L
@@ -197,7 +197,8 @@ class Context:
                 self._check(L.flx_pipeline_set_qsplit(pipe, float(split_window_q)))
             two_planes = (exclude is not None or adapters is not None) and (kmers is None or kmers.empty())
             if exclude is not None:
-                self._check(L.flx_pipeline_set_screen(pipe, exclude.h, float(exclude_percent)))
+                set_screen = L.flx_pipeline_set_screenset if isinstance(exclude, ScreenSet) else L.flx_pipeline_set_screen
+                self._check(set_screen(pipe, exclude.h, float(exclude_percent)))
             if adapters is not None:
                 self._check(L.flx_pipeline_set_adapters(pipe, adapters.h))
             for strings in chunks:
@@ -415,6 +416,22 @@ class Context:
             ordp = order.ctypes.data
         self._check(self.L.flx_screen_hits(self.h, kmers.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data,
                                            ordp, n, hits.ctypes.data))
+        return hits[:n]
+
+    def screenset_hits(self, plane, offsets, lengths, sset, order=None):
+        """flx_screenset_hits: screen_hits against a ScreenSet — the number of every read's K-mers (K = sset.k) whose canonical key
+        is stored in it.  uint32 array in input order."""
+        n = len(lengths)
+        plane = np.ascontiguousarray(plane, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        hits = np.full(max(n, 1), 0xA5A5A5A5, dtype=np.uint32)
+        ordp = None
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.uint32)
+            ordp = order.ctypes.data
+        self._check(self.L.flx_screenset_hits(self.h, sset.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data,
+                                              ordp, n, hits.ctypes.data))
         return hits[:n]
 
     def screen_hits_dev(self, kmers, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_hits):
@@ -917,6 +934,48 @@ class Kmers:
         if self.h:
             if self.ctx.h:  # a set never outlives its context (Context.close() closes its sets first)
                 self.ctx.L.flx_kmerset_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ScreenSet:
+    """flx_screenset: the canonical K-mers (16 <= K <= 31) of a contaminant as a hash table on the device — what lets the screen
+    take a genome.  log2_capacity: the table's first size in slots (None: 2^16); it grows as sequences are added."""
+
+    def __init__(self, ctx, k, log2_capacity=None):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx._check(ctx.L.flx_screenset_create(ctx.h, int(k), 16 if log2_capacity is None else int(log2_capacity), C.byref(h)))
+        self.h = h
+        ctx._sets.append(weakref.ref(self))
+
+    def add_fasta(self, seqs):
+        """flx_screenset_add: the sequences as they are; a window with a byte outside ACGTacgt is in no set."""
+        Kmers._add(self, self.ctx.L.flx_screenset_add, seqs)
+
+    def finalize(self):
+        self.ctx._check(self.ctx.L.flx_screenset_finalize(self.h))
+
+    def __len__(self):
+        return int(self.ctx.L.flx_screenset_size(self.h))
+
+    @property
+    def k(self):
+        return int(self.ctx.L.flx_screenset_k(self.h))
+
+    @property
+    def capacity(self):
+        return int(self.ctx.L.flx_screenset_capacity(self.h))
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:  # (Context.close() closes its sets first)
+                self.ctx.L.flx_screenset_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -43,6 +43,7 @@ struct Args {
     bool adapter_errors_set = false; long long adapter_errors = 20;   // --adapter_errors E: edits a pattern may carry, percent of its length (-1: not an integer)
     bool adapter_window_set = false; long long adapter_window = 150;  // --adapter_window W: the bases at either end that are searched (-1: not an integer)
     bool split_adapters = false;  // --split_adapters: reads are also split at the adapters inside them (chimeras); needs --trim_adapters
+    bool exclude_k_set = false; long long exclude_k = 16;  // --exclude_k K: ... of their K-mers, 16 <= K <= 31; above 16 the set is a hash table of canonical keys (-1: not an integer)
     bool adapter_split_errors_set = false; long long adapter_split_errors = 10;  // --adapter_split_errors E2: edits a pattern may carry inside a read, percent (-1: not an integer)
     bool exclude_percent_set = false; double exclude_percent = 10.0; std::string exclude_percent_text = "10";  // --exclude_percent P: ... with at least P % of their 16-mers in it
 };
@@ -124,7 +125,7 @@ static long long whole_number(const std::string &value) {
 // terminal on STDOUT (TIOCGWINSZ; indent 1 / 2 / 3 / 4 for widths up to 60 / 80 / 120 / beyond).  When stdout is no terminal the
 // reference reads the width out of an untouched `struct winsize` — 0 in practice: the description comes out one word per line and,
 // the other widths being unsigned differences that wrap around, nothing else is wrapped at all.  Both cases are restated here.
-// (--gpus, --gzip, --bam, --report, --split_window_q, --exclude, --exclude_percent, --trim_adapters, --adapter_errors,
+// (--gpus, --gzip, --bam, --report, --split_window_q, --exclude, --exclude_percent, --exclude_k, --trim_adapters, --adapter_errors,
 // --adapter_window, --split_adapters and --adapter_split_errors, this binary's flags of its own, are documented in README.md: the
 // menu is the reference's.)
 static std::vector<std::string> help_wrap(const std::string &in, size_t width, size_t first = 0) {  // src/args.h:94-149
@@ -299,6 +300,7 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
                 a.exclude_percent_set = true;
             }
             else if (flag == "trim_adapters") { a.trim_adapters = need("trim_adapters"); a.trim_adapters_set = true; }
+            else if (flag == "exclude_k") { a.exclude_k = whole_number(need("exclude_k")); a.exclude_k_set = true; }
             else if (flag == "adapter_errors") { a.adapter_errors = whole_number(need("adapter_errors")); a.adapter_errors_set = true; }
             else if (flag == "adapter_window") { a.adapter_window = whole_number(need("adapter_window")); a.adapter_window_set = true; }
             else if (flag == "split_adapters") a.split_adapters = true;
@@ -372,6 +374,10 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
         std::cerr << "Error: the value for --adapter_split_errors must be an integer between 0 and 40\n"; return BAD; }
     if (a.split_adapters && !a.trim_adapters_set) { std::cerr << "Error: --split_adapters needs --trim_adapters\n"; return BAD; }
     if (a.adapter_split_errors_set && !a.split_adapters) { std::cerr << "Error: --adapter_split_errors needs --split_adapters\n"; return BAD; }
+    // --exclude_k: behind every check above
+    if (a.exclude_k_set && (a.exclude_k < 16 || a.exclude_k > 31)) {
+        std::cerr << "Error: the value for --exclude_k must be an integer between 16 and 31\n"; return BAD; }
+    if (a.exclude_k_set && !a.exclude_set) { std::cerr << "Error: --exclude_k needs --exclude\n"; return BAD; }
     return GOOD;
 }
 

@@ -75,9 +75,9 @@ static int exchange_totals(const Run &run, const Pass1 &p, const flx_scores &res
         for (size_t i = 0; i < p.lengths.size(); ++i)
             if (res.child_offsets[i + 1] - res.child_offsets[i] >= 2) ++split_reads;
     if (world > 1) {
-        std::vector<uint64_t> sums(2 * (size_t)world + 1 + (run.exclude ? 2 : 0) + (args.split_adapters ? 1 : 0), 0);
+        std::vector<uint64_t> sums(2 * (size_t)world + 1 + (run.excluding() ? 2 : 0) + (args.split_adapters ? 1 : 0), 0);
         if (args.split_adapters) sums.back() = split_reads;
-        if (run.exclude) { sums[2 * (size_t)world + 1] = excluded_reads; sums[2 * (size_t)world + 2] = excluded_bases; }
+        if (run.excluding()) { sums[2 * (size_t)world + 1] = excluded_reads; sums[2 * (size_t)world + 2] = excluded_bases; }
         sums[rank] = r2.reads.size();
         sums[world] = (uint64_t)after_total;
         sums[(size_t)world + 1 + rank] = r2.longest_name;  // (the --verbose table pads every name to the longest of ALL reads2, main.cpp:199-201)
@@ -85,14 +85,14 @@ static int exchange_totals(const Run &run, const Pass1 &p, const flx_scores &res
         r2.n_total = 0;
         for (int r = 0; r < world; ++r) { r2.n_total += sums[r]; r2.longest_name = std::max<size_t>(r2.longest_name, sums[(size_t)world + 1 + r]); }
         after_total = (long long)sums[world];
-        if (run.exclude) { excluded_reads = sums[2 * (size_t)world + 1]; excluded_bases = sums[2 * (size_t)world + 2]; }
+        if (run.excluding()) { excluded_reads = sums[2 * (size_t)world + 1]; excluded_bases = sums[2 * (size_t)world + 2]; }
         if (args.split_adapters) split_reads = sums.back();
         if (args.verbose && rank == 0) {
             if (!print_verbose_parts(run, "vblocks")) return 1;
             std::cerr << "\n";
         }
     }
-    if (run.exclude && rank == 0)
+    if (run.excluding() && rank == 0)
         std::cerr << "  excluded by reference: " << int_to_string((long long)excluded_reads) << " reads (" << int_to_string((long long)excluded_bases) << " bp)\n";
     if ((args.trim || args.split_set || args.split_window_q_set || args.trim_adapters_set) && rank == 0) {  // src/main.cpp:155-166 (--split_window_q: "after splitting")
         if (args.split_adapters) std::cerr << "  split at adapters: " << int_to_string((long long)split_reads) << " reads\n";
@@ -139,6 +139,7 @@ static int leave(Run &run, Scorer &scorer, const Report &report) {
         run.stage("pipeline teardown");
         if (run.kmers) flx_kmerset_destroy(run.kmers);
         if (run.exclude) flx_kmerset_destroy(run.exclude);
+        if (run.exclude_hash) flx_screenset_destroy(run.exclude_hash);
         if (run.adapters) flx_adapters_destroy(run.adapters);
         g_gpu_inflater.destroy();
         flx_ctx_destroy(run.ctx);

@@ -115,6 +115,7 @@ struct Scorer {
         // --exclude: the pipeline also screens every chunk against the contaminant's set; in Phred mode a chunk then carries the sequences
         // as a second plane behind the qualities
         if (run.exclude && flx_pipeline_set_screen(pipe, run.exclude, run.args.exclude_percent) != FLX_OK) return false;
+        if (run.exclude_hash && flx_pipeline_set_screenset(pipe, run.exclude_hash, run.args.exclude_percent) != FLX_OK) return false;
         // --trim_adapters: the pipeline cuts the adapters off the read ends and returns at most one child per read (with --split_adapters
         // the object also splits at the adapters inside a read: any number of children); the same second plane
         return !run.adapters || flx_pipeline_set_adapters(pipe, run.adapters) == FLX_OK;
@@ -152,7 +153,7 @@ struct Scorer {
         }
         const int32_t *len = lengths.data() + base;
         const bool phred = run.kmers_empty;
-        const bool second_plane = phred && (run.exclude != nullptr || run.adapters != nullptr);
+        const bool second_plane = phred && (run.excluding() || run.adapters != nullptr);
         for (uint64_t at = 0; at < cnt;) {
             // the next chunk: as many records as fit the slot (flx_plane_layout's rule: 16-byte slots, 128-byte starts for long reads)
             uint64_t end = at, bytes = 0;
@@ -202,7 +203,7 @@ struct Scorer {
         if (!create_pipe()) return report ? run.fail("pipeline") : 1;
         uint64_t n_scored = 0;
         if (flx_pipeline_finish(pipe, &res, &n_scored) != FLX_OK || n_scored != n) return report ? run.fail("scoring") : 1;
-        if (run.exclude && flx_pipeline_screen(pipe, &run.screen_hits, &run.screen_excluded) != FLX_OK) return report ? run.fail("scoring") : 1;
+        if (run.excluding() && flx_pipeline_screen(pipe, &run.screen_hits, &run.screen_excluded) != FLX_OK) return report ? run.fail("scoring") : 1;
         if (run.adapters && flx_pipeline_adapters(pipe, &run.adapter_keys) != FLX_OK) return report ? run.fail("scoring") : 1;
         return kGoOn;
     }

@@ -9,6 +9,8 @@
 // size of the file (round 4 held three copies of every sequence).  The progress lines are printed record by record with the
 // reference's rule, so stderr is the reference's byte for byte.  Pipes and empty files keep the in-memory reader (fastx.h: Input).
 #pragma once
+#include <sys/stat.h>
+
 #include "format.h"
 #include "run.h"
 
@@ -18,7 +20,9 @@ static void print_hash_progress(const std::string &filename, long long base_coun
 
 // hashes one reference file into sets[0 .. n_sets); returns the number of sequences (those shorter than 16 bases count too,
 // src/kmers.cpp:96-100); ok = false: the library refused a batch (flx_last_error says why)
-static int hash_reference(const std::string &filename, flx_kmerset *const *sets, int n_sets, bool short_reads, bool &ok, bool screen = false) {
+// hashed: the batches go into this set of --exclude_k instead (sets is then empty); *rc: what the library answered last
+static int hash_reference(const std::string &filename, flx_kmerset *const *sets, int n_sets, bool short_reads, bool &ok, bool screen = false,
+                          flx_screenset *hashed = nullptr, int *rc_out = nullptr) {
     int n = 0;
     long long bases = 0, last_progress = 0;
     size_t batch_bytes = (size_t)256 << 20;
@@ -29,6 +33,11 @@ static int hash_reference(const std::string &filename, flx_kmerset *const *sets,
     ok = true;
     auto flush = [&]() {
         if (offsets.empty() || !ok) return;
+        if (hashed) {
+            const int rc = flx_screenset_add(hashed, pack.data(), offsets.data(), lengths.data(), offsets.size());
+            if (rc_out) *rc_out = rc;
+            ok = rc == FLX_OK;
+        }
         for (int k = 0; k < n_sets && ok; ++k) {
             const int rc = screen        ? flx_screen_set_add(sets[k], pack.data(), offsets.data(), lengths.data(), offsets.size())
                            : short_reads ? flx_kmerset_add_short_reads(sets[k], pack.data(), offsets.data(), lengths.data(), offsets.size())
@@ -118,10 +127,46 @@ static int build_reference_set(Run &run) {
 // reader of -a (gzip included, in batches); flx_screen_set_add cuts the sequences at every byte outside ACGTacgt.  16-mers cannot
 // screen a large genome: an unrelated read keeps N / 2^32 of its windows, and once that background reaches half the threshold —
 // N * 200 >= P * 2^32 — the run is refused.
+// --exclude_k K, 17 <= K <= 31: the contaminant's canonical K-mers in a hash table on the device (csrc/screen_hash.h), which is what
+// lets a genome be screened.  The table starts at twice the file's bytes, so that a plain FASTA is never rehashed (a gzip file grows
+// as it is read).  The background of an unrelated read is at most 2 M / 4^K of its windows for M canonical keys; the rule above
+// becomes M * 400 >= P * 4^K.
+static int build_exclude_hash(Run &run) {
+    const Args &args = run.args;
+    const int k = (int)args.exclude_k;
+    struct stat st;
+    uint64_t file_bytes = stat(args.exclude.c_str(), &st) == 0 && st.st_size > 0 ? (uint64_t)st.st_size : 0;
+    int hint = 16;
+    while (hint < 40 && (1ull << hint) < 2 * file_bytes) ++hint;
+    const char *no_memory = "Error: not enough device memory for the --exclude set\n";
+    int rc = flx_screenset_create(run.ctx, k, hint, &run.exclude_hash);
+    if (rc == FLX_ERR_NOMEM) { std::cerr << no_memory; return 1; }
+    if (rc != FLX_OK) return run.fail("exclude set");
+    run.exclude_k = k;
+    std::cerr << "Hashing " << k << "-mers to exclude\n";
+    std::cerr << "  " << args.exclude << "\n";
+    bool ok = true;
+    rc = FLX_OK;
+    const int count = hash_reference(args.exclude, nullptr, 0, false, ok, true, run.exclude_hash, &rc);
+    if (!ok && rc == FLX_ERR_NOMEM) { std::cerr << no_memory; return 1; }
+    if (!ok) return run.fail("exclude");
+    if (flx_screenset_finalize(run.exclude_hash) != FLX_OK) return run.fail("exclude set");
+    const uint64_t n = flx_screenset_size(run.exclude_hash);
+    std::cerr << "  " << int_to_string(count) << " " << (count == 1 ? "sequence" : "sequences") << ", " << int_to_string((long long)n) << " canonical " << k
+              << "-mers\n\n";
+    if ((long double)n * 400.0L >= (long double)args.exclude_percent * (long double)(1ull << (2 * k))) {
+        std::cerr << "Error: the reference for --exclude holds too many " << k << "-mers (" << n << ") for --exclude_percent " << args.exclude_percent_text << "\n";
+        return 1;
+    }
+    if (n == 0) { std::cerr << "Error: the reference for --exclude holds no " << k << "-mer of ACGT\n"; return 1; }
+    return kGoOn;
+}
+
 static int build_exclude_set(Run &run) {
     const Args &args = run.args;
     if (!args.exclude_set) return kGoOn;
     if (!run.ready()) return 1;
+    if (args.exclude_k > 16) return build_exclude_hash(run);
     if (flx_kmerset_create(run.ctx, &run.exclude) != FLX_OK) return run.fail("exclude set");
     std::cerr << "Hashing 16-mers to exclude\n";
     std::cerr << "  " << args.exclude << "\n";

@@ -47,7 +47,7 @@ static int summarise_for_report(const Run &run, const Pass1 &p, const flx_scores
         flx_summary(run.ctx, r2.len.size(), r2.len.data(), r2.mean.data(), r2.window.data(), r2.pass.data(), global, &kept) != FLX_OK)
         return run.fail("report");
     // --exclude: a fourth summary, the input reads the screen took (a collective like the other three)
-    if (run.exclude && flx_summary(run.ctx, p.lengths.size(), p.lengths.data(), res.mean_q, res.window_q, run.screen_excluded, global, &excluded) != FLX_OK)
+    if (run.excluding() && flx_summary(run.ctx, p.lengths.size(), p.lengths.data(), res.mean_q, res.window_q, run.screen_excluded, global, &excluded) != FLX_OK)
         return run.fail("report");
     if (run.rank > 0) return kGoOn;
     double edges[51];
@@ -60,7 +60,7 @@ static int summarise_for_report(const Run &run, const Pass1 &p, const flx_scores
         s += (k ? ", " : "") + std::string(buf);
     }
     s += "],\n \"input\": " + report_summary(input) + ",\n \"scored\": " + report_summary(scored) + ",\n \"kept\": " + report_summary(kept) +
-         (run.exclude ? ",\n \"excluded\": " + report_summary(excluded) : std::string()) + "}\n";
+         (run.excluding() ? ",\n \"excluded\": " + report_summary(excluded) : std::string()) + "}\n";
     return kGoOn;
 }
 

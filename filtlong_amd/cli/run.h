@@ -41,6 +41,9 @@ struct Run {
     flx_kmerset *kmers = nullptr;
     bool kmers_empty = true;
     flx_kmerset *exclude = nullptr;            // --exclude: the contaminant's 16-mers (reference.h: build_exclude_set)
+    flx_screenset *exclude_hash = nullptr;     // --exclude_k 17..31: the contaminant's canonical K-mers instead (one of the two)
+    int exclude_k = 16;                        // the K of whichever set was built
+    bool excluding() const { return exclude != nullptr || exclude_hash != nullptr; }
     const uint32_t *screen_hits = nullptr;     // ... and, once the scores are in, every read's hits and whether it was excluded
     const uint8_t *screen_excluded = nullptr;  // (owned by the pipeline; this rank's reads in submission order)
     flx_adapters *adapters = nullptr;          // --trim_adapters: the patterns (reference.h: build_adapters) ...

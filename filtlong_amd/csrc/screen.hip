@@ -25,7 +25,7 @@
 #include "flx_internal.h"
 #include "kmerset.h"
 #include "rank_internal.h"
-#include "screen.h"
+#include "screen_hash.h"
 
 namespace {
 
@@ -36,13 +36,13 @@ constexpr int kScreenThreads = 1024;  // 16 waves: with the 128 KiB table one wo
 constexpr int kPre10Words = 1 << 15;  // 4^10 bits
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // (the compiler's own vector: sixteen bytes that stay in registers)
 
-__global__ void __launch_bounds__(256) k_screen_segments(const int32_t *lengths, const uint32_t *order, uint64_t n_reads, uint32_t *counts) {
+__global__ void __launch_bounds__(256) k_screen_segments(const int32_t *lengths, const uint32_t *order, uint64_t n_reads, int k, uint32_t *counts) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r > n_reads) return;
     uint32_t c = 0;
     if (r < n_reads) {
         const uint32_t read = order ? order[r] : (uint32_t)r;
-        c = (screen::windows_of(lengths[read]) + (uint32_t)kScreenSpan - 1u) / (uint32_t)kScreenSpan;
+        c = (screenk::windows_of(lengths[read], k) + (uint32_t)kScreenSpan - 1u) / (uint32_t)kScreenSpan;
     }
     counts[r] = c;  // counts[n_reads] = 0: its scanned value is the number of spans
 }
@@ -170,11 +170,11 @@ __global__ void __launch_bounds__(kScreenThreads) k_screen_hits(const uint8_t *_
     }
 }
 
-__global__ void __launch_bounds__(256) k_screen_apply(uint64_t n_reads, const int32_t *lengths, const uint32_t *hits, uint64_t t, uint8_t *passed,
-                                                      const uint64_t *child_offsets, uint8_t *child_passed, uint8_t *excluded) {
+__global__ void __launch_bounds__(256) k_screen_apply(uint64_t n_reads, const int32_t *lengths, const uint32_t *hits, uint64_t t, int k,
+                                                      uint8_t *passed, const uint64_t *child_offsets, uint8_t *child_passed, uint8_t *excluded) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_reads) return;
-    const bool out = screen::excluded(hits[i], screen::windows_of(lengths[i]), t);
+    const bool out = screen::excluded(hits[i], screenk::windows_of(lengths[i], k), t);
     excluded[i] = out ? 1 : 0;
     if (!out) return;
     passed[i] = 0;
@@ -184,13 +184,22 @@ __global__ void __launch_bounds__(256) k_screen_apply(uint64_t n_reads, const in
 
 }  // namespace
 
+// the spans of every read in processing order for windows of k bases, counts[0 .. n_reads] (the last is 0), on the context's stream:
+// the head of flx_screen_hits_dev and of screen_hash.hip's calls
+int flx_screen_segments_dev(flx_ctx *ctx, const int32_t *d_lengths, const uint32_t *d_order, uint64_t n_reads, int k, uint32_t *d_counts) {
+    hipLaunchKernelGGL(k_screen_segments, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, ctx->stream, d_lengths, d_order, n_reads, k,
+                       d_counts);
+    FLX_HIP(ctx, hipGetLastError());
+    return FLX_OK;
+}
+
 // An excluded read is a read that fails a hard cut-off: its pass flag and those of its children are cleared on the device, on the
 // context's stream, before anything is copied back (pipeline.hip).
-int flx_screen_apply_dev(flx_ctx *ctx, uint64_t n_reads, const int32_t *d_lengths, const uint32_t *d_hits, uint64_t t, uint8_t *d_passed,
-                         const uint64_t *d_child_offsets, uint8_t *d_child_passed, uint8_t *d_excluded) {
+int flx_screen_apply_dev(flx_ctx *ctx, uint64_t n_reads, const int32_t *d_lengths, const uint32_t *d_hits, uint64_t t, int k,
+                         uint8_t *d_passed, const uint64_t *d_child_offsets, uint8_t *d_child_passed, uint8_t *d_excluded) {
     if (n_reads == 0) return FLX_OK;
     flx_time_begin(ctx, "flx_screen_apply");
-    hipLaunchKernelGGL(k_screen_apply, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, ctx->stream, n_reads, d_lengths, d_hits, t,
+    hipLaunchKernelGGL(k_screen_apply, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, ctx->stream, n_reads, d_lengths, d_hits, t, k,
                        d_passed, d_child_offsets, d_child_passed, d_excluded);
     flx_time_end(ctx);
     FLX_HIP(ctx, hipGetLastError());
@@ -249,8 +258,7 @@ extern "C" int flx_screen_hits_dev(flx_ctx *ctx, const flx_kmerset *set, const v
 
     flx_time_scope timed(ctx, "flx_screen");
     FLX_HIP(ctx, hipMemsetAsync(d_hits, 0, n_reads * 4, st));
-    hipLaunchKernelGGL(k_screen_segments, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, st, (const int32_t *)d_lengths,
-                       (const uint32_t *)d_order, n_reads, counts);
+    FLX_CHECK(flx_screen_segments_dev(ctx, (const int32_t *)d_lengths, (const uint32_t *)d_order, n_reads, 16, counts));
     FLX_CHECK(flx_exclusive_scan_u32(ctx, n_reads + 1, counts, seg_start, ws, scan_ws));
 #define FLX_SCREEN_LAUNCH(T, blocks)                                                                                                        \
     hipLaunchKernelGGL(k_screen_hits<T>, dim3(blocks), dim3(kScreenThreads), 0, st, (const uint8_t *)d_plane, (const uint64_t *)d_offsets, \

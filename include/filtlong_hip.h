@@ -229,6 +229,36 @@ int flx_screen_hits_dev(flx_ctx *ctx, const flx_kmerset *set, const void *d_plan
 const char *flx_last_screen_filter(const flx_ctx *ctx);
 
 /* ------------------------------------------------------------------------------------------
+ * the screen with K-mers of 16 <= K <= 31 bases (added under version 4): what lets --exclude screen a genome.  The definition above
+ * with 16 replaced by K: windows = max(0, L - K + 1), a window counts if its K bytes are all in ACGTacgt and it is in X_K, every K-mer
+ * of either strand of the reference that consists of ACGTacgt only (no window spans two sequences); t and the decision are unchanged.
+ * A window's forward code has A 0, C 1, G 2, T 3, the first base on top, in 2 K bits; the set stores CANONICAL keys, the smaller of a
+ * window's code and its reverse complement's, in an open-addressing table of 64-bit slots in device memory: capacity a power of two
+ * and at least twice the stored keys after every add, linear probing.  Neither the hash nor the capacity can change a result.
+ *   flx_screenset_create    k outside 16..31 or a hint outside 1..40: FLX_ERR_INVALID.  The table starts at 2^log2_capacity_hint slots;
+ *                           it grows (every key is rehashed) before a batch whose windows could take the load above 1/2, so a caller
+ *                           who knows the reference's size passes log2 of twice its bases and the table is never rehashed.
+ *   flx_screenset_add       host arrays, any offsets, sequences back to back; lengths up to 2^31 - 1 (FLX_ERR_INVALID beyond); any
+ *                           number of calls.  Nothing is cut on the host: a window with a byte outside ACGTacgt is not valid.
+ *   flx_screenset_finalize  afterwards every call but the getters and flx_screenset_destroy is FLX_ERR_STATE
+ *   flx_screenset_size      the stored canonical keys;  flx_screenset_k, flx_screenset_capacity (slots of 8 bytes)
+ *   flx_screenset_hits(_dev) arguments, checks and timing name of flx_screen_hits(_dev); flx_last_screen_filter then answers "hash"
+ * A device allocation that fails is FLX_ERR_NOMEM and leaves the set as it was before the call.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct flx_screenset flx_screenset;
+int flx_screenset_create(flx_ctx *ctx, int k, int log2_capacity_hint, flx_screenset **out);
+int flx_screenset_add(flx_screenset *set, const uint8_t *bases, const uint64_t *offsets, const int64_t *lengths, uint64_t n_seqs);
+int flx_screenset_finalize(flx_screenset *set);
+uint64_t flx_screenset_size(const flx_screenset *set);
+int flx_screenset_k(const flx_screenset *set);
+uint64_t flx_screenset_capacity(const flx_screenset *set);
+void flx_screenset_destroy(flx_screenset *set);
+int flx_screenset_hits(flx_ctx *ctx, const flx_screenset *set, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets,
+                       const int32_t *lengths, const uint32_t *order, uint64_t n_reads, uint32_t *hits);
+int flx_screenset_hits_dev(flx_ctx *ctx, const flx_screenset *set, const void *d_plane, uint64_t plane_bytes, const void *d_offsets,
+                           const void *d_lengths, const void *d_order, uint64_t n_reads, uint32_t *d_hits);
+
+/* ------------------------------------------------------------------------------------------
  * adapter trimming (added under version 4; the reference has no counterpart: its users run an adapter trimmer over the whole file
  * in front of it): known adapters are cut off the two ends of every read.  Defined on integers, so every decomposition gives the
  * same answer:
@@ -398,6 +428,10 @@ int flx_pipeline_set_qsplit(flx_pipeline *p, double q);
  * after flx_pipeline_finish. */
 int flx_pipeline_set_screen(flx_pipeline *p, const flx_kmerset *exclude_set, double percent);
 int flx_pipeline_screen(flx_pipeline *p, const uint32_t **hits, const uint8_t **excluded);
+/* --exclude with --exclude_k for a pipeline: flx_pipeline_set_screen with a flx_screenset — the same state rules, the same two planes
+ * in Phred mode, windows = max(0, L - K + 1) in the decision, and flx_pipeline_screen afterwards.  A pipeline takes one of the two
+ * calls: the other one is then FLX_ERR_STATE. */
+int flx_pipeline_set_screenset(flx_pipeline *p, const flx_screenset *exclude_set, double percent);
 /* --trim_adapters for a Phred-mode pipeline (added under version 4): every chunk then goes through flx_score_batch_adapters_dev.
  * The chunk carries the second plane exactly as flx_pipeline_set_screen arranged it (qualities, then the sequences at the same
  * offsets; with both a screen and adapters there is still ONE sequence plane).  The screen keeps looking at the whole parent; an
