@@ -402,37 +402,29 @@ class Context:
         return rep
 
     # ---- the contaminant screen ------------------------------------------------------------------
-    def screen_hits(self, plane, offsets, lengths, kmers, order=None):
-        """flx_screen_hits: for every read of the SEQUENCE plane the number of its 16-mers that are members of `kmers` (a set
-        filled with Kmers.add_screen_fasta).  uint32 array in input order."""
+    def _per_read(self, fn, handle, plane, offsets, lengths, order, per_read):
+        """The host-array form of a call that answers `per_read` uint32 per read of the SEQUENCE plane, in input order."""
         n = len(lengths)
         plane = np.ascontiguousarray(plane, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         lengths = np.ascontiguousarray(lengths, dtype=np.int32)
-        hits = np.full(max(n, 1), 0xA5A5A5A5, dtype=np.uint32)
+        out = np.full(per_read * max(n, 1), 0xA5A5A5A5, dtype=np.uint32)
         ordp = None
         if order is not None:
             order = np.ascontiguousarray(order, dtype=np.uint32)
             ordp = order.ctypes.data
-        self._check(self.L.flx_screen_hits(self.h, kmers.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data,
-                                           ordp, n, hits.ctypes.data))
-        return hits[:n]
+        self._check(fn(self.h, handle, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data, ordp, n, out.ctypes.data))
+        return out[:per_read * n]
+
+    def screen_hits(self, plane, offsets, lengths, kmers, order=None):
+        """flx_screen_hits: for every read of the SEQUENCE plane the number of its 16-mers that are members of `kmers` (a set
+        filled with Kmers.add_screen_fasta).  uint32 array in input order."""
+        return self._per_read(self.L.flx_screen_hits, kmers.h, plane, offsets, lengths, order, 1)
 
     def screenset_hits(self, plane, offsets, lengths, sset, order=None):
         """flx_screenset_hits: screen_hits against a ScreenSet — the number of every read's K-mers (K = sset.k) whose canonical key
         is stored in it.  uint32 array in input order."""
-        n = len(lengths)
-        plane = np.ascontiguousarray(plane, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
-        hits = np.full(max(n, 1), 0xA5A5A5A5, dtype=np.uint32)
-        ordp = None
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.uint32)
-            ordp = order.ctypes.data
-        self._check(self.L.flx_screenset_hits(self.h, sset.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data,
-                                              ordp, n, hits.ctypes.data))
-        return hits[:n]
+        return self._per_read(self.L.flx_screenset_hits, sset.h, plane, offsets, lengths, order, 1)
 
     def screen_hits_dev(self, kmers, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_hits):
         self._check(self.L.flx_screen_hits_dev(self.h, kmers.h, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_hits))
@@ -441,18 +433,7 @@ class Context:
     def adapter_cuts(self, plane, offsets, lengths, adapters, order=None):
         """flx_adapter_cuts: for every read of the SEQUENCE plane its two keys, (jbest << 8) | pattern of the adapter occurrence that
         reaches furthest into the read at the head and at the tail, 0 without a hit.  uint32 array (n, 2) in input order."""
-        n = len(lengths)
-        plane = np.ascontiguousarray(plane, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
-        keys = np.full(2 * max(n, 1), 0xA5A5A5A5, dtype=np.uint32)
-        ordp = None
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.uint32)
-            ordp = order.ctypes.data
-        self._check(self.L.flx_adapter_cuts(self.h, adapters.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data,
-                                            ordp, n, keys.ctypes.data))
-        return keys[:2 * n].reshape(-1, 2)
+        return self._per_read(self.L.flx_adapter_cuts, adapters.h, plane, offsets, lengths, order, 2).reshape(-1, 2)
 
     def adapter_cuts_dev(self, adapters, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_keys):
         self._check(self.L.flx_adapter_cuts_dev(self.h, adapters.h, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_keys))
@@ -879,6 +860,18 @@ class Adapters:
             pass
 
 
+def _add_seqs(ctx, fn, handle, seqs):
+    """The sequences, packed back to back, into the set `handle` through one of the library's add calls."""
+    seqs = [bytes(s) for s in seqs]
+    n = len(seqs)
+    lengths = np.array([len(s) for s in seqs], dtype=np.int64)
+    offsets = np.zeros(max(n, 1), dtype=np.uint64)
+    if n:
+        offsets[1:n] = np.cumsum(lengths[:-1])
+    bases = np.frombuffer(b"".join(seqs) or b"\0", dtype=np.uint8)
+    ctx._check(fn(handle, bases.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, n))
+
+
 class Kmers:
     """Reference 16-mer set on the device — mirrors the reference's Kmers (src/kmers.h:28-56)."""
 
@@ -890,29 +883,19 @@ class Kmers:
         self._final = False
         ctx._sets.append(weakref.ref(self))
 
-    def _add(self, fn, seqs):
-        seqs = [bytes(s) for s in seqs]
-        n = len(seqs)
-        lengths = np.array([len(s) for s in seqs], dtype=np.int64)
-        offsets = np.zeros(max(n, 1), dtype=np.uint64)
-        if n:
-            offsets[1:n] = np.cumsum(lengths[:-1])
-        bases = np.frombuffer(b"".join(seqs) or b"\0", dtype=np.uint8)
-        self.ctx._check(fn(self.h, bases.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, n))
-
     def add_assembly_fasta(self, seqs):
         """Kmers::add_assembly_fasta (src/kmers.cpp:61-72) on already-parsed contig sequences."""
-        self._add(self.ctx.L.flx_kmerset_add_assembly, seqs)
+        _add_seqs(self.ctx, self.ctx.L.flx_kmerset_add_assembly, self.h, seqs)
 
     def add_screen_fasta(self, seqs):
         """flx_screen_set_add: the sequences of a contaminant for the screen — cut at every byte outside ACGTacgt, pieces of at
         least 16 bases only, so that an N run puts no poly-A into the set."""
-        self._add(self.ctx.L.flx_screen_set_add, seqs)
+        _add_seqs(self.ctx, self.ctx.L.flx_screen_set_add, self.h, seqs)
 
     def add_read_fastqs(self, files_of_seqs):
         """Kmers::add_read_fastqs (src/kmers.cpp:50-58): one list of read sequences per file, -1 then -2."""
         for seqs in files_of_seqs:
-            self._add(self.ctx.L.flx_kmerset_add_short_reads, seqs)
+            _add_seqs(self.ctx, self.ctx.L.flx_kmerset_add_short_reads, self.h, seqs)
 
     def finalize(self):
         self.ctx._check(self.ctx.L.flx_kmerset_finalize(self.h))
@@ -956,7 +939,7 @@ class ScreenSet:
 
     def add_fasta(self, seqs):
         """flx_screenset_add: the sequences as they are; a window with a byte outside ACGTacgt is in no set."""
-        Kmers._add(self, self.ctx.L.flx_screenset_add, seqs)
+        _add_seqs(self.ctx, self.ctx.L.flx_screenset_add, self.h, seqs)
 
     def finalize(self):
         self.ctx._check(self.ctx.L.flx_screenset_finalize(self.h))

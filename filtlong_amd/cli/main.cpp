@@ -138,8 +138,7 @@ static int leave(Run &run, Scorer &scorer, const Report &report) {
         scorer.destroy();
         run.stage("pipeline teardown");
         if (run.kmers) flx_kmerset_destroy(run.kmers);
-        if (run.exclude) flx_kmerset_destroy(run.exclude);
-        if (run.exclude_hash) flx_screenset_destroy(run.exclude_hash);
+        run.destroy_exclude();
         if (run.adapters) flx_adapters_destroy(run.adapters);
         g_gpu_inflater.destroy();
         flx_ctx_destroy(run.ctx);

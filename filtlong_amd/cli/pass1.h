@@ -114,8 +114,7 @@ struct Scorer {
         if (run.args.split_window_q_set && flx_pipeline_set_qsplit(pipe, run.args.split_window_q) != FLX_OK) return false;
         // --exclude: the pipeline also screens every chunk against the contaminant's set; in Phred mode a chunk then carries the sequences
         // as a second plane behind the qualities
-        if (run.exclude && flx_pipeline_set_screen(pipe, run.exclude, run.args.exclude_percent) != FLX_OK) return false;
-        if (run.exclude_hash && flx_pipeline_set_screenset(pipe, run.exclude_hash, run.args.exclude_percent) != FLX_OK) return false;
+        if (run.excluding() && run.set_pipeline_screen(pipe) != FLX_OK) return false;
         // --trim_adapters: the pipeline cuts the adapters off the read ends and returns at most one child per read (with --split_adapters
         // the object also splits at the adapters inside a read: any number of children); the same second plane
         return !run.adapters || flx_pipeline_set_adapters(pipe, run.adapters) == FLX_OK;

@@ -18,11 +18,37 @@ static void print_hash_progress(const std::string &filename, long long base_coun
     std::cerr << "\r  " << filename << " (" << int_to_string(base_count) << " bp)";
 }
 
-// hashes one reference file into sets[0 .. n_sets); returns the number of sequences (those shorter than 16 bases count too,
-// src/kmers.cpp:96-100); ok = false: the library refused a batch (flx_last_error says why)
-// hashed: the batches go into this set of --exclude_k instead (sets is then empty); *rc: what the library answered last
-static int hash_reference(const std::string &filename, flx_kmerset *const *sets, int n_sets, bool short_reads, bool &ok, bool screen = false,
-                          flx_screenset *hashed = nullptr, int *rc_out = nullptr) {
+// every record of a reference file, in file order: a regular file — plain or gzip — block by block, a pipe or an empty file through
+// the in-memory reader (FLX_CLI_NO_STREAM: always that one).  Any error ends the loop silently, like `while ((l = kseq_read(seq)) >= 0)`;
+// so does keep_going() answering false.
+template <class Take, class KeepGoing>
+static void for_each_record(const std::string &filename, Take take, KeepGoing keep_going) {
+    BlockReader blocks;
+    if (!getenv("FLX_CLI_NO_STREAM") && blocks.open(filename, false)) {
+        Parsed batch;
+        while (keep_going() && blocks.next(batch)) {
+            for (const Record &r : batch.recs) take(r);
+            if (batch.status <= -2) break;
+        }
+    } else {
+        Input data;
+        std::deque<std::string> arena;
+        if (data.open(filename)) {
+            Parser p(data, arena);
+            Record r;
+            while (keep_going() && p.next(r) >= 0) {
+                take(r);
+                arena.clear();  // (the record's multi-line fields have been copied)
+            }
+        }
+    }
+}
+
+// hashes one reference file: its sequences of at least 16 bases go to add(bases, offsets, lengths, n) in batches; returns the number
+// of sequences (those shorter than 16 bases count too, src/kmers.cpp:96-100).  rc: what add answered last — not FLX_OK: the library
+// refused a batch (flx_last_error says why) and the rest of the file was not read
+template <class Add>
+static int hash_reference(const std::string &filename, Add add, int &rc) {
     int n = 0;
     long long bases = 0, last_progress = 0;
     size_t batch_bytes = (size_t)256 << 20;
@@ -30,20 +56,10 @@ static int hash_reference(const std::string &filename, flx_kmerset *const *sets,
     std::vector<uint8_t> pack;
     std::vector<uint64_t> offsets;
     std::vector<int64_t> lengths;
-    ok = true;
+    rc = FLX_OK;
     auto flush = [&]() {
-        if (offsets.empty() || !ok) return;
-        if (hashed) {
-            const int rc = flx_screenset_add(hashed, pack.data(), offsets.data(), lengths.data(), offsets.size());
-            if (rc_out) *rc_out = rc;
-            ok = rc == FLX_OK;
-        }
-        for (int k = 0; k < n_sets && ok; ++k) {
-            const int rc = screen        ? flx_screen_set_add(sets[k], pack.data(), offsets.data(), lengths.data(), offsets.size())
-                           : short_reads ? flx_kmerset_add_short_reads(sets[k], pack.data(), offsets.data(), lengths.data(), offsets.size())
-                                         : flx_kmerset_add_assembly(sets[k], pack.data(), offsets.data(), lengths.data(), offsets.size());
-            ok = rc == FLX_OK;
-        }
+        if (offsets.empty() || rc != FLX_OK) return;
+        rc = add(pack.data(), offsets.data(), lengths.data(), (uint64_t)offsets.size());
         pack.clear();
         offsets.clear();
         lengths.clear();
@@ -61,25 +77,7 @@ static int hash_reference(const std::string &filename, flx_kmerset *const *sets,
             print_hash_progress(filename, bases);
         }
     };
-    BlockReader blocks;
-    if (!getenv("FLX_CLI_NO_STREAM") && blocks.open(filename, false)) {
-        Parsed batch;
-        while (ok && blocks.next(batch)) {  // any error ends the loop silently, like `while ((l = kseq_read(seq)) >= 0)`
-            for (const Record &r : batch.recs) take(r);
-            if (batch.status <= -2) break;
-        }
-    } else {
-        Input data;
-        std::deque<std::string> arena;
-        if (data.open(filename)) {
-            Parser p(data, arena);
-            Record r;
-            while (ok && p.next(r) >= 0) {
-                take(r);
-                arena.clear();  // (the record's multi-line fields have been copied)
-            }
-        }
-    }
+    for_each_record(filename, take, [&] { return rc == FLX_OK; });
     flush();
     print_hash_progress(filename, bases);
     std::cerr << "\n";
@@ -98,10 +96,12 @@ static int build_reference_set(Run &run) {
         // takes a second set, which is fed the same batches and dropped once it has been counted
         flx_kmerset *alone = nullptr;
         if (!args.short_reads.empty() && flx_kmerset_create(run.ctx, &alone) != FLX_OK) return run.fail("k-mer set");
-        flx_kmerset *both[2] = {run.kmers, alone};
-        bool ok = true;
-        const int count = hash_reference(args.assembly, both, alone ? 2 : 1, false, ok);
-        if (!ok) return run.fail("assembly");
+        int rc;
+        const int count = hash_reference(args.assembly, [&](const uint8_t *bases, const uint64_t *offsets, const int64_t *lengths, uint64_t n) {
+            const int first = flx_kmerset_add_assembly(run.kmers, bases, offsets, lengths, n);
+            return first != FLX_OK || !alone ? first : flx_kmerset_add_assembly(alone, bases, offsets, lengths, n);
+        }, rc);
+        if (rc != FLX_OK) return run.fail("assembly");
         flx_kmerset *counted = alone ? alone : run.kmers;
         if (flx_kmerset_finalize(counted) != FLX_OK) return run.fail(alone ? "assembly" : "k-mer set");
         std::cerr << "  " << int_to_string(count) << " " << (count == 1 ? "contig" : "contigs") << ", "
@@ -112,9 +112,11 @@ static int build_reference_set(Run &run) {
         std::cerr << "Hashing 16-mers from short reads\n";
         int count = 0;
         for (auto &f : args.short_reads) {
-            bool ok = true;
-            count += hash_reference(f, &run.kmers, 1, true, ok);
-            if (!ok) return run.fail("short reads");
+            int rc;
+            count += hash_reference(f, [&](const uint8_t *bases, const uint64_t *offsets, const int64_t *lengths, uint64_t n) {
+                return flx_kmerset_add_short_reads(run.kmers, bases, offsets, lengths, n);
+            }, rc);
+            if (rc != FLX_OK) return run.fail("short reads");
         }
         if (flx_kmerset_finalize(run.kmers) != FLX_OK) return run.fail("k-mer set");
         std::cerr << "  " << int_to_string(count) << " reads, " << int_to_string((long long)flx_kmerset_size(run.kmers)) << " 16-mers\n\n";
@@ -131,56 +133,45 @@ static int build_reference_set(Run &run) {
 // lets a genome be screened.  The table starts at twice the file's bytes, so that a plain FASTA is never rehashed (a gzip file grows
 // as it is read).  The background of an unrelated read is at most 2 M / 4^K of its windows for M canonical keys; the rule above
 // becomes M * 400 >= P * 4^K.
-static int build_exclude_hash(Run &run) {
-    const Args &args = run.args;
-    const int k = (int)args.exclude_k;
-    struct stat st;
-    uint64_t file_bytes = stat(args.exclude.c_str(), &st) == 0 && st.st_size > 0 ? (uint64_t)st.st_size : 0;
-    int hint = 16;
-    while (hint < 40 && (1ull << hint) < 2 * file_bytes) ++hint;
-    const char *no_memory = "Error: not enough device memory for the --exclude set\n";
-    int rc = flx_screenset_create(run.ctx, k, hint, &run.exclude_hash);
-    if (rc == FLX_ERR_NOMEM) { std::cerr << no_memory; return 1; }
-    if (rc != FLX_OK) return run.fail("exclude set");
-    run.exclude_k = k;
-    std::cerr << "Hashing " << k << "-mers to exclude\n";
-    std::cerr << "  " << args.exclude << "\n";
-    bool ok = true;
-    rc = FLX_OK;
-    const int count = hash_reference(args.exclude, nullptr, 0, false, ok, true, run.exclude_hash, &rc);
-    if (!ok && rc == FLX_ERR_NOMEM) { std::cerr << no_memory; return 1; }
-    if (!ok) return run.fail("exclude");
-    if (flx_screenset_finalize(run.exclude_hash) != FLX_OK) return run.fail("exclude set");
-    const uint64_t n = flx_screenset_size(run.exclude_hash);
-    std::cerr << "  " << int_to_string(count) << " " << (count == 1 ? "sequence" : "sequences") << ", " << int_to_string((long long)n) << " canonical " << k
-              << "-mers\n\n";
-    if ((long double)n * 400.0L >= (long double)args.exclude_percent * (long double)(1ull << (2 * k))) {
-        std::cerr << "Error: the reference for --exclude holds too many " << k << "-mers (" << n << ") for --exclude_percent " << args.exclude_percent_text << "\n";
-        return 1;
-    }
-    if (n == 0) { std::cerr << "Error: the reference for --exclude holds no " << k << "-mer of ACGT\n"; return 1; }
-    return kGoOn;
-}
-
 static int build_exclude_set(Run &run) {
     const Args &args = run.args;
     if (!args.exclude_set) return kGoOn;
     if (!run.ready()) return 1;
-    if (args.exclude_k > 16) return build_exclude_hash(run);
-    if (flx_kmerset_create(run.ctx, &run.exclude) != FLX_OK) return run.fail("exclude set");
-    std::cerr << "Hashing 16-mers to exclude\n";
+    // what the two kinds of set differ in: K, the calls, the noun of the count line, the background rule (refused when
+    // n * factor >= P * space) and, for the hashed kind, a message of its own for FLX_ERR_NOMEM from create or add
+    const bool hashed = args.exclude_k > 16;
+    const int k = hashed ? (int)args.exclude_k : 16;
+    const long double factor = hashed ? 400.0L : 200.0L, space = hashed ? (long double)(1ull << (2 * k)) : 4294967296.0L;
+    const char *no_memory = "Error: not enough device memory for the --exclude set\n";
+    int rc;
+    if (hashed) {
+        struct stat st;
+        const uint64_t file_bytes = stat(args.exclude.c_str(), &st) == 0 && st.st_size > 0 ? (uint64_t)st.st_size : 0;
+        int hint = 16;
+        while (hint < 40 && (1ull << hint) < 2 * file_bytes) ++hint;
+        rc = flx_screenset_create(run.ctx, k, hint, &run.exclude_hash);
+    } else {
+        rc = flx_kmerset_create(run.ctx, &run.exclude);
+    }
+    if (hashed && rc == FLX_ERR_NOMEM) { std::cerr << no_memory; return 1; }
+    if (rc != FLX_OK) return run.fail("exclude set");
+    run.exclude_k = k;
+    std::cerr << "Hashing " << k << "-mers to exclude\n";
     std::cerr << "  " << args.exclude << "\n";
-    bool ok = true;
-    const int count = hash_reference(args.exclude, &run.exclude, 1, false, ok, true);
-    if (!ok) return run.fail("exclude");
-    if (flx_kmerset_finalize(run.exclude) != FLX_OK) return run.fail("exclude set");
-    const uint64_t n = flx_kmerset_size(run.exclude);
-    std::cerr << "  " << int_to_string(count) << " " << (count == 1 ? "sequence" : "sequences") << ", " << int_to_string((long long)n) << " 16-mers\n\n";
-    if ((long double)n * 200.0L >= (long double)args.exclude_percent * 4294967296.0L) {
-        std::cerr << "Error: the reference for --exclude holds too many 16-mers (" << n << ") for --exclude_percent " << args.exclude_percent_text << "\n";
+    const int count = hash_reference(args.exclude, [&](const uint8_t *bases, const uint64_t *offsets, const int64_t *lengths, uint64_t n) {
+        return hashed ? flx_screenset_add(run.exclude_hash, bases, offsets, lengths, n) : flx_screen_set_add(run.exclude, bases, offsets, lengths, n);
+    }, rc);
+    if (hashed && rc == FLX_ERR_NOMEM) { std::cerr << no_memory; return 1; }
+    if (rc != FLX_OK) return run.fail("exclude");
+    if ((hashed ? flx_screenset_finalize(run.exclude_hash) : flx_kmerset_finalize(run.exclude)) != FLX_OK) return run.fail("exclude set");
+    const uint64_t n = hashed ? flx_screenset_size(run.exclude_hash) : flx_kmerset_size(run.exclude);
+    std::cerr << "  " << int_to_string(count) << " " << (count == 1 ? "sequence" : "sequences") << ", " << int_to_string((long long)n) << " " << (hashed ? "canonical " : "") << k
+              << "-mers\n\n";
+    if ((long double)n * factor >= (long double)args.exclude_percent * space) {
+        std::cerr << "Error: the reference for --exclude holds too many " << k << "-mers (" << n << ") for --exclude_percent " << args.exclude_percent_text << "\n";
         return 1;
     }
-    if (n == 0) { std::cerr << "Error: the reference for --exclude holds no 16-mer of ACGT\n"; return 1; }
+    if (n == 0) { std::cerr << "Error: the reference for --exclude holds no " << k << "-mer of ACGT\n"; return 1; }
     return kGoOn;
 }
 
@@ -200,25 +191,7 @@ static int build_adapters(Run &run) {
         lengths.push_back((int64_t)r.seq.size());
         pack.insert(pack.end(), (const uint8_t *)r.seq.p, (const uint8_t *)r.seq.p + r.seq.size());
     };
-    BlockReader blocks;
-    if (!getenv("FLX_CLI_NO_STREAM") && blocks.open(args.trim_adapters, false)) {
-        Parsed batch;
-        while (blocks.next(batch)) {
-            for (const Record &r : batch.recs) take(r);
-            if (batch.status <= -2) break;
-        }
-    } else {
-        Input data;
-        std::deque<std::string> arena;
-        if (data.open(args.trim_adapters)) {
-            Parser p(data, arena);
-            Record r;
-            while (p.next(r) >= 0) {
-                take(r);
-                arena.clear();
-            }
-        }
-    }
+    for_each_record(args.trim_adapters, take, [] { return true; });
     const size_t count = offsets.size();
     std::cerr << "  " << int_to_string((long long)count) << " " << (count == 1 ? "sequence" : "sequences") << "\n\n";
     for (size_t i = 0; i < count; ++i) {

@@ -44,6 +44,15 @@ struct Run {
     flx_screenset *exclude_hash = nullptr;     // --exclude_k 17..31: the contaminant's canonical K-mers instead (one of the two)
     int exclude_k = 16;                        // the K of whichever set was built
     bool excluding() const { return exclude != nullptr || exclude_hash != nullptr; }
+    int set_pipeline_screen(flx_pipeline *pipe) const {  // the pipeline screens every chunk against whichever set was built
+        return exclude_hash ? flx_pipeline_set_screenset(pipe, exclude_hash, args.exclude_percent) : flx_pipeline_set_screen(pipe, exclude, args.exclude_percent);
+    }
+    void destroy_exclude() {
+        if (exclude) flx_kmerset_destroy(exclude);
+        if (exclude_hash) flx_screenset_destroy(exclude_hash);
+        exclude = nullptr;
+        exclude_hash = nullptr;
+    }
     const uint32_t *screen_hits = nullptr;     // ... and, once the scores are in, every read's hits and whether it was excluded
     const uint8_t *screen_excluded = nullptr;  // (owned by the pipeline; this rank's reads in submission order)
     flx_adapters *adapters = nullptr;          // --trim_adapters: the patterns (reference.h: build_adapters) ...

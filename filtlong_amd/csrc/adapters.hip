@@ -165,21 +165,6 @@ int flx_adapters_table(flx_ctx *ctx, flx_adapters *ad, const Pattern **out) {
     return FLX_OK;
 }
 
-int flx_adapters_check_reads(flx_ctx *ctx, uint64_t plane_bytes, const uint64_t *offsets, const int32_t *lengths, const uint32_t *order, uint64_t n_reads) {
-    for (uint64_t i = 0; i < n_reads; ++i) {
-        if (lengths[i] < 0 || (offsets[i] & 15) || offsets[i] + (((uint64_t)lengths[i] + 15) & ~15ull) > plane_bytes)
-            return flx_fail(ctx, FLX_ERR_INVALID, "read %llu: offset must be 16-byte aligned and inside the plane", (unsigned long long)i);
-    }
-    if (order) {  // a permutation: every key is written by exactly the patterns of its own read end
-        std::vector<uint8_t> seen(n_reads, 0);
-        for (uint64_t i = 0; i < n_reads; ++i) {
-            if (order[i] >= n_reads || seen[order[i]]) return flx_fail(ctx, FLX_ERR_INVALID, "order is not a permutation of the reads");
-            seen[order[i]] = 1;
-        }
-    }
-    return FLX_OK;
-}
-
 extern "C" int flx_adapters_create(const uint8_t *bases, const uint64_t *offsets, const int64_t *lengths, uint64_t n_seqs, int errors_percent,
                                    int window, flx_adapters **out) {
     if (!out) return FLX_ERR_INVALID;
@@ -243,7 +228,7 @@ extern "C" int flx_adapter_cuts(flx_ctx *ctx, flx_adapters *ad, const uint8_t *p
     if (plane_bytes & 15) return flx_fail(ctx, FLX_ERR_INVALID, "plane_bytes must be a multiple of 16");
     if (n_reads == 0) return FLX_OK;
     if (!plane || !offsets || !lengths || !keys) return flx_fail(ctx, FLX_ERR_INVALID, "plane/offsets/lengths/keys must not be NULL");
-    FLX_CHECK(flx_adapters_check_reads(ctx, plane_bytes, offsets, lengths, order, n_reads));
+    FLX_CHECK(flx_check_reads(ctx, plane_bytes, offsets, lengths, order, n_reads));  // (every key is written by the patterns of its own read end)
     FLX_HIP(ctx, hipSetDevice(ctx->device));
     flx_dbuf d_plane, d_off, d_len, d_ord, d_keys;
     FLX_CHECK(flx_dalloc(ctx, d_plane, plane_bytes ? plane_bytes : 16));

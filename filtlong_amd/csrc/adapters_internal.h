@@ -17,9 +17,6 @@ struct flx_adapters {
 
 // the adapters' pattern table on the context's device
 int flx_adapters_table(flx_ctx *ctx, flx_adapters *ad, const adapters::Pattern **out);
-// what the host forms of flx_adapter_cuts and flx_adapter_marks check of their reads
-int flx_adapters_check_reads(flx_ctx *ctx, uint64_t plane_bytes, const uint64_t *offsets, const int32_t *lengths, const uint32_t *order,
-                             uint64_t n_reads);
 
 // adapters_split.hip.  The device scratch of one marks call: flx_adapter_marks_scratch(n_reads) bytes.
 size_t flx_adapter_marks_scratch(uint64_t n_reads);

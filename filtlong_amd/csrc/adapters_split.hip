@@ -404,7 +404,7 @@ extern "C" int flx_adapter_marks(flx_ctx *ctx, flx_adapters *ad, const uint8_t *
     if (plane_bytes & 15) return flx_fail(ctx, FLX_ERR_INVALID, "plane_bytes must be a multiple of 16");
     if (n_reads == 0) return FLX_OK;
     if (!plane || !offsets || !lengths || !marks) return flx_fail(ctx, FLX_ERR_INVALID, "plane/offsets/lengths/marks must not be NULL");
-    FLX_CHECK(flx_adapters_check_reads(ctx, plane_bytes, offsets, lengths, order, n_reads));
+    FLX_CHECK(flx_check_reads(ctx, plane_bytes, offsets, lengths, order, n_reads));
     FLX_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t mark_bytes = adapters::mark_words(plane_bytes) * 4;
     flx_dbuf d_plane, d_off, d_len, d_ord, d_marks;

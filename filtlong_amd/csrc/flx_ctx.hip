@@ -309,6 +309,21 @@ extern "C" int flx_plane_layout(const int32_t *lengths, uint64_t n_reads, uint64
     return FLX_OK;
 }
 
+int flx_check_reads(flx_ctx *ctx, uint64_t plane_bytes, const uint64_t *offsets, const int32_t *lengths, const uint32_t *order, uint64_t n_reads) {
+    for (uint64_t i = 0; i < n_reads; ++i) {
+        if (lengths[i] < 0 || (offsets[i] & 15) || offsets[i] + (((uint64_t)lengths[i] + 15) & ~15ull) > plane_bytes)
+            return flx_fail(ctx, FLX_ERR_INVALID, "read %llu: offset must be 16-byte aligned and inside the plane", (unsigned long long)i);
+    }
+    if (order) {
+        std::vector<uint8_t> seen(n_reads, 0);
+        for (uint64_t i = 0; i < n_reads; ++i) {
+            if (order[i] >= n_reads || seen[order[i]]) return flx_fail(ctx, FLX_ERR_INVALID, "order is not a permutation of the reads");
+            seen[order[i]] = 1;
+        }
+    }
+    return FLX_OK;
+}
+
 extern "C" int flx_length_order(const int32_t *lengths, uint64_t n_reads, uint32_t *order) {
     if ((!lengths || !order) && n_reads) return FLX_ERR_INVALID;
     if (n_reads > 0xffffffffull) return FLX_ERR_INVALID;

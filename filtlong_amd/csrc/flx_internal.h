@@ -129,6 +129,10 @@ struct flx_dbuf {
 };
 int flx_dalloc(flx_ctx *ctx, flx_dbuf &b, size_t bytes);
 
+// What the host-array entry points check of their reads: every read 16-byte aligned and, padded to 16, inside the plane; `order`
+// (NULL: not checked) a permutation of the reads, for the kernels that write every read's result exactly once.
+int flx_check_reads(flx_ctx *ctx, uint64_t plane_bytes, const uint64_t *offsets, const int32_t *lengths, const uint32_t *order, uint64_t n_reads);
+
 // comm.hip: element-wise sums over all ranks of the context's communicator
 int flx_comm_allreduce_u64_dev(flx_ctx *ctx, uint64_t *d_buf, uint64_t count);   // device buffer, in stream order
 int flx_comm_allreduce_u64_host(flx_ctx *ctx, uint64_t *buf, uint64_t count);    // host buffer, synchronous

@@ -13,15 +13,7 @@
 #include <mutex>
 #include <thread>
 
-#include "flx_internal.h"
-#include "kmerset.h"
-#include "screen.h"
-
-// screen.hip: passed[i] = 0 and child_passed = 0 for the children of every read the screen excludes; excluded[i] says which
-int flx_screen_apply_dev(flx_ctx *ctx, uint64_t n_reads, const int32_t *d_lengths, const uint32_t *d_hits, uint64_t t, int k,
-                         uint8_t *d_passed, const uint64_t *d_child_offsets, uint8_t *d_child_passed, uint8_t *d_excluded);
-// screen_hash.hip
-bool flx_screenset_is_final(const flx_screenset *set);
+#include "screen_internal.h"
 
 // adapters.hip: flx_score_batch_adapters_dev that also leaves the keys [2 n] in d_keys (NULL: in a workspace of its own)
 int flx_adapters_score_dev(flx_ctx *ctx, flx_adapters *ad, const void *d_plane, const void *d_seq_plane, uint64_t plane_bytes, const void *d_offsets,
@@ -58,10 +50,8 @@ struct flx_pipeline {
     flx_params params;
     bool qsplit = false;     // flx_pipeline_set_qsplit: Phred mode, reads split at their low-quality windows
     double qsplit_q = 0;
-    const flx_kmerset *screen_set = nullptr;  // flx_pipeline_set_screen: reads that match this set fail
-    const flx_screenset *screen_hash = nullptr;  // flx_pipeline_set_screenset: the same with K-mers of 16..31 bases (one of the two)
-    int screen_k = 16;
-    uint64_t screen_t = 0;
+    flx_screen_ref screen;   // flx_pipeline_set_screen / flx_pipeline_set_screenset: reads that match this set fail ...
+    uint64_t screen_t = 0;   // ... with more than this share of their windows (screen.h: threshold)
     flx_adapters *adapters = nullptr;         // flx_pipeline_set_adapters: Phred mode, adapters cut off the read ends
     int planes = 1;          // 2: a Phred-mode pipeline with a screen or adapters — qualities, then sequences, plane_bytes each
     bool submitted = false;  // a chunk has been submitted
@@ -114,7 +104,7 @@ int alloc_slot(flx_pipeline *p, Slot &s) {
     FLX_HIP(ctx, hipMalloc((void **)&s.d_first, nr * 4));
     FLX_HIP(ctx, hipMalloc((void **)&s.d_last, nr * 4));
     FLX_HIP(ctx, hipMalloc((void **)&s.d_coff, (nr + 1) * 8));
-    if (p->screen_set || p->screen_hash) {
+    if (p->screen) {
         FLX_HIP(ctx, hipMalloc((void **)&s.d_hits, nr * 4));
         FLX_HIP(ctx, hipMalloc((void **)&s.d_excl, nr));
     }
@@ -176,10 +166,9 @@ int score_slot(flx_pipeline *p, Slot &s) {
         FLX_CHECK(rc);
         break;
     }
-    if ((p->screen_set || p->screen_hash) && n) {  // behind the scoring, on the same stream
-        if (p->screen_set) FLX_CHECK(flx_screen_hits_dev(ctx, p->screen_set, d_seq, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, s.d_hits));
-        else FLX_CHECK(flx_screenset_hits_dev(ctx, p->screen_hash, d_seq, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, s.d_hits));
-        FLX_CHECK(flx_screen_apply_dev(ctx, n, s.d_len, s.d_hits, p->screen_t, p->screen_k, s.d_pass, want_children ? s.d_coff : nullptr,
+    if (p->screen && n) {  // behind the scoring, on the same stream
+        FLX_CHECK(screen_hits_dev(ctx, p->screen, d_seq, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, s.d_hits));
+        FLX_CHECK(flx_screen_apply_dev(ctx, n, s.d_len, s.d_hits, p->screen_t, p->screen.k(), s.d_pass, want_children ? s.d_coff : nullptr,
                                        want_children ? p->d_cpass : nullptr, s.d_excl));
     }
     const size_t at = p->mean_q.size();
@@ -193,7 +182,7 @@ int score_slot(flx_pipeline *p, Slot &s) {
         FLX_HIP(ctx, hipMemcpyAsync(&p->first[at], s.d_first, n * 4, hipMemcpyDeviceToHost, st));
         FLX_HIP(ctx, hipMemcpyAsync(&p->last[at], s.d_last, n * 4, hipMemcpyDeviceToHost, st));
     }
-    if (p->screen_set || p->screen_hash) {
+    if (p->screen) {
         p->hits.resize(at + n); p->excluded.resize(at + n);
         if (n) {
             FLX_HIP(ctx, hipMemcpyAsync(&p->hits[at], s.d_hits, n * 4, hipMemcpyDeviceToHost, st));
@@ -222,6 +211,25 @@ int score_slot(flx_pipeline *p, Slot &s) {
     FLX_HIP(ctx, hipStreamSynchronize(st));
     for (uint64_t i = 0; i < n; ++i) p->child_offsets[oat + i] = cbase + coff[i + 1];
     return FLX_OK;
+}
+
+// the slots again, for what the pipeline has been given since: capacities, a screen's arrays, the keys, room for the sequences
+int realloc_slots(flx_pipeline *p) {
+    for (int k = 0; k < 2; ++k) free_slot(p->slot[k]);
+    for (int k = 0; k < 2; ++k) FLX_CHECK(alloc_slot(p, p->slot[k]));
+    return FLX_OK;
+}
+
+// the rest of both screen setters, behind the checks of their own kind of set
+int set_screen_common(flx_pipeline *p, flx_screen_ref ref, double percent) {
+    flx_ctx *ctx = p->ctx;
+    uint64_t t = 0;
+    if (flx_screen_threshold(percent, &t) != FLX_OK) return flx_fail(ctx, FLX_ERR_INVALID, "exclude_percent must be greater than 0 and at most 100");
+    FLX_HIP(ctx, hipSetDevice(ctx->device));
+    p->screen = ref;
+    p->screen_t = t;
+    p->planes = p->set && flx_kmerset_size(p->set) > 0 ? 1 : 2;  // (Phred mode: room for the sequences)
+    return realloc_slots(p);
 }
 
 void worker_main(flx_pipeline *p) {
@@ -307,41 +315,22 @@ extern "C" int flx_pipeline_set_screen(flx_pipeline *p, const flx_kmerset *exclu
     if (!p) return FLX_ERR_INVALID;
     flx_ctx *ctx = p->ctx;
     if (p->submitted || p->handed_out) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_screen after flx_pipeline_next_buffer / flx_pipeline_submit");
-    if (p->screen_hash) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_screen on a pipeline with flx_pipeline_set_screenset");
+    if (p->screen.hashed) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_screen on a pipeline with flx_pipeline_set_screenset");
     if (!exclude_set) return flx_fail(ctx, FLX_ERR_INVALID, "flx_pipeline_set_screen: set must not be NULL");
     if (!flx_kmerset_is_final(exclude_set)) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is not finalized");
     if (flx_kmerset_size(exclude_set) == 0) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is empty (no run of 16 bases of ACGT in it)");
-    uint64_t t = 0;
-    if (flx_screen_threshold(percent, &t) != FLX_OK) return flx_fail(ctx, FLX_ERR_INVALID, "exclude_percent must be greater than 0 and at most 100");
-    FLX_HIP(ctx, hipSetDevice(ctx->device));
-    const bool kmer_mode = p->set && flx_kmerset_size(p->set) > 0;
-    for (int k = 0; k < 2; ++k) free_slot(p->slot[k]);  // the slots again, with the screen's arrays and (Phred mode) room for the sequences
-    p->screen_set = exclude_set;
-    p->screen_t = t;
-    p->planes = kmer_mode ? 1 : 2;
-    for (int k = 0; k < 2; ++k) FLX_CHECK(alloc_slot(p, p->slot[k]));
-    return FLX_OK;
+    return set_screen_common(p, flx_screen_ref{exclude_set, nullptr}, percent);
 }
 
 extern "C" int flx_pipeline_set_screenset(flx_pipeline *p, const flx_screenset *exclude_set, double percent) {
     if (!p) return FLX_ERR_INVALID;
     flx_ctx *ctx = p->ctx;
     if (p->submitted || p->handed_out) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_screenset after flx_pipeline_next_buffer / flx_pipeline_submit");
-    if (p->screen_set) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_screenset on a pipeline with flx_pipeline_set_screen");
+    if (p->screen.bitmap) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_screenset on a pipeline with flx_pipeline_set_screen");
     if (!exclude_set) return flx_fail(ctx, FLX_ERR_INVALID, "flx_pipeline_set_screenset: set must not be NULL");
     if (!flx_screenset_is_final(exclude_set)) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is not finalized");
     if (flx_screenset_size(exclude_set) == 0) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is empty (no K-mer of ACGT in it)");
-    uint64_t t = 0;
-    if (flx_screen_threshold(percent, &t) != FLX_OK) return flx_fail(ctx, FLX_ERR_INVALID, "exclude_percent must be greater than 0 and at most 100");
-    FLX_HIP(ctx, hipSetDevice(ctx->device));
-    const bool kmer_mode = p->set && flx_kmerset_size(p->set) > 0;
-    for (int k = 0; k < 2; ++k) free_slot(p->slot[k]);  // the slots again, as flx_pipeline_set_screen makes them
-    p->screen_hash = exclude_set;
-    p->screen_k = flx_screenset_k(exclude_set);
-    p->screen_t = t;
-    p->planes = kmer_mode ? 1 : 2;
-    for (int k = 0; k < 2; ++k) FLX_CHECK(alloc_slot(p, p->slot[k]));
-    return FLX_OK;
+    return set_screen_common(p, flx_screen_ref{nullptr, exclude_set}, percent);
 }
 
 extern "C" int flx_pipeline_set_adapters(flx_pipeline *p, flx_adapters *adapters) {
@@ -353,11 +342,9 @@ extern "C" int flx_pipeline_set_adapters(flx_pipeline *p, flx_adapters *adapters
     if (!adapters) return flx_fail(ctx, FLX_ERR_INVALID, "flx_pipeline_set_adapters: adapters must not be NULL");
     if (p->params.trim || p->params.split_set) return flx_fail(ctx, FLX_ERR_INVALID, "trim/split need a k-mer set: not with adapters");
     FLX_HIP(ctx, hipSetDevice(ctx->device));
-    for (int k = 0; k < 2; ++k) free_slot(p->slot[k]);  // the slots again, with the keys and room for the sequences
     p->adapters = adapters;
     p->planes = 2;  // (with a screen as well there is still ONE sequence plane)
-    for (int k = 0; k < 2; ++k) FLX_CHECK(alloc_slot(p, p->slot[k]));
-    return FLX_OK;
+    return realloc_slots(p);
 }
 
 extern "C" int flx_pipeline_adapters(flx_pipeline *p, const uint32_t **keys) {
@@ -371,7 +358,7 @@ extern "C" int flx_pipeline_adapters(flx_pipeline *p, const uint32_t **keys) {
 
 extern "C" int flx_pipeline_screen(flx_pipeline *p, const uint32_t **hits, const uint8_t **excluded) {
     if (!p) return FLX_ERR_INVALID;
-    if (!p->screen_set && !p->screen_hash) return flx_fail(p->ctx, FLX_ERR_STATE, "flx_pipeline_screen on a pipeline without a screen");
+    if (!p->screen) return flx_fail(p->ctx, FLX_ERR_STATE, "flx_pipeline_screen on a pipeline without a screen");
     std::unique_lock<std::mutex> lk(p->mu);
     if (!p->queue.empty()) return flx_fail(p->ctx, FLX_ERR_STATE, "flx_pipeline_screen before flx_pipeline_finish");
     if (hits) *hits = p->hits.data();
@@ -398,14 +385,9 @@ extern "C" int flx_pipeline_reserve(flx_pipeline *p, uint64_t chunk_plane_bytes,
     FLX_HIP(ctx, hipSetDevice(ctx->device));
     FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     FLX_HIP(ctx, hipStreamSynchronize(p->copy_stream));
-    for (int k = 0; k < 2; ++k) free_slot(p->slot[k]);
     p->cap_bytes = want_bytes;
     p->cap_reads = want_reads;
-    for (int k = 0; k < 2; ++k) {
-        const int rc = alloc_slot(p, p->slot[k]);
-        if (rc != FLX_OK) return rc;
-    }
-    return FLX_OK;
+    return realloc_slots(p);
 }
 
 extern "C" int flx_pipeline_next_buffer(flx_pipeline *p, uint8_t **plane, uint64_t *capacity_bytes, uint64_t *capacity_reads) {

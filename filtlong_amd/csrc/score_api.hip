@@ -71,12 +71,8 @@ static int score_batch_host(flx_ctx *ctx, const flx_kmerset *set, const uint8_t 
         return FLX_OK;
     }
     if (!plane || !offsets || !lengths) return flx_fail(ctx, FLX_ERR_INVALID, "plane/offsets/lengths must not be NULL");
-    for (uint64_t i = 0; i < n_reads; ++i) {
-        if (lengths[i] < 0 || (offsets[i] & 15) ||
-            offsets[i] + (((uint64_t)lengths[i] + 15) & ~15ull) > plane_bytes)
-            return flx_fail(ctx, FLX_ERR_INVALID, "read %llu: offset must be 16-byte aligned and inside the plane",
-                            (unsigned long long)i);
-    }
+    // (with adapters `order` must be a permutation: every key is written by exactly the patterns of its own read end)
+    FLX_CHECK(flx_check_reads(ctx, plane_bytes, offsets, lengths, adapters ? order : nullptr, n_reads));
     PhaseTimer pt;
     pt.mark("validate");
     FLX_HIP(ctx, hipSetDevice(ctx->device));
@@ -214,12 +210,5 @@ extern "C" int flx_score_batch_adapters(flx_ctx *ctx, flx_adapters *adapters, co
     if (!adapters) return flx_fail(ctx, FLX_ERR_INVALID, "flx_score_batch_adapters: adapters must not be NULL");
     if (n_reads && !seq_plane) return flx_fail(ctx, FLX_ERR_INVALID, "the sequence plane must not be NULL");
     if (params && (params->trim || params->split_set)) return flx_fail(ctx, FLX_ERR_INVALID, "trim/split need a k-mer set: not with adapters");
-    if (order) {  // a permutation: every key is written by exactly the patterns of its own read end
-        std::vector<uint8_t> seen(n_reads, 0);
-        for (uint64_t i = 0; i < n_reads; ++i) {
-            if (order[i] >= n_reads || seen[order[i]]) return flx_fail(ctx, FLX_ERR_INVALID, "order is not a permutation of the reads");
-            seen[order[i]] = 1;
-        }
-    }
     return score_batch_host(ctx, nullptr, plane, plane_bytes, offsets, lengths, order, n_reads, params, nullptr, out, adapters, seq_plane);
 }

@@ -8,11 +8,16 @@
 //   k_screen_segments   spans per read in processing order, ceil(windows / kScreenSpan); the exclusive scan of sort.hip turns them
 //                       into the segment table seg_start[0 .. n_reads], all on the device: no host round trip in front of the kernel
 //   k_screen_hits       persistent workgroups of 16 waves; wave w of the grid takes the spans w, w + waves, ...; the read of a span
-//                       is found by a binary search in seg_start (wave-uniform).  A span goes 1024 positions a step: every lane owns
-//                       16 consecutive window starts, i.e. the 16 bytes of one aligned 16-byte load plus the next 15 (a second
-//                       aligned load, skipped where it would leave [offset, offset + round_up(L, 16))).  The next step's bytes are
-//                       requested before this step's are used.  Per lane: the 2-bit codes of its 31 bases in one 64-bit word, a
-//                       validity bit per byte, and from those the 16 windows that consist of ACGTacgt only.
+//                       is found by a binary search in seg_start (wave-uniform; screen_walk.h: span_of).  A span goes 1024 positions
+//                       a step: every lane owns 16 consecutive window starts, i.e. the 16 bytes of one aligned 16-byte load plus the
+//                       next 15 (a second aligned load, skipped where it would leave [offset, offset + round_up(L, 16))).  The next
+//                       step's bytes are requested before this step's are used.  Per lane: the 2-bit codes of its 31 bases in one
+//                       64-bit word, a validity bit per byte (screen_walk.h has both, for the hashed kernels too), and from those the
+//                       16 windows that consist of ACGTacgt only.
+//
+// The host side of both kinds of set is here as well (screen_internal.h): screen_hits_dev — the checks, the segment table, the launch
+// of k_screen_hits or of screen_hash.hip's kernel — and screen_hits_host, the staged host-array form; flx_screen_hits*,
+// flx_screenset_hits* and the pipeline call them with a flx_screen_ref.
 //
 // Three filters stand in front of the exact answer; none has false negatives, and only the exact bitmap decides a hit:
 //   TIER 2 "lds"    the presence bitmap of the 10-mers inside members of X (4^10 bits = 128 KiB), loaded into LDS once per workgroup
@@ -22,19 +27,21 @@
 //   TIER 1 "pre12"  no LDS table (too full to pay: kmerset.hip has the threshold): the L2-resident 12-mer prefilter, rolled the
 //                   same way — 20 lookups per lane, five consecutive set bits — then the bitmap.
 //   TIER 0 "exact"  the set has no prefilters (FLX_KMER_PREFILTER=0, or a set too large for them): every valid window asks the bitmap.
-#include "flx_internal.h"
-#include "kmerset.h"
 #include "rank_internal.h"
-#include "screen_hash.h"
+#include "screen_internal.h"
+#include "screen_walk.h"
 
 namespace {
 
 using screen::kScreenSpan;
 using screen::kScreenStep;
+using screen_walk::codes4;
+using screen_walk::span_of;
+using screen_walk::u32x4;
+using screen_walk::valid4;
 
 constexpr int kScreenThreads = 1024;  // 16 waves: with the 128 KiB table one workgroup per CU
 constexpr int kPre10Words = 1 << 15;  // 4^10 bits
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // (the compiler's own vector: sixteen bytes that stay in registers)
 
 __global__ void __launch_bounds__(256) k_screen_segments(const int32_t *lengths, const uint32_t *order, uint64_t n_reads, int k, uint32_t *counts) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -48,18 +55,6 @@ __global__ void __launch_bounds__(256) k_screen_segments(const int32_t *lengths,
 }
 
 __device__ __forceinline__ uint32_t bit_of(const uint32_t *bm, uint32_t k) { return (bm[k >> 5] >> (k & 31)) & 1u; }
-
-// the codes of the four bases in a dword of the plane, first base on top (bits 7..0 of the result)
-__device__ __forceinline__ uint32_t codes4(uint32_t w) {
-    const uint32_t c2 = ((w >> 1) ^ (w >> 2)) & 0x03030303u;  // the code of byte b in bits 8 b + 1 .. 8 b
-    return (c2 * 0x40100401u) >> 24;                          // b0 << 30 | b1 << 28 | b2 << 26 | b3 << 24: no two terms overlap
-}
-__device__ __forceinline__ uint32_t valid4(uint32_t w) {
-    uint32_t m = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) m |= (screen::is_acgt((uint8_t)(w >> (8 * b))) ? 1u : 0u) << b;
-    return m;
-}
 
 template <int TIER>
 __global__ void __launch_bounds__(kScreenThreads) k_screen_hits(const uint8_t *__restrict__ plane, const uint64_t *__restrict__ offsets,
@@ -81,13 +76,7 @@ __global__ void __launch_bounds__(kScreenThreads) k_screen_hits(const uint8_t *_
     const u32x4 zero = {0u, 0u, 0u, 0u};  // (a zero byte is not in ACGTacgt)
 
     for (uint32_t sp = blockIdx.x * (kScreenThreads / 64) + wave; sp < total; sp += n_waves) {
-        // the read of span sp: the largest r with seg_start[r] <= sp (reads without spans share their successor's start and lose)
-        uint32_t lo = 0, hi = n_reads;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (seg_start[mid] <= sp) lo = mid;
-            else hi = mid;
-        }
+        const uint32_t lo = span_of(seg_start, n_reads, sp);
         const uint32_t read = order ? order[lo] : lo;
         const uint32_t len = (uint32_t)lengths[read];     // at least 16: the read has a span
         const uint32_t lpad = (len + 15u) & ~15u;         // loads stay inside [offset, offset + lpad)
@@ -184,13 +173,18 @@ __global__ void __launch_bounds__(256) k_screen_apply(uint64_t n_reads, const in
 
 }  // namespace
 
-// the spans of every read in processing order for windows of k bases, counts[0 .. n_reads] (the last is 0), on the context's stream:
-// the head of flx_screen_hits_dev and of screen_hash.hip's calls
-int flx_screen_segments_dev(flx_ctx *ctx, const int32_t *d_lengths, const uint32_t *d_order, uint64_t n_reads, int k, uint32_t *d_counts) {
-    hipLaunchKernelGGL(k_screen_segments, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, ctx->stream, d_lengths, d_order, n_reads, k,
-                       d_counts);
+// the spans of every read in processing order for windows of k bases, counts[0 .. n] (the last is 0), and their exclusive scan: no
+// host round trip in front of a walk (screen_hits_dev below, flx_screenset_add)
+int flx_screen_segment_table(flx_ctx *ctx, const int32_t *d_lengths, const uint32_t *d_order, uint64_t n, int k, uint32_t **seg_start) {
+    const size_t table = ((n + 1) * 4 + 255) & ~(size_t)255;
+    const size_t scan_ws = ((n + 1) / 2048 + 4096) * 8;
+    void *scr;
+    FLX_CHECK(flx_scratch(ctx, 2 * table + scan_ws, &scr));
+    uint32_t *counts = (uint32_t *)scr;
+    *seg_start = (uint32_t *)((char *)scr + table);
+    hipLaunchKernelGGL(k_screen_segments, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, ctx->stream, d_lengths, d_order, n, k, counts);
     FLX_HIP(ctx, hipGetLastError());
-    return FLX_OK;
+    return flx_exclusive_scan_u32(ctx, n + 1, counts, *seg_start, (char *)scr + 2 * table, scan_ws);
 }
 
 // An excluded read is a read that fails a hard cut-off: its pass flag and those of its children are cleared on the device, on the
@@ -229,70 +223,61 @@ extern "C" int flx_screen_set_add(flx_kmerset *set, const uint8_t *bases, const 
     return flx_kmerset_add_assembly(set, bases, piece_offsets.data(), piece_lengths.data(), piece_offsets.size());
 }
 
-extern "C" int flx_screen_hits_dev(flx_ctx *ctx, const flx_kmerset *set, const void *d_plane, uint64_t plane_bytes, const void *d_offsets,
-                                   const void *d_lengths, const void *d_order, uint64_t n_reads, uint32_t *d_hits) {
-    if (!ctx) return FLX_ERR_INVALID;
-    if (!set) return flx_fail(ctx, FLX_ERR_INVALID, "flx_screen_hits: set must not be NULL");
-    if (!flx_kmerset_is_final(set)) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is not finalized");
-    if (flx_kmerset_size(set) == 0) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is empty (no run of 16 bases of ACGT in it)");
+namespace {
+
+int check_set(flx_ctx *ctx, flx_screen_ref ref) {
+    if (!ref.is_final()) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is not finalized");
+    if (ref.size() == 0) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is empty (no run of %d bases of ACGT in it)", ref.k());
+    return FLX_OK;
+}
+
+// k_screen_hits<tier> for the filters the set has, over a finished segment table
+int launch_bitmap_hits(flx_ctx *ctx, const flx_kmerset *set, const void *d_plane, const void *d_offsets, const void *d_lengths, const void *d_order,
+                       uint64_t n_reads, const uint32_t *seg_start, uint32_t *d_hits) {
+    const uint32_t *pre10 = flx_kmerset_pre10(set), *pre12 = flx_kmerset_prefilter(set);
+    const int tier = pre10 ? 2 : pre12 ? 1 : 0;
+    ctx->last_screen_filter = tier == 2 ? "lds" : tier == 1 ? "pre12" : "exact";
+    const unsigned n_cu = (unsigned)ctx->prop.multiProcessorCount;
+#define FLX_SCREEN_LAUNCH(T, blocks)                                                                                                                \
+    hipLaunchKernelGGL(k_screen_hits<T>, dim3(blocks), dim3(kScreenThreads), 0, ctx->stream, (const uint8_t *)d_plane, (const uint64_t *)d_offsets, \
+                       (const int32_t *)d_lengths, (const uint32_t *)d_order, (uint32_t)n_reads, seg_start, flx_kmerset_bitmap(set), pre12, pre10, d_hits)
+    if (tier == 2) FLX_SCREEN_LAUNCH(2, n_cu);  // the table fills the LDS of a CU: one workgroup each
+    else if (tier == 1) FLX_SCREEN_LAUNCH(1, 2 * n_cu);
+    else FLX_SCREEN_LAUNCH(0, 2 * n_cu);
+#undef FLX_SCREEN_LAUNCH
+    FLX_HIP(ctx, hipGetLastError());
+    return FLX_OK;
+}
+
+}  // namespace
+
+int screen_hits_dev(flx_ctx *ctx, flx_screen_ref ref, const void *d_plane, uint64_t plane_bytes, const void *d_offsets, const void *d_lengths,
+                    const void *d_order, uint64_t n_reads, uint32_t *d_hits) {
+    FLX_CHECK(check_set(ctx, ref));
     if (n_reads > 0xfffffffeull) return flx_fail(ctx, FLX_ERR_INVALID, "at most 2^32-2 reads per batch");
     if (plane_bytes & 15) return flx_fail(ctx, FLX_ERR_INVALID, "plane_bytes must be a multiple of 16");
     if (n_reads == 0) return FLX_OK;
     if (!d_plane || !d_offsets || !d_lengths || !d_hits) return flx_fail(ctx, FLX_ERR_INVALID, "plane/offsets/lengths/hits must not be NULL");
     if (plane_bytes / (uint64_t)kScreenSpan + n_reads > 0xffffffffull) return flx_fail(ctx, FLX_ERR_INVALID, "too many spans in one batch");
     FLX_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-
-    // counts [n + 1] | seg_start [n + 1] | the scan's block sums
-    const size_t table = ((n_reads + 1) * 4 + 255) & ~(size_t)255;
-    const size_t scan_ws = ((n_reads + 1) / 2048 + 4096) * 8;
-    void *scr;
-    FLX_CHECK(flx_scratch(ctx, 2 * table + scan_ws, &scr));
-    uint32_t *counts = (uint32_t *)scr, *seg_start = (uint32_t *)((char *)scr + table);
-    void *ws = (char *)scr + 2 * table;
-
-    const uint32_t *pre10 = flx_kmerset_pre10(set), *pre12 = flx_kmerset_prefilter(set);
-    const int tier = pre10 ? 2 : pre12 ? 1 : 0;
-    ctx->last_screen_filter = tier == 2 ? "lds" : tier == 1 ? "pre12" : "exact";
-    const unsigned n_cu = (unsigned)ctx->prop.multiProcessorCount;
-
     flx_time_scope timed(ctx, "flx_screen");
-    FLX_HIP(ctx, hipMemsetAsync(d_hits, 0, n_reads * 4, st));
-    FLX_CHECK(flx_screen_segments_dev(ctx, (const int32_t *)d_lengths, (const uint32_t *)d_order, n_reads, 16, counts));
-    FLX_CHECK(flx_exclusive_scan_u32(ctx, n_reads + 1, counts, seg_start, ws, scan_ws));
-#define FLX_SCREEN_LAUNCH(T, blocks)                                                                                                        \
-    hipLaunchKernelGGL(k_screen_hits<T>, dim3(blocks), dim3(kScreenThreads), 0, st, (const uint8_t *)d_plane, (const uint64_t *)d_offsets, \
-                       (const int32_t *)d_lengths, (const uint32_t *)d_order, (uint32_t)n_reads, (const uint32_t *)seg_start,             \
-                       flx_kmerset_bitmap(set), pre12, pre10, d_hits)
-    if (tier == 2) FLX_SCREEN_LAUNCH(2, n_cu);  // the table fills the LDS of a CU: one workgroup each
-    else if (tier == 1) FLX_SCREEN_LAUNCH(1, 2 * n_cu);
-    else FLX_SCREEN_LAUNCH(0, 2 * n_cu);
-#undef FLX_SCREEN_LAUNCH
-    FLX_HIP(ctx, hipGetLastError());
+    FLX_HIP(ctx, hipMemsetAsync(d_hits, 0, n_reads * 4, ctx->stream));
+    uint32_t *seg_start = nullptr;
+    FLX_CHECK(flx_screen_segment_table(ctx, (const int32_t *)d_lengths, (const uint32_t *)d_order, n_reads, ref.k(), &seg_start));
+    if (ref.hashed) FLX_CHECK(flx_screenset_launch_hits(ctx, ref.hashed, d_plane, d_offsets, d_lengths, d_order, n_reads, seg_start, d_hits));
+    else FLX_CHECK(launch_bitmap_hits(ctx, ref.bitmap, d_plane, d_offsets, d_lengths, d_order, n_reads, seg_start, d_hits));
     timed.end();
     return FLX_OK;
 }
 
-extern "C" int flx_screen_hits(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets,
-                               const int32_t *lengths, const uint32_t *order, uint64_t n_reads, uint32_t *hits) {
-    if (!ctx) return FLX_ERR_INVALID;
-    if (!set) return flx_fail(ctx, FLX_ERR_INVALID, "flx_screen_hits: set must not be NULL");
-    if (!flx_kmerset_is_final(set)) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is not finalized");
-    if (flx_kmerset_size(set) == 0) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is empty (no run of 16 bases of ACGT in it)");
+// the host-array form: everything staged through device buffers of the call's own
+int screen_hits_host(flx_ctx *ctx, flx_screen_ref ref, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets, const int32_t *lengths,
+                     const uint32_t *order, uint64_t n_reads, uint32_t *hits) {
+    FLX_CHECK(check_set(ctx, ref));
     if (plane_bytes & 15) return flx_fail(ctx, FLX_ERR_INVALID, "plane_bytes must be a multiple of 16");
     if (n_reads == 0) return FLX_OK;
     if (!plane || !offsets || !lengths || !hits) return flx_fail(ctx, FLX_ERR_INVALID, "plane/offsets/lengths/hits must not be NULL");
-    for (uint64_t i = 0; i < n_reads; ++i) {
-        if (lengths[i] < 0 || (offsets[i] & 15) || offsets[i] + (((uint64_t)lengths[i] + 15) & ~15ull) > plane_bytes)
-            return flx_fail(ctx, FLX_ERR_INVALID, "read %llu: offset must be 16-byte aligned and inside the plane", (unsigned long long)i);
-    }
-    if (order) {  // a permutation: the kernel adds every span of every read exactly once
-        std::vector<uint8_t> seen(n_reads, 0);
-        for (uint64_t i = 0; i < n_reads; ++i) {
-            if (order[i] >= n_reads || seen[order[i]]) return flx_fail(ctx, FLX_ERR_INVALID, "order is not a permutation of the reads");
-            seen[order[i]] = 1;
-        }
-    }
+    FLX_CHECK(flx_check_reads(ctx, plane_bytes, offsets, lengths, order, n_reads));  // (the kernel adds every span of every read exactly once)
     FLX_HIP(ctx, hipSetDevice(ctx->device));
     flx_dbuf d_plane, d_off, d_len, d_ord, d_hits;
     FLX_CHECK(flx_dalloc(ctx, d_plane, plane_bytes ? plane_bytes : 16));
@@ -308,8 +293,22 @@ extern "C" int flx_screen_hits(flx_ctx *ctx, const flx_kmerset *set, const uint8
     }
     // (a pattern no count can be: a kernel that wrote nothing must not hand back an earlier call's answers — score_api.hip)
     FLX_HIP(ctx, hipMemsetAsync(d_hits.p, 0xA5, n_reads * 4, ctx->stream));
-    FLX_CHECK(flx_screen_hits_dev(ctx, set, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr, n_reads, d_hits.as<uint32_t>()));
+    FLX_CHECK(screen_hits_dev(ctx, ref, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr, n_reads, d_hits.as<uint32_t>()));
     FLX_HIP(ctx, hipMemcpyAsync(hits, d_hits.p, n_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
     FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return FLX_OK;
+}
+
+extern "C" int flx_screen_hits_dev(flx_ctx *ctx, const flx_kmerset *set, const void *d_plane, uint64_t plane_bytes, const void *d_offsets,
+                                   const void *d_lengths, const void *d_order, uint64_t n_reads, uint32_t *d_hits) {
+    if (!ctx) return FLX_ERR_INVALID;
+    if (!set) return flx_fail(ctx, FLX_ERR_INVALID, "flx_screen_hits: set must not be NULL");
+    return screen_hits_dev(ctx, flx_screen_ref{set, nullptr}, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n_reads, d_hits);
+}
+
+extern "C" int flx_screen_hits(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets,
+                               const int32_t *lengths, const uint32_t *order, uint64_t n_reads, uint32_t *hits) {
+    if (!ctx) return FLX_ERR_INVALID;
+    if (!set) return flx_fail(ctx, FLX_ERR_INVALID, "flx_screen_hits: set must not be NULL");
+    return screen_hits_host(ctx, flx_screen_ref{set, nullptr}, plane, plane_bytes, offsets, lengths, order, n_reads, hits);
 }

@@ -4,9 +4,10 @@
 // The bitmap of screen.hip is exact for 16-mers and nothing else: an unrelated read keeps |X| / 2^32 of its windows, so a genome
 // cannot be screened with it.  A K-mer of up to 31 bases is a 62-bit number; the set of those of a reference is sparse in 2^62 and
 // is stored by hash.  Both kernels walk their sequences the same way, the way k_screen_hits walks reads (walk_spans below): a work
-// item is a SPAN of kScreenSpan window starts of one sequence, found through the segment table; a lane owns 16 consecutive window
-// starts, i.e. the bytes p .. p + 14 + K <= p + 45 of three aligned 16-byte loads, and turns them into two words of 2-bit codes and
-// a validity mask (lane_words); window_key cuts window j out of them.  One 250 Mbp chromosome is sixty thousand spans.
+// item is a SPAN of kScreenSpan window starts of one sequence, found through the segment table (screen_walk.h: span_of); a lane owns
+// 16 consecutive window starts, i.e. the bytes p .. p + 14 + K <= p + 45 of three aligned 16-byte loads, and turns them into two words
+// of 2-bit codes and a validity mask (lane_words, on the byte helpers of screen_walk.h); window_key cuts window j out of them.  One
+// 250 Mbp chromosome is sixty thousand spans.
 //
 //   k_screenset_insert   every valid window's canonical key goes into the table: a 64-bit atomicCAS on the slot — empty: taken,
 //                        equal: stored already, other: the next slot.  Only the lane whose CAS took an empty slot counts a new key;
@@ -15,12 +16,8 @@
 //   k_screen_hits_hash   persistent workgroups; wave w of the grid takes the spans w, w + waves, ...; the next step's bytes are
 //                        requested before this step's are used; the first probes of eight windows are in flight together, a probe
 //                        chain goes on until the key or an empty slot; one atomicAdd per wave and span into hits[read].
-#include "flx_internal.h"
-#include "rank_internal.h"
-#include "screen_hash.h"
-
-// screen.hip
-int flx_screen_segments_dev(flx_ctx *ctx, const int32_t *d_lengths, const uint32_t *d_order, uint64_t n_reads, int k, uint32_t *d_counts);
+#include "screen_internal.h"
+#include "screen_walk.h"
 
 struct flx_screenset {
     flx_ctx *ctx = nullptr;
@@ -37,25 +34,14 @@ namespace {
 
 using screen::kScreenSpan;
 using screen::kScreenStep;
+using screen_walk::codes16;
+using screen_walk::span_of;
+using screen_walk::u32x4;
+using screen_walk::valid16;
 using screenk::kEmpty;
 
 constexpr int kHashThreads = 256;
 constexpr int kGroup = 8;  // windows of a lane whose first probes are in flight together
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// the codes of the four bases in a dword of the plane, first base on top (bits 7..0 of the result)
-__device__ __forceinline__ uint32_t codes4(uint32_t w) {
-    const uint32_t c2 = ((w >> 1) ^ (w >> 2)) & 0x03030303u;
-    return (c2 * 0x40100401u) >> 24;
-}
-__device__ __forceinline__ uint32_t codes16(u32x4 v) { return (codes4(v.x) << 24) | (codes4(v.y) << 16) | (codes4(v.z) << 8) | codes4(v.w); }
-__device__ __forceinline__ uint32_t valid4(uint32_t w) {
-    uint32_t m = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) m |= (screen::is_acgt((uint8_t)(w >> (8 * b))) ? 1u : 0u) << b;
-    return m;
-}
-__device__ __forceinline__ uint32_t valid16(u32x4 v) { return valid4(v.x) | (valid4(v.y) << 4) | (valid4(v.z) << 8) | (valid4(v.w) << 12); }
 
 // The lane's 48 bytes as codes and windows.  hi: bases 0..31, base b in bits 2 (31 - b) + 1 .. 2 (31 - b); lo: bases 32..47 in the
 // upper half the same way, the lower half zero.  Returns bit j (j < 16): the K bytes from base j on are all in ACGTacgt and j < left,
@@ -89,13 +75,7 @@ __device__ __forceinline__ void walk_spans(const uint8_t *__restrict__ plane, co
     const uint32_t total = seg_start[n_reads];
     const u32x4 zero = {0u, 0u, 0u, 0u};
     for (uint32_t sp = wave; sp < total; sp += n_waves) {
-        // the read of span sp: the largest r with seg_start[r] <= sp (reads without spans share their successor's start and lose)
-        uint32_t lo_r = 0, hi_r = n_reads;
-        while (hi_r - lo_r > 1) {
-            const uint32_t mid = (lo_r + hi_r) >> 1;
-            if (seg_start[mid] <= sp) lo_r = mid;
-            else hi_r = mid;
-        }
+        const uint32_t lo_r = span_of(seg_start, n_reads, sp);
         const uint32_t read = order ? order[lo_r] : lo_r;
         const uint32_t len = (uint32_t)lengths[read];  // at least k: the read has a span
         const uint32_t lpad = (len + 15u) & ~15u;
@@ -252,29 +232,8 @@ int set_grow(flx_screenset *set, uint64_t capacity) {
     return FLX_OK;
 }
 
-// counts [n + 1] | seg_start [n + 1] | the scan's block sums, in the context's scratch; seg_start filled on the stream
-int segment_table(flx_ctx *ctx, const int32_t *d_lengths, const uint32_t *d_order, uint64_t n, int k, uint32_t **seg_start) {
-    const size_t table = ((n + 1) * 4 + 255) & ~(size_t)255;
-    const size_t scan_ws = ((n + 1) / 2048 + 4096) * 8;
-    void *scr;
-    FLX_CHECK(flx_scratch(ctx, 2 * table + scan_ws, &scr));
-    uint32_t *counts = (uint32_t *)scr;
-    *seg_start = (uint32_t *)((char *)scr + table);
-    FLX_CHECK(flx_screen_segments_dev(ctx, d_lengths, d_order, n, k, counts));
-    return flx_exclusive_scan_u32(ctx, n + 1, counts, *seg_start, (char *)scr + 2 * table, scan_ws);
-}
-
-int hits_checks(flx_ctx *ctx, const flx_screenset *set, uint64_t plane_bytes) {
-    if (!set) return flx_fail(ctx, FLX_ERR_INVALID, "flx_screenset_hits: set must not be NULL");
-    if (!set->final) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is not finalized");
-    if (set->size == 0) return flx_fail(ctx, FLX_ERR_STATE, "the set to screen against is empty (no run of %d bases of ACGT in it)", set->k);
-    if (plane_bytes & 15) return flx_fail(ctx, FLX_ERR_INVALID, "plane_bytes must be a multiple of 16");
-    return FLX_OK;
-}
-
 }  // namespace
 
-// pipeline.hip
 bool flx_screenset_is_final(const flx_screenset *set) { return set->final; }
 
 extern "C" int flx_screenset_create(flx_ctx *ctx, int k, int log2_capacity_hint, flx_screenset **out) {
@@ -356,7 +315,7 @@ extern "C" int flx_screenset_add(flx_screenset *set, const uint8_t *bases, const
     FLX_HIP(ctx, hipMemcpyAsync(d_plane.p, plane.data(), plane_bytes, hipMemcpyHostToDevice, st));
     FLX_HIP(ctx, hipMemcpyAsync(d_off.p, at.data(), n * 8, hipMemcpyHostToDevice, st));
     FLX_HIP(ctx, hipMemcpyAsync(d_len.p, len.data(), n * 4, hipMemcpyHostToDevice, st));
-    FLX_CHECK(segment_table(ctx, d_len.as<int32_t>(), nullptr, n, set->k, &seg_start));
+    FLX_CHECK(flx_screen_segment_table(ctx, d_len.as<int32_t>(), nullptr, n, set->k, &seg_start));
     hipLaunchKernelGGL(k_screenset_insert, dim3(set->blocks), dim3(kHashThreads), 0, st, (const uint8_t *)d_plane.p, (const uint64_t *)d_off.p,
                        (const int32_t *)d_len.p, (uint32_t)n, (const uint32_t *)seg_start, set->k, set->d_table, set->capacity - 1,
                        (unsigned long long *)set->d_count);
@@ -379,62 +338,26 @@ extern "C" uint64_t flx_screenset_size(const flx_screenset *set) { return set ? 
 extern "C" int flx_screenset_k(const flx_screenset *set) { return set ? set->k : 0; }
 extern "C" uint64_t flx_screenset_capacity(const flx_screenset *set) { return set ? set->capacity : 0; }
 
+int flx_screenset_launch_hits(flx_ctx *ctx, const flx_screenset *set, const void *d_plane, const void *d_offsets, const void *d_lengths,
+                              const void *d_order, uint64_t n_reads, const uint32_t *seg_start, uint32_t *d_hits) {
+    ctx->last_screen_filter = "hash";
+    hipLaunchKernelGGL(k_screen_hits_hash, dim3(set->blocks), dim3(kHashThreads), 0, ctx->stream, (const uint8_t *)d_plane, (const uint64_t *)d_offsets,
+                       (const int32_t *)d_lengths, (const uint32_t *)d_order, (uint32_t)n_reads, seg_start, set->k, (const uint64_t *)set->d_table,
+                       set->capacity - 1, d_hits);
+    FLX_HIP(ctx, hipGetLastError());
+    return FLX_OK;
+}
+
 extern "C" int flx_screenset_hits_dev(flx_ctx *ctx, const flx_screenset *set, const void *d_plane, uint64_t plane_bytes, const void *d_offsets,
                                       const void *d_lengths, const void *d_order, uint64_t n_reads, uint32_t *d_hits) {
     if (!ctx) return FLX_ERR_INVALID;
-    FLX_CHECK(hits_checks(ctx, set, plane_bytes));
-    if (n_reads > 0xfffffffeull) return flx_fail(ctx, FLX_ERR_INVALID, "at most 2^32-2 reads per batch");
-    if (n_reads == 0) return FLX_OK;
-    if (!d_plane || !d_offsets || !d_lengths || !d_hits) return flx_fail(ctx, FLX_ERR_INVALID, "plane/offsets/lengths/hits must not be NULL");
-    if (plane_bytes / (uint64_t)kScreenSpan + n_reads > 0xffffffffull) return flx_fail(ctx, FLX_ERR_INVALID, "too many spans in one batch");
-    FLX_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->last_screen_filter = "hash";
-    flx_time_scope timed(ctx, "flx_screen");
-    FLX_HIP(ctx, hipMemsetAsync(d_hits, 0, n_reads * 4, ctx->stream));
-    uint32_t *seg_start = nullptr;
-    FLX_CHECK(segment_table(ctx, (const int32_t *)d_lengths, (const uint32_t *)d_order, n_reads, set->k, &seg_start));
-    hipLaunchKernelGGL(k_screen_hits_hash, dim3(set->blocks), dim3(kHashThreads), 0, ctx->stream, (const uint8_t *)d_plane, (const uint64_t *)d_offsets,
-                       (const int32_t *)d_lengths, (const uint32_t *)d_order, (uint32_t)n_reads, (const uint32_t *)seg_start, set->k,
-                       (const uint64_t *)set->d_table, set->capacity - 1, d_hits);
-    FLX_HIP(ctx, hipGetLastError());
-    timed.end();
-    return FLX_OK;
+    if (!set) return flx_fail(ctx, FLX_ERR_INVALID, "flx_screenset_hits: set must not be NULL");
+    return screen_hits_dev(ctx, flx_screen_ref{nullptr, set}, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n_reads, d_hits);
 }
 
 extern "C" int flx_screenset_hits(flx_ctx *ctx, const flx_screenset *set, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets,
                                   const int32_t *lengths, const uint32_t *order, uint64_t n_reads, uint32_t *hits) {
     if (!ctx) return FLX_ERR_INVALID;
-    FLX_CHECK(hits_checks(ctx, set, plane_bytes));
-    if (n_reads == 0) return FLX_OK;
-    if (!plane || !offsets || !lengths || !hits) return flx_fail(ctx, FLX_ERR_INVALID, "plane/offsets/lengths/hits must not be NULL");
-    for (uint64_t i = 0; i < n_reads; ++i) {
-        if (lengths[i] < 0 || (offsets[i] & 15) || offsets[i] + (((uint64_t)lengths[i] + 15) & ~15ull) > plane_bytes)
-            return flx_fail(ctx, FLX_ERR_INVALID, "read %llu: offset must be 16-byte aligned and inside the plane", (unsigned long long)i);
-    }
-    if (order) {  // a permutation: the kernel adds every span of every read exactly once
-        std::vector<uint8_t> seen(n_reads, 0);
-        for (uint64_t i = 0; i < n_reads; ++i) {
-            if (order[i] >= n_reads || seen[order[i]]) return flx_fail(ctx, FLX_ERR_INVALID, "order is not a permutation of the reads");
-            seen[order[i]] = 1;
-        }
-    }
-    FLX_HIP(ctx, hipSetDevice(ctx->device));
-    flx_dbuf d_plane, d_off, d_len, d_ord, d_hits;
-    FLX_CHECK(flx_dalloc(ctx, d_plane, plane_bytes ? plane_bytes : 16));
-    FLX_CHECK(flx_dalloc(ctx, d_off, n_reads * 8));
-    FLX_CHECK(flx_dalloc(ctx, d_len, n_reads * 4));
-    FLX_CHECK(flx_dalloc(ctx, d_hits, n_reads * 4));
-    if (plane_bytes) FLX_HIP(ctx, hipMemcpyAsync(d_plane.p, plane, plane_bytes, hipMemcpyHostToDevice, ctx->stream));
-    FLX_HIP(ctx, hipMemcpyAsync(d_off.p, offsets, n_reads * 8, hipMemcpyHostToDevice, ctx->stream));
-    FLX_HIP(ctx, hipMemcpyAsync(d_len.p, lengths, n_reads * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (order) {
-        FLX_CHECK(flx_dalloc(ctx, d_ord, n_reads * 4));
-        FLX_HIP(ctx, hipMemcpyAsync(d_ord.p, order, n_reads * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    // (a pattern no count can be: a kernel that wrote nothing must not hand back an earlier call's answers)
-    FLX_HIP(ctx, hipMemsetAsync(d_hits.p, 0xA5, n_reads * 4, ctx->stream));
-    FLX_CHECK(flx_screenset_hits_dev(ctx, set, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr, n_reads, d_hits.as<uint32_t>()));
-    FLX_HIP(ctx, hipMemcpyAsync(hits, d_hits.p, n_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return FLX_OK;
+    if (!set) return flx_fail(ctx, FLX_ERR_INVALID, "flx_screenset_hits: set must not be NULL");
+    return screen_hits_host(ctx, flx_screen_ref{nullptr, set}, plane, plane_bytes, offsets, lengths, order, n_reads, hits);
 }
