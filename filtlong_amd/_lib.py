@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "flx_adapters_create", "flx_adapters_destroy", "flx_adapters_patterns", "flx_adapter_cuts", "flx_adapter_cuts_dev",
     "flx_score_batch_adapters", "flx_score_batch_adapters_dev", "flx_pipeline_set_adapters", "flx_pipeline_adapters",
     "flx_adapters_set_split", "flx_adapters_split", "flx_adapter_marks", "flx_adapter_marks_dev",
+    "flx_complexity_window", "flx_complexity_span", "flx_complexity_bad", "flx_complexity_bad_dev", "flx_pipeline_set_complexity",
+    "flx_pipeline_complexity",
 ]
 
 
@@ -227,6 +229,15 @@ def load():
     L.flx_screen_hits_dev.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp]
     L.flx_pipeline_set_screen.argtypes = [vp, vp, dbl]
     L.flx_pipeline_screen.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    if hasattr(L, "flx_complexity_bad") or not os.environ.get("FLX_LIB_PATH"):  # (an experiment build of an older tree may lack them)
+        L.flx_complexity_window.argtypes = []
+        L.flx_complexity_window.restype = C.c_uint32
+        L.flx_complexity_span.argtypes = []
+        L.flx_complexity_span.restype = C.c_uint32
+        L.flx_complexity_bad.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.c_int, vp]
+        L.flx_complexity_bad_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.c_int, vp]
+        L.flx_pipeline_set_complexity.argtypes = [vp, dbl, C.c_int]
+        L.flx_pipeline_complexity.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.flx_last_screen_filter.argtypes = [vp]
     L.flx_last_screen_filter.restype = C.c_char_p
     if hasattr(L, "flx_screenset_create") or not os.environ.get("FLX_LIB_PATH"):  # (an experiment build of an older tree may lack them)

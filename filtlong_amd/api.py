@@ -180,14 +180,16 @@ class Context:
 
     # ---- seam 2, streaming ----------------------------------------------------------------------
     def score_stream(self, chunks, params, kmers=None, chunk_bytes=1 << 20, chunk_reads=1 << 12, grow=False, split_window_q=None,
-                     exclude=None, exclude_percent=10.0, adapters=None):
+                     exclude=None, exclude_percent=10.0, adapters=None, max_low_complexity=None, low_complexity_score=20):
         """flx_pipeline_*: `chunks` is an iterable of lists of byte strings (Phred mode: qualities, k-mer mode: sequences).
         Every chunk is packed into the pipeline's pinned buffer and submitted; returns the same dict as score_reads for
         all reads in submission order.  grow: enlarge the slots (flx_pipeline_reserve) for a chunk that does not fit.
         split_window_q: flx_pipeline_set_qsplit before the first chunk.  exclude (a Kmers filled with add_screen_fasta, or a
         ScreenSet): flx_pipeline_set_screen / flx_pipeline_set_screenset with exclude_percent; in Phred mode every chunk is then a PAIR (qualities, sequences) of lists, and
         the result also has "hits" and "excluded".  adapters (an Adapters, Phred mode): flx_pipeline_set_adapters; every chunk is
-        such a PAIR as well and the result also has "adapter_keys" (n x 2: head, tail)."""
+        such a PAIR as well and the result also has "adapter_keys" (n x 2: head, tail).  max_low_complexity (a percentage):
+        flx_pipeline_set_complexity with low_complexity_score; in Phred mode every chunk is such a PAIR too, and the result also has
+        "bad_windows" and "low_complexity"."""
         L = self.L
         pipe = C.c_void_p()
         self._check(L.flx_pipeline_create(self.h, kmers.h if kmers is not None else None, C.byref(params), chunk_bytes,
@@ -195,12 +197,14 @@ class Context:
         try:
             if split_window_q is not None:
                 self._check(L.flx_pipeline_set_qsplit(pipe, float(split_window_q)))
-            two_planes = (exclude is not None or adapters is not None) and (kmers is None or kmers.empty())
+            two_planes = (exclude is not None or adapters is not None or max_low_complexity is not None) and (kmers is None or kmers.empty())
             if exclude is not None:
                 set_screen = L.flx_pipeline_set_screenset if isinstance(exclude, ScreenSet) else L.flx_pipeline_set_screen
                 self._check(set_screen(pipe, exclude.h, float(exclude_percent)))
             if adapters is not None:
                 self._check(L.flx_pipeline_set_adapters(pipe, adapters.h))
+            if max_low_complexity is not None:
+                self._check(L.flx_pipeline_set_complexity(pipe, float(max_low_complexity), int(low_complexity_score)))
             for strings in chunks:
                 seqs = None
                 if two_planes:
@@ -250,6 +254,10 @@ class Context:
                 hp, ep = C.c_void_p(), C.c_void_p()
                 self._check(L.flx_pipeline_screen(pipe, C.byref(hp), C.byref(ep)))
                 out["hits"], out["excluded"] = take(hp, np.uint32, n), take(ep, np.uint8, n)
+            if max_low_complexity is not None:
+                bp, fp = C.c_void_p(), C.c_void_p()
+                self._check(L.flx_pipeline_complexity(pipe, C.byref(bp), C.byref(fp)))
+                out["bad_windows"], out["low_complexity"] = take(bp, np.uint32, n), take(fp, np.uint8, n)
             if adapters is not None:
                 kp = C.c_void_p()
                 self._check(L.flx_pipeline_adapters(pipe, C.byref(kp)))
@@ -429,6 +437,26 @@ class Context:
     def screen_hits_dev(self, kmers, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_hits):
         self._check(self.L.flx_screen_hits_dev(self.h, kmers.h, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, d_hits))
 
+    # ---- the low-complexity filter ---------------------------------------------------------------
+    def complexity_bad(self, plane, offsets, lengths, score=20, order=None):
+        """flx_complexity_bad: for every read of the SEQUENCE plane the number of its 64-base windows whose triplet-pair score S has
+        10 S > score * 61 (windows with a byte outside ACGTacgt are never bad).  uint32 array in input order."""
+        n = len(lengths)
+        plane = np.ascontiguousarray(plane, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        out = np.full(max(n, 1), 0xA5A5A5A5, dtype=np.uint32)
+        ordp = None
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.uint32)
+            ordp = order.ctypes.data
+        self._check(self.L.flx_complexity_bad(self.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data, ordp, n,
+                                              int(score), out.ctypes.data))
+        return out[:n]
+
+    def complexity_bad_dev(self, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, score, d_bad):
+        self._check(self.L.flx_complexity_bad_dev(self.h, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, int(score), d_bad))
+
     # ---- adapter trimming -------------------------------------------------------------------------
     def adapter_cuts(self, plane, offsets, lengths, adapters, order=None):
         """flx_adapter_cuts: for every read of the SEQUENCE plane its two keys, (jbest << 8) | pattern of the adapter occurrence that
@@ -607,6 +635,26 @@ def screen_excluded(hits, lengths, percent):
     for i, (h, n) in enumerate(zip(hits, lengths)):
         w = max(0, int(n) - 15)
         out[i] = 1 if w > 0 and (int(h) << 32) >= t * w else 0
+    return out
+
+
+def complexity_window():
+    """Bases of a window of the low-complexity filter: 64 (flx_complexity_window; no device needed)."""
+    return int(_lib.load().flx_complexity_window())
+
+
+def complexity_span():
+    """Window positions per work item of the low-complexity kernel (flx_complexity_span; no device needed)."""
+    return int(_lib.load().flx_complexity_span())
+
+
+def complexity_flagged(bad, lengths, percent):
+    """The decision of --max_low_complexity on integers: windows > 0 and (bad << 32) >= t * windows, windows = max(0, L - 63)."""
+    t = screen_threshold(percent)
+    out = np.zeros(len(bad), dtype=np.uint8)
+    for i, (b, n) in enumerate(zip(bad, lengths)):
+        w = max(0, int(n) - 63)
+        out[i] = 1 if w > 0 and (int(b) << 32) >= t * w else 0
     return out
 
 

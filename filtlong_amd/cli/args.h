@@ -46,6 +46,8 @@ struct Args {
     bool exclude_k_set = false; long long exclude_k = 16;  // --exclude_k K: ... of their K-mers, 16 <= K <= 31; above 16 the set is a hash table of canonical keys (-1: not an integer)
     bool adapter_split_errors_set = false; long long adapter_split_errors = 10;  // --adapter_split_errors E2: edits a pattern may carry inside a read, percent (-1: not an integer)
     bool exclude_percent_set = false; double exclude_percent = 10.0; std::string exclude_percent_text = "10";  // --exclude_percent P: ... with at least P % of their 16-mers in it
+    bool max_low_complexity_set = false; double max_low_complexity = 0;  // not a reference flag: --max_low_complexity P drops reads with at least P % of their 64-base windows simple repeats
+    bool low_complexity_score_set = false; long long low_complexity_score = 20;  // --low_complexity_score T: a window is a simple repeat above T tenths on sdust's scale (-1: not an integer)
 };
 enum ParsingResult { GOOD, BAD, HELP, VERSION };
 
@@ -126,8 +128,8 @@ static long long whole_number(const std::string &value) {
 // reference reads the width out of an untouched `struct winsize` — 0 in practice: the description comes out one word per line and,
 // the other widths being unsigned differences that wrap around, nothing else is wrapped at all.  Both cases are restated here.
 // (--gpus, --gzip, --bam, --report, --split_window_q, --exclude, --exclude_percent, --exclude_k, --trim_adapters, --adapter_errors,
-// --adapter_window, --split_adapters and --adapter_split_errors, this binary's flags of its own, are documented in README.md: the
-// menu is the reference's.)
+// --adapter_window, --split_adapters, --adapter_split_errors, --max_low_complexity and --low_complexity_score, this binary's flags of
+// its own, are documented in README.md: the menu is the reference's.)
 static std::vector<std::string> help_wrap(const std::string &in, size_t width, size_t first = 0) {  // src/args.h:94-149
     std::vector<std::string> out;
     size_t cur = first ? first : width, linesize = 0;
@@ -305,6 +307,8 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
             else if (flag == "adapter_window") { a.adapter_window = whole_number(need("adapter_window")); a.adapter_window_set = true; }
             else if (flag == "split_adapters") a.split_adapters = true;
             else if (flag == "adapter_split_errors") { a.adapter_split_errors = whole_number(need("adapter_split_errors")); a.adapter_split_errors_set = true; }
+            else if (flag == "max_low_complexity") { a.max_low_complexity = read_double("float", need("max_low_complexity")); a.max_low_complexity_set = true; }
+            else if (flag == "low_complexity_score") { a.low_complexity_score = whole_number(need("low_complexity_score")); a.low_complexity_score_set = true; }
             else throw ParseError("Error: flag could not be matched: " + flag);
         }
     } catch (const ParseError &e) {
@@ -329,7 +333,7 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     for (auto &f : files)
         if (!file_exists(f)) { std::cerr << "Error: cannot find file: " << f << "\n"; return BAD; }
     if (!a.trim && !a.split_set && !a.target_bases_set && !a.keep_percent_set && !a.min_length_set && !a.max_length_set &&
-        !a.min_mean_q_set && !a.min_window_q_set && !a.split_window_q_set && !a.exclude_set && !a.trim_adapters_set) {
+        !a.min_mean_q_set && !a.min_window_q_set && !a.split_window_q_set && !a.exclude_set && !a.trim_adapters_set && !a.max_low_complexity_set) {
         std::cerr << "Error: no thresholds set, you must use one of the following options:\n";
         std::cerr << "target_bases, keep_percent, min_length, max_length, min_mean_q, min_window_q, trim, split\n";
         return BAD;
@@ -378,6 +382,12 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     if (a.exclude_k_set && (a.exclude_k < 16 || a.exclude_k > 31)) {
         std::cerr << "Error: the value for --exclude_k must be an integer between 16 and 31\n"; return BAD; }
     if (a.exclude_k_set && !a.exclude_set) { std::cerr << "Error: --exclude_k needs --exclude\n"; return BAD; }
+    // --max_low_complexity / --low_complexity_score: behind every check above
+    if (a.max_low_complexity_set && !(a.max_low_complexity > 0.0 && a.max_low_complexity <= 100.0)) {
+        std::cerr << "Error: the value for --max_low_complexity must be greater than 0 and at most 100\n"; return BAD; }
+    if (a.low_complexity_score_set && (a.low_complexity_score < 10 || a.low_complexity_score > 300)) {
+        std::cerr << "Error: the value for --low_complexity_score must be an integer between 10 and 300\n"; return BAD; }
+    if (a.low_complexity_score_set && !a.max_low_complexity_set) { std::cerr << "Error: --low_complexity_score needs --max_low_complexity\n"; return BAD; }
     return GOOD;
 }
 

@@ -70,14 +70,20 @@ static int exchange_totals(const Run &run, const Pass1 &p, const flx_scores &res
     if (run.screen_excluded)
         for (size_t i = 0; i < p.lengths.size(); ++i)
             if (run.screen_excluded[i]) { ++excluded_reads; excluded_bases += (uint64_t)p.lengths[i]; }
+    uint64_t lowc_reads = 0, lowc_bases = 0;  // --max_low_complexity: the input reads the filter took
+    if (run.complexity_flagged)
+        for (size_t i = 0; i < p.lengths.size(); ++i)
+            if (run.complexity_flagged[i]) { ++lowc_reads; lowc_bases += (uint64_t)p.lengths[i]; }
     uint64_t split_reads = 0;  // --split_adapters: the input reads that went on as two children or more
     if (args.split_adapters && res.child_offsets)
         for (size_t i = 0; i < p.lengths.size(); ++i)
             if (res.child_offsets[i + 1] - res.child_offsets[i] >= 2) ++split_reads;
     if (world > 1) {
-        std::vector<uint64_t> sums(2 * (size_t)world + 1 + (run.excluding() ? 2 : 0) + (args.split_adapters ? 1 : 0), 0);
+        const size_t lowc_at = 2 * (size_t)world + 1 + (run.excluding() ? 2 : 0);
+        std::vector<uint64_t> sums(lowc_at + (run.low_complexity() ? 2 : 0) + (args.split_adapters ? 1 : 0), 0);
         if (args.split_adapters) sums.back() = split_reads;
         if (run.excluding()) { sums[2 * (size_t)world + 1] = excluded_reads; sums[2 * (size_t)world + 2] = excluded_bases; }
+        if (run.low_complexity()) { sums[lowc_at] = lowc_reads; sums[lowc_at + 1] = lowc_bases; }
         sums[rank] = r2.reads.size();
         sums[world] = (uint64_t)after_total;
         sums[(size_t)world + 1 + rank] = r2.longest_name;  // (the --verbose table pads every name to the longest of ALL reads2, main.cpp:199-201)
@@ -86,6 +92,7 @@ static int exchange_totals(const Run &run, const Pass1 &p, const flx_scores &res
         for (int r = 0; r < world; ++r) { r2.n_total += sums[r]; r2.longest_name = std::max<size_t>(r2.longest_name, sums[(size_t)world + 1 + r]); }
         after_total = (long long)sums[world];
         if (run.excluding()) { excluded_reads = sums[2 * (size_t)world + 1]; excluded_bases = sums[2 * (size_t)world + 2]; }
+        if (run.low_complexity()) { lowc_reads = sums[lowc_at]; lowc_bases = sums[lowc_at + 1]; }
         if (args.split_adapters) split_reads = sums.back();
         if (args.verbose && rank == 0) {
             if (!print_verbose_parts(run, "vblocks")) return 1;
@@ -94,6 +101,8 @@ static int exchange_totals(const Run &run, const Pass1 &p, const flx_scores &res
     }
     if (run.excluding() && rank == 0)
         std::cerr << "  excluded by reference: " << int_to_string((long long)excluded_reads) << " reads (" << int_to_string((long long)excluded_bases) << " bp)\n";
+    if (run.low_complexity() && rank == 0)
+        std::cerr << "  low complexity: " << int_to_string((long long)lowc_reads) << " reads (" << int_to_string((long long)lowc_bases) << " bp)\n";
     if ((args.trim || args.split_set || args.split_window_q_set || args.trim_adapters_set) && rank == 0) {  // src/main.cpp:155-166 (--split_window_q: "after splitting")
         if (args.split_adapters) std::cerr << "  split at adapters: " << int_to_string((long long)split_reads) << " reads\n";
         if (args.trim_adapters_set) std::cerr << "  after adapter trimming: ";

@@ -117,7 +117,10 @@ struct Scorer {
         if (run.excluding() && run.set_pipeline_screen(pipe) != FLX_OK) return false;
         // --trim_adapters: the pipeline cuts the adapters off the read ends and returns at most one child per read (with --split_adapters
         // the object also splits at the adapters inside a read: any number of children); the same second plane
-        return !run.adapters || flx_pipeline_set_adapters(pipe, run.adapters) == FLX_OK;
+        if (run.adapters && flx_pipeline_set_adapters(pipe, run.adapters) != FLX_OK) return false;
+        // --max_low_complexity: the pipeline also counts the bad windows of every read, behind the screen; the same second plane
+        return !run.low_complexity() ||
+               flx_pipeline_set_complexity(pipe, run.args.max_low_complexity, (int)run.args.low_complexity_score) == FLX_OK;
     }
 
     // Pack records [lo, lo + cnt) of a batch chunk by chunk; their lengths are appended to `lengths`.
@@ -152,7 +155,7 @@ struct Scorer {
         }
         const int32_t *len = lengths.data() + base;
         const bool phred = run.kmers_empty;
-        const bool second_plane = phred && (run.excluding() || run.adapters != nullptr);
+        const bool second_plane = phred && (run.excluding() || run.adapters != nullptr || run.low_complexity());
         for (uint64_t at = 0; at < cnt;) {
             // the next chunk: as many records as fit the slot (flx_plane_layout's rule: 16-byte slots, 128-byte starts for long reads)
             uint64_t end = at, bytes = 0;
@@ -204,6 +207,7 @@ struct Scorer {
         if (flx_pipeline_finish(pipe, &res, &n_scored) != FLX_OK || n_scored != n) return report ? run.fail("scoring") : 1;
         if (run.excluding() && flx_pipeline_screen(pipe, &run.screen_hits, &run.screen_excluded) != FLX_OK) return report ? run.fail("scoring") : 1;
         if (run.adapters && flx_pipeline_adapters(pipe, &run.adapter_keys) != FLX_OK) return report ? run.fail("scoring") : 1;
+        if (run.low_complexity() && flx_pipeline_complexity(pipe, &run.complexity_bad, &run.complexity_flagged) != FLX_OK) return report ? run.fail("scoring") : 1;
         return kGoOn;
     }
 };

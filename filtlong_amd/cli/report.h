@@ -41,13 +41,17 @@ static std::string report_summary(const struct flx_summary &m) {
 static int summarise_for_report(const Run &run, const Pass1 &p, const flx_scores &res, const Reads2 &r2, Report &report) {
     if (!run.args.report_set) return kGoOn;
     const int global = run.world > 1;
-    struct flx_summary input, scored, kept, excluded;
+    struct flx_summary input, scored, kept, excluded, low_complexity;
     if (flx_summary(run.ctx, p.lengths.size(), p.lengths.data(), res.mean_q, res.window_q, nullptr, global, &input) != FLX_OK ||
         flx_summary(run.ctx, r2.len.size(), r2.len.data(), r2.mean.data(), r2.window.data(), nullptr, global, &scored) != FLX_OK ||
         flx_summary(run.ctx, r2.len.size(), r2.len.data(), r2.mean.data(), r2.window.data(), r2.pass.data(), global, &kept) != FLX_OK)
         return run.fail("report");
     // --exclude: a fourth summary, the input reads the screen took (a collective like the other three)
     if (run.excluding() && flx_summary(run.ctx, p.lengths.size(), p.lengths.data(), res.mean_q, res.window_q, run.screen_excluded, global, &excluded) != FLX_OK)
+        return run.fail("report");
+    // --max_low_complexity: one more, the input reads the filter took, behind the screen's
+    if (run.low_complexity() &&
+        flx_summary(run.ctx, p.lengths.size(), p.lengths.data(), res.mean_q, res.window_q, run.complexity_flagged, global, &low_complexity) != FLX_OK)
         return run.fail("report");
     if (run.rank > 0) return kGoOn;
     double edges[51];
@@ -60,7 +64,8 @@ static int summarise_for_report(const Run &run, const Pass1 &p, const flx_scores
         s += (k ? ", " : "") + std::string(buf);
     }
     s += "],\n \"input\": " + report_summary(input) + ",\n \"scored\": " + report_summary(scored) + ",\n \"kept\": " + report_summary(kept) +
-         (run.excluding() ? ",\n \"excluded\": " + report_summary(excluded) : std::string()) + "}\n";
+         (run.excluding() ? ",\n \"excluded\": " + report_summary(excluded) : std::string()) +
+         (run.low_complexity() ? ",\n \"low_complexity\": " + report_summary(low_complexity) : std::string()) + "}\n";
     return kGoOn;
 }
 

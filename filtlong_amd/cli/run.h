@@ -55,6 +55,9 @@ struct Run {
     }
     const uint32_t *screen_hits = nullptr;     // ... and, once the scores are in, every read's hits and whether it was excluded
     const uint8_t *screen_excluded = nullptr;  // (owned by the pipeline; this rank's reads in submission order)
+    bool low_complexity() const { return args.max_low_complexity_set; }  // --max_low_complexity: the pipeline also counts every read's bad windows
+    const uint32_t *complexity_bad = nullptr;  // ... and, once the scores are in, every read's bad windows and whether it was flagged
+    const uint8_t *complexity_flagged = nullptr;  // (owned by the pipeline; this rank's reads in submission order)
     flx_adapters *adapters = nullptr;          // --trim_adapters: the patterns (reference.h: build_adapters) ...
     std::vector<std::string> adapter_names;    // ... the names of their sequences (pattern p belongs to sequence p / 2) ...
     const uint32_t *adapter_keys = nullptr;    // ... and, once the scores are in, every read's head and tail key (owned by the pipeline)

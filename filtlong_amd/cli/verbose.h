@@ -71,6 +71,9 @@ static void print_read_blocks(std::ostream &os, const Run &run, const Pass1 &p, 
         if (run.screen_hits)  // --exclude: behind the lines of the parent's block
             os << "          excluded = " << (run.screen_excluded[i] ? "yes" : "no") << " (" << run.screen_hits[i] << " of "
                << (lengths[i] >= run.exclude_k ? lengths[i] - run.exclude_k + 1 : 0) << " " << run.exclude_k << "-mers)\n";
+        if (run.complexity_bad)  // --max_low_complexity: behind the excluded line, if any
+            os << "          low complexity = " << (run.complexity_flagged[i] ? "yes" : "no") << " (" << run.complexity_bad[i] << " of "
+               << (lengths[i] >= 64 ? lengths[i] - 63 : 0) << " windows)\n";
         if (a != b) {
             for (uint64_t k = a; k < b; ++k) {
                 os << "\n" << rname << "_" << c_ranges[2 * k] + 1 << "-" << c_ranges[2 * k + 1] << "\n";

@@ -13,6 +13,7 @@
 #include <mutex>
 #include <thread>
 
+#include "complexity_internal.h"
 #include "screen_internal.h"
 
 // adapters.hip: flx_score_batch_adapters_dev that also leaves the keys [2 n] in d_keys (NULL: in a workspace of its own)
@@ -37,6 +38,8 @@ struct Slot {
     uint32_t *d_hits = nullptr;  // with a screen only
     uint8_t *d_excl = nullptr;
     uint32_t *d_keys = nullptr;  // with adapters only: [2 n]
+    uint32_t *d_bad = nullptr;   // with the low-complexity filter only
+    uint8_t *d_lowc = nullptr;
     hipEvent_t copied = nullptr;
     uint64_t n = 0, plane_bytes = 0;
     bool busy = false;  // submitted, not yet scored
@@ -52,6 +55,9 @@ struct flx_pipeline {
     double qsplit_q = 0;
     flx_screen_ref screen;   // flx_pipeline_set_screen / flx_pipeline_set_screenset: reads that match this set fail ...
     uint64_t screen_t = 0;   // ... with more than this share of their windows (screen.h: threshold)
+    bool complexity = false;  // flx_pipeline_set_complexity: reads whose windows are mostly simple repeats fail
+    uint64_t complexity_t = 0;
+    int complexity_score = 0;
     flx_adapters *adapters = nullptr;         // flx_pipeline_set_adapters: Phred mode, adapters cut off the read ends
     int planes = 1;          // 2: a Phred-mode pipeline with a screen or adapters — qualities, then sequences, plane_bytes each
     bool submitted = false;  // a chunk has been submitted
@@ -81,6 +87,8 @@ struct flx_pipeline {
     std::vector<uint64_t> child_offsets;  // global CSR: [n + 1]
     std::vector<uint32_t> hits;           // with a screen: 16-mers of every read in the set, and who was excluded
     std::vector<uint8_t> excluded;
+    std::vector<uint32_t> bad_windows;    // with the low-complexity filter: bad windows of every read, and who was flagged
+    std::vector<uint8_t> low_complexity;
     std::vector<uint32_t> adapter_keys;   // with adapters: head and tail key of every read
     double h2d_s = 0, score_s = 0;
 };
@@ -109,6 +117,10 @@ int alloc_slot(flx_pipeline *p, Slot &s) {
         FLX_HIP(ctx, hipMalloc((void **)&s.d_excl, nr));
     }
     if (p->adapters) FLX_HIP(ctx, hipMalloc((void **)&s.d_keys, nr * 8 + 8));
+    if (p->complexity) {
+        FLX_HIP(ctx, hipMalloc((void **)&s.d_bad, nr * 4));
+        FLX_HIP(ctx, hipMalloc((void **)&s.d_lowc, nr));
+    }
     FLX_HIP(ctx, hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
     return FLX_OK;
 }
@@ -117,7 +129,7 @@ void free_slot(Slot &s) {
     if (s.h_plane) (void)hipHostFree(s.h_plane);
     if (s.h_off) (void)hipHostFree(s.h_off);
     for (void *d : {(void *)s.d_plane, (void *)s.d_off, (void *)s.d_mean, (void *)s.d_win, (void *)s.d_pass, (void *)s.d_first,
-                    (void *)s.d_last, (void *)s.d_coff, (void *)s.d_hits, (void *)s.d_excl, (void *)s.d_keys})
+                    (void *)s.d_last, (void *)s.d_coff, (void *)s.d_hits, (void *)s.d_excl, (void *)s.d_keys, (void *)s.d_bad, (void *)s.d_lowc})
         if (d) (void)hipFree(d);
     if (s.copied) (void)hipEventDestroy(s.copied);
     s = Slot();
@@ -171,6 +183,11 @@ int score_slot(flx_pipeline *p, Slot &s) {
         FLX_CHECK(flx_screen_apply_dev(ctx, n, s.d_len, s.d_hits, p->screen_t, p->screen.k(), s.d_pass, want_children ? s.d_coff : nullptr,
                                        want_children ? p->d_cpass : nullptr, s.d_excl));
     }
+    if (p->complexity && n) {  // behind the screen, on the same stream
+        FLX_CHECK(flx_complexity_bad_dev(ctx, d_seq, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, p->complexity_score, s.d_bad));
+        FLX_CHECK(flx_complexity_apply_dev(ctx, n, s.d_len, s.d_bad, p->complexity_t, s.d_pass, want_children ? s.d_coff : nullptr,
+                                           want_children ? p->d_cpass : nullptr, s.d_lowc));
+    }
     const size_t at = p->mean_q.size();
     p->mean_q.resize(at + n); p->window_q.resize(at + n); p->passed.resize(at + n);
     p->first.resize(at + n); p->last.resize(at + n);
@@ -187,6 +204,13 @@ int score_slot(flx_pipeline *p, Slot &s) {
         if (n) {
             FLX_HIP(ctx, hipMemcpyAsync(&p->hits[at], s.d_hits, n * 4, hipMemcpyDeviceToHost, st));
             FLX_HIP(ctx, hipMemcpyAsync(&p->excluded[at], s.d_excl, n, hipMemcpyDeviceToHost, st));
+        }
+    }
+    if (p->complexity) {
+        p->bad_windows.resize(at + n); p->low_complexity.resize(at + n);
+        if (n) {
+            FLX_HIP(ctx, hipMemcpyAsync(&p->bad_windows[at], s.d_bad, n * 4, hipMemcpyDeviceToHost, st));
+            FLX_HIP(ctx, hipMemcpyAsync(&p->low_complexity[at], s.d_lowc, n, hipMemcpyDeviceToHost, st));
         }
     }
     if (p->adapters) {
@@ -345,6 +369,31 @@ extern "C" int flx_pipeline_set_adapters(flx_pipeline *p, flx_adapters *adapters
     p->adapters = adapters;
     p->planes = 2;  // (with a screen as well there is still ONE sequence plane)
     return realloc_slots(p);
+}
+
+extern "C" int flx_pipeline_set_complexity(flx_pipeline *p, double percent, int score_t) {
+    if (!p) return FLX_ERR_INVALID;
+    flx_ctx *ctx = p->ctx;
+    if (p->submitted || p->handed_out) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_complexity after flx_pipeline_next_buffer / flx_pipeline_submit");
+    uint64_t t = 0;
+    if (flx_screen_threshold(percent, &t) != FLX_OK) return flx_fail(ctx, FLX_ERR_INVALID, "max_low_complexity must be greater than 0 and at most 100");
+    if (!complexity::score_valid(score_t)) return flx_fail(ctx, FLX_ERR_INVALID, "low_complexity_score must be an integer between 10 and 300");
+    FLX_HIP(ctx, hipSetDevice(ctx->device));
+    p->complexity = true;
+    p->complexity_t = t;
+    p->complexity_score = score_t;
+    p->planes = p->set && flx_kmerset_size(p->set) > 0 ? 1 : 2;  // (Phred mode: room for the sequences; one plane of them whoever else reads it)
+    return realloc_slots(p);
+}
+
+extern "C" int flx_pipeline_complexity(flx_pipeline *p, const uint32_t **bad, const uint8_t **flagged) {
+    if (!p) return FLX_ERR_INVALID;
+    if (!p->complexity) return flx_fail(p->ctx, FLX_ERR_STATE, "flx_pipeline_complexity on a pipeline without the low-complexity filter");
+    std::unique_lock<std::mutex> lk(p->mu);
+    if (!p->queue.empty()) return flx_fail(p->ctx, FLX_ERR_STATE, "flx_pipeline_complexity before flx_pipeline_finish");
+    if (bad) *bad = p->bad_windows.data();
+    if (flagged) *flagged = p->low_complexity.data();
+    return FLX_OK;
 }
 
 extern "C" int flx_pipeline_adapters(flx_pipeline *p, const uint32_t **keys) {

@@ -43,13 +43,14 @@ using screen_walk::valid4;
 constexpr int kScreenThreads = 1024;  // 16 waves: with the 128 KiB table one workgroup per CU
 constexpr int kPre10Words = 1 << 15;  // 4^10 bits
 
-__global__ void __launch_bounds__(256) k_screen_segments(const int32_t *lengths, const uint32_t *order, uint64_t n_reads, int k, uint32_t *counts) {
+__global__ void __launch_bounds__(256) k_screen_segments(const int32_t *lengths, const uint32_t *order, uint64_t n_reads, int k, uint32_t span,
+                                                         uint32_t *counts) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r > n_reads) return;
     uint32_t c = 0;
     if (r < n_reads) {
         const uint32_t read = order ? order[r] : (uint32_t)r;
-        c = (screenk::windows_of(lengths[read], k) + (uint32_t)kScreenSpan - 1u) / (uint32_t)kScreenSpan;
+        c = (screenk::windows_of(lengths[read], k) + span - 1u) / span;
     }
     counts[r] = c;  // counts[n_reads] = 0: its scanned value is the number of spans
 }
@@ -174,15 +175,15 @@ __global__ void __launch_bounds__(256) k_screen_apply(uint64_t n_reads, const in
 }  // namespace
 
 // the spans of every read in processing order for windows of k bases, counts[0 .. n] (the last is 0), and their exclusive scan: no
-// host round trip in front of a walk (screen_hits_dev below, flx_screenset_add)
-int flx_screen_segment_table(flx_ctx *ctx, const int32_t *d_lengths, const uint32_t *d_order, uint64_t n, int k, uint32_t **seg_start) {
+// host round trip in front of a walk (screen_hits_dev below, flx_screenset_add; complexity.hip with spans of its own)
+int flx_screen_segment_table(flx_ctx *ctx, const int32_t *d_lengths, const uint32_t *d_order, uint64_t n, int k, uint32_t **seg_start, uint32_t span) {
     const size_t table = ((n + 1) * 4 + 255) & ~(size_t)255;
     const size_t scan_ws = ((n + 1) / 2048 + 4096) * 8;
     void *scr;
     FLX_CHECK(flx_scratch(ctx, 2 * table + scan_ws, &scr));
     uint32_t *counts = (uint32_t *)scr;
     *seg_start = (uint32_t *)((char *)scr + table);
-    hipLaunchKernelGGL(k_screen_segments, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, ctx->stream, d_lengths, d_order, n, k, counts);
+    hipLaunchKernelGGL(k_screen_segments, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, ctx->stream, d_lengths, d_order, n, k, span, counts);
     FLX_HIP(ctx, hipGetLastError());
     return flx_exclusive_scan_u32(ctx, n + 1, counts, *seg_start, (char *)scr + 2 * table, scan_ws);
 }

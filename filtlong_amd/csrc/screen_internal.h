@@ -4,6 +4,7 @@
 
 #include "flx_internal.h"
 #include "kmerset.h"
+#include "screen.h"
 
 bool flx_screenset_is_final(const flx_screenset *set);  // screen_hash.hip
 
@@ -19,8 +20,10 @@ struct flx_screen_ref {
 
 // screen.hip -------------------------------------------------------------------------------------
 // The segment table of a walk over windows of k bases: the spans of every read in processing order, scanned.  counts [n + 1] |
-// seg_start [n + 1] | the scan's block sums, in the context's scratch; seg_start is filled on the context's stream.
-int flx_screen_segment_table(flx_ctx *ctx, const int32_t *d_lengths, const uint32_t *d_order, uint64_t n, int k, uint32_t **seg_start);
+// seg_start [n + 1] | the scan's block sums, in the context's scratch; seg_start is filled on the context's stream.  A span is `span`
+// window start positions (the screen's kScreenSpan unless the walk has its own: complexity.hip).
+int flx_screen_segment_table(flx_ctx *ctx, const int32_t *d_lengths, const uint32_t *d_order, uint64_t n, int k, uint32_t **seg_start,
+                             uint32_t span = (uint32_t)screen::kScreenSpan);
 // flx_screen_hits_dev / flx_screenset_hits_dev, and their host-array forms, behind the check of their own set's NULL
 int screen_hits_dev(flx_ctx *ctx, flx_screen_ref ref, const void *d_plane, uint64_t plane_bytes, const void *d_offsets, const void *d_lengths,
                     const void *d_order, uint64_t n_reads, uint32_t *d_hits);

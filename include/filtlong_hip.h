@@ -259,6 +259,31 @@ int flx_screenset_hits_dev(flx_ctx *ctx, const flx_screenset *set, const void *d
                            const void *d_lengths, const void *d_order, uint64_t n_reads, uint32_t *d_hits);
 
 /* ------------------------------------------------------------------------------------------
+ * the low-complexity filter (added under version 4; the reference has no counterpart: its users run fastp -y, prinseq -lc_method dust
+ * or an entropy filter over the whole file in front of it): how many 64-base windows of every read are simple repeats.  Defined on
+ * integers, so every decomposition gives the same answer:
+ *   window     64 consecutive bases = 62 overlapping triplets; a read of L bases has windows = max(0, L - 63), one per start position
+ *   c_t        for a window whose 64 bytes are all in ACGTacgt (case folded; A 0, C 1, G 2, T 3): how often triplet kind t of the 64
+ *              kinds occurs among the window's 62 triplets
+ *   S          sum over t of c_t (c_t - 1) / 2, the pairs of equal triplets, 0 .. 1891: the score of DUST / sdust at one fixed
+ *              window length
+ *   bad window all 64 bytes in ACGTacgt AND 10 S > score_t * 61; score_t is an integer on sdust's scale of tenths, 10 .. 300
+ *              (20 is sdust's default).  Equality is not bad: at 20, S = 122 is good and S = 123 is bad.  A window with any other
+ *              byte is never bad.
+ *   flagged    iff windows > 0 and ((uint64_t)bad << 32) >= t * windows, t = flx_screen_threshold(percent): the screen's rule
+ * flx_complexity_bad(_dev): the arguments and checks of flx_screen_hits(_dev) without the set; bad has n_reads entries and is not
+ * accumulated across calls.  FLX_ERR_INVALID for score_t outside 10..300.  The work item is a span of flx_complexity_span() window
+ * start positions of one read (a multiple of flx_complexity_window() = 64; host only: tests place lengths on its edges), every lane
+ * of a wave walking span / 64 of them from a fresh state.  Timed as "flx_complexity".
+ * ---------------------------------------------------------------------------------------- */
+uint32_t flx_complexity_window(void);
+uint32_t flx_complexity_span(void);
+int flx_complexity_bad(flx_ctx *ctx, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets, const int32_t *lengths,
+                       const uint32_t *order, uint64_t n_reads, int score_t, uint32_t *bad);
+int flx_complexity_bad_dev(flx_ctx *ctx, const void *d_plane, uint64_t plane_bytes, const void *d_offsets, const void *d_lengths,
+                           const void *d_order, uint64_t n_reads, int score_t, uint32_t *d_bad);
+
+/* ------------------------------------------------------------------------------------------
  * adapter trimming (added under version 4; the reference has no counterpart: its users run an adapter trimmer over the whole file
  * in front of it): known adapters are cut off the two ends of every read.  Defined on integers, so every decomposition gives the
  * same answer:
@@ -441,6 +466,16 @@ int flx_pipeline_set_screenset(flx_pipeline *p, const flx_screenset *exclude_set
  * valid after flx_pipeline_finish until the pipeline is destroyed. */
 int flx_pipeline_set_adapters(flx_pipeline *p, flx_adapters *adapters);
 int flx_pipeline_adapters(flx_pipeline *p, const uint32_t **keys);
+/* --max_low_complexity for a pipeline (added under version 4): every chunk also goes through flx_complexity_bad_dev, on the
+ * context's stream behind the scoring and behind the screen; a flagged read (above) is treated exactly like an excluded one: its pass
+ * flag and those of all its children are cleared on the device, and it stays an entry.  The state rules of flx_pipeline_set_screen:
+ * before the first flx_pipeline_next_buffer, FLX_ERR_STATE afterwards; FLX_ERR_INVALID unless 0 < percent <= 100 and 10 <= score_t
+ * <= 300.  In a Phred-mode pipeline the chunk carries the two planes exactly as a screen or adapters arrange them (with those as
+ * well there is still ONE sequence plane).  A screen and this filter may both be set; a read flagged by both shows in both.
+ * flx_pipeline_complexity: the bad windows and the flags (1 / 0) of all reads in submission order, host arrays owned by the
+ * pipeline, after flx_pipeline_finish. */
+int flx_pipeline_set_complexity(flx_pipeline *p, double percent, int score_t);
+int flx_pipeline_complexity(flx_pipeline *p, const uint32_t **bad, const uint8_t **flagged);
 int flx_pipeline_next_buffer(flx_pipeline *p, uint8_t **plane, uint64_t *capacity_bytes, uint64_t *capacity_reads);
 /* Grow both slots to at least this capacity (never shrinks; waits for the chunks in flight first).  For callers that learn
  * the longest read only while streaming.  Not between next_buffer and submit. */
