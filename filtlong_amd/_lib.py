@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "flx_adapters_create", "flx_adapters_destroy", "flx_adapters_patterns", "flx_adapter_cuts", "flx_adapter_cuts_dev",
     "flx_score_batch_adapters", "flx_score_batch_adapters_dev", "flx_pipeline_set_adapters", "flx_pipeline_adapters",
     "flx_adapters_set_split", "flx_adapters_split", "flx_adapter_marks", "flx_adapter_marks_dev",
+    "flx_adapters_set_overhang", "flx_adapters_overhang",
     "flx_complexity_window", "flx_complexity_span", "flx_complexity_bad", "flx_complexity_bad_dev", "flx_pipeline_set_complexity",
     "flx_pipeline_complexity",
 ]
@@ -278,3 +279,6 @@ def _declare_adapters(L):
         L.flx_adapters_split.argtypes = [vp]
         L.flx_adapter_marks.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp]
         L.flx_adapter_marks_dev.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp]
+    if hasattr(L, "flx_adapters_set_overhang") or not os.environ.get("FLX_LIB_PATH"):
+        L.flx_adapters_set_overhang.argtypes = [vp, i32]
+        L.flx_adapters_overhang.argtypes = [vp]

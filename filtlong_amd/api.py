@@ -864,9 +864,11 @@ class Adapters:
     """flx_adapters: the sequences of --trim_adapters (12 to 64 bases of ACGT each, at most 128), each with its reverse complement;
     errors: the edits a pattern may carry, percent of its length (0..40); window: the bases at either read end that are searched
     (1..1024).  split_errors (0..40, None: off): the adapters INSIDE the reads are searched as well, with that many edits percent, and
-    the reads are split there (flx_adapters_set_split).  Belongs to no context."""
+    the reads are split there (flx_adapters_set_split).  overhang (0..52, 0: off): an adapter that the read begins or ends inside is
+    found as well, with up to that many of its bases missing beyond the read's edge (flx_adapters_set_overhang).  Belongs to no
+    context."""
 
-    def __init__(self, seqs, errors=20, window=150, split_errors=None):
+    def __init__(self, seqs, errors=20, window=150, split_errors=None, overhang=0):
         seqs = [bytes(s) for s in seqs]
         n = len(seqs)
         lengths = np.array([len(s) for s in seqs], dtype=np.int64)
@@ -884,6 +886,21 @@ class Adapters:
         self.split_errors = None
         if split_errors is not None:
             self.set_split(split_errors)
+        self._overhang = 0
+        if overhang != 0:  # (0 is the state after flx_adapters_create)
+            self.overhang = overhang
+
+    @property
+    def overhang(self):
+        """flx_adapters_overhang: the adapter bases that may lie beyond a read's edge, 0: the whole adapter must be in the read"""
+        return self._overhang
+
+    @overhang.setter
+    def overhang(self, overhang):
+        """flx_adapters_set_overhang: 0..52; the devices that hold the patterns get them again with their next call"""
+        if self.L.flx_adapters_set_overhang(self.h, int(overhang)) != _lib.FLX_OK:
+            raise FlxError(1, "flx_adapters_set_overhang: overhang 0..52")
+        self._overhang = int(self.L.flx_adapters_overhang(self.h))
 
     def set_split(self, split_errors):
         """flx_adapters_set_split: 0..40 turns the search inside the reads on, None (or -1) off"""

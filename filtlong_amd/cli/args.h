@@ -48,6 +48,7 @@ struct Args {
     bool exclude_percent_set = false; double exclude_percent = 10.0; std::string exclude_percent_text = "10";  // --exclude_percent P: ... with at least P % of their 16-mers in it
     bool max_low_complexity_set = false; double max_low_complexity = 0;  // not a reference flag: --max_low_complexity P drops reads with at least P % of their 64-base windows simple repeats
     bool low_complexity_score_set = false; long long low_complexity_score = 20;  // --low_complexity_score T: a window is a simple repeat above T tenths on sdust's scale (-1: not an integer)
+    bool adapter_overhang_set = false; long long adapter_overhang = 0;  // --adapter_overhang O: adapter bases that may lie beyond a read's edge, 0: off (-1: not an integer)
 };
 enum ParsingResult { GOOD, BAD, HELP, VERSION };
 
@@ -114,7 +115,7 @@ static long long read_ll(const std::string &name, const std::string &value, long
     return v;
 }
 
-// --adapter_errors / --adapter_window / --adapter_split_errors: a decimal integer of at most six digits, or -1 (the range check then names the flag)
+// --adapter_errors / --adapter_window / --adapter_split_errors / --adapter_overhang: a decimal integer of at most six digits, or -1 (the range check then names the flag)
 static long long whole_number(const std::string &value) {
     if (value.empty() || value.size() > 6) return -1;
     for (char c : value)
@@ -128,8 +129,8 @@ static long long whole_number(const std::string &value) {
 // reference reads the width out of an untouched `struct winsize` — 0 in practice: the description comes out one word per line and,
 // the other widths being unsigned differences that wrap around, nothing else is wrapped at all.  Both cases are restated here.
 // (--gpus, --gzip, --bam, --report, --split_window_q, --exclude, --exclude_percent, --exclude_k, --trim_adapters, --adapter_errors,
-// --adapter_window, --split_adapters, --adapter_split_errors, --max_low_complexity and --low_complexity_score, this binary's flags of
-// its own, are documented in README.md: the menu is the reference's.)
+// --adapter_window, --split_adapters, --adapter_split_errors, --max_low_complexity, --low_complexity_score and --adapter_overhang, this
+// binary's flags of its own, are documented in README.md: the menu is the reference's.)
 static std::vector<std::string> help_wrap(const std::string &in, size_t width, size_t first = 0) {  // src/args.h:94-149
     std::vector<std::string> out;
     size_t cur = first ? first : width, linesize = 0;
@@ -308,6 +309,7 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
             else if (flag == "split_adapters") a.split_adapters = true;
             else if (flag == "adapter_split_errors") { a.adapter_split_errors = whole_number(need("adapter_split_errors")); a.adapter_split_errors_set = true; }
             else if (flag == "max_low_complexity") { a.max_low_complexity = read_double("float", need("max_low_complexity")); a.max_low_complexity_set = true; }
+            else if (flag == "adapter_overhang") { a.adapter_overhang = whole_number(need("adapter_overhang")); a.adapter_overhang_set = true; }
             else if (flag == "low_complexity_score") { a.low_complexity_score = whole_number(need("low_complexity_score")); a.low_complexity_score_set = true; }
             else throw ParseError("Error: flag could not be matched: " + flag);
         }
@@ -388,6 +390,10 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     if (a.low_complexity_score_set && (a.low_complexity_score < 10 || a.low_complexity_score > 300)) {
         std::cerr << "Error: the value for --low_complexity_score must be an integer between 10 and 300\n"; return BAD; }
     if (a.low_complexity_score_set && !a.max_low_complexity_set) { std::cerr << "Error: --low_complexity_score needs --max_low_complexity\n"; return BAD; }
+    // --adapter_overhang: behind every check above
+    if (a.adapter_overhang_set && (a.adapter_overhang < 0 || a.adapter_overhang > 52)) {
+        std::cerr << "Error: the value for --adapter_overhang must be an integer between 0 and 52\n"; return BAD; }
+    if (a.adapter_overhang_set && !a.trim_adapters_set) { std::cerr << "Error: --adapter_overhang needs --trim_adapters\n"; return BAD; }
     return GOOD;
 }
 

@@ -193,7 +193,9 @@ static int build_adapters(Run &run) {
     };
     for_each_record(args.trim_adapters, take, [] { return true; });
     const size_t count = offsets.size();
-    std::cerr << "  " << int_to_string((long long)count) << " " << (count == 1 ? "sequence" : "sequences") << "\n\n";
+    std::cerr << "  " << int_to_string((long long)count) << " " << (count == 1 ? "sequence" : "sequences") << "\n";
+    if (args.adapter_overhang > 0) std::cerr << "  overhang: up to " << args.adapter_overhang << " bases\n";  // --adapter_overhang (0 prints nothing)
+    std::cerr << "\n";
     for (size_t i = 0; i < count; ++i) {
         bool good = lengths[i] >= 12 && lengths[i] <= 64;
         for (int64_t k = 0; good && k < lengths[i]; ++k) good = strchr("ACGTacgt", (char)pack[offsets[i] + (uint64_t)k]) != nullptr && pack[offsets[i] + (uint64_t)k] != 0;
@@ -207,6 +209,11 @@ static int build_adapters(Run &run) {
     }
     // --split_adapters: the same patterns are also searched inside the reads
     if (args.split_adapters && flx_adapters_set_split(run.adapters, (int)args.adapter_split_errors) != FLX_OK) {
+        std::cerr << "Error: the adapters of " << args.trim_adapters << " were refused\n";
+        return 1;
+    }
+    // --adapter_overhang: adapters that a read begins or ends inside are found as well
+    if (args.adapter_overhang > 0 && flx_adapters_set_overhang(run.adapters, (int)args.adapter_overhang) != FLX_OK) {
         std::cerr << "Error: the adapters of " << args.trim_adapters << " were refused\n";
         return 1;
     }

@@ -12,7 +12,17 @@
 //   match         unit-cost edit distance of the whole pattern against any substring of the text: D[0][j] = 0, D[i][0] = i,
 //                 d(j) = D[m][j] for 1 <= j <= n; dmin = min d(j), jbest the LARGEST j with d(j) = dmin.  The pattern hits iff
 //                 n >= 1 and dmin <= k.
-//   cut           per end, key = max over the hitting patterns of (jbest << 8) | pattern, 0 without a hit; cut = key >> 8.
+//   overhang      O = --adapter_overhang, 0..52 (kMaxBases - kMinBases), 0: off.  A read that begins or ends INSIDE an adapter pays
+//                 one edit per missing base above; with O > 0 every (text, pattern) pair gets a second, ANCHORED walk.  Per pattern
+//                 O_p = min(O, m - 12) (12 pattern bases always remain) and k'_p = (m - O_p) * E / 100: the allowance of the
+//                 shortest truncated pattern, used for every truncation.  O_p = 0: no second walk.  The same texts, masks and
+//                 recurrence with other borders: D[i][0] = max(0, i - O_p) (the first O_p pattern bases may be missing at no cost)
+//                 and D[0][j] = j (the occurrence begins at the read's edge).  d'(j) = D[m][j], dmin' and jbest' as above; the
+//                 walk hits iff n >= 1 and dmin' <= k'_p.  d'(j) >= j - m, so no j above m + k'_p can be a hit and a walk may stop
+//                 after min(n, m + k'_p) columns.  At the tail the reversed pattern's first bases are the adapter's last: there
+//                 the overhang frees the END of the adapter.
+//   cut           per end, key = max over the hitting walks, free or anchored, of every pattern of (jbest << 8) | pattern, 0
+//                 without a hit; cut = key >> 8.  (The key with overhang is never below the key without: the maximum only gains.)
 //                 s = cut_head, e = L - cut_tail.  No hit at either end: no child, first = 0, last = L.  s < e: one child [s, e).
 //                 s >= e: no child, first = last = -1 — the read stays one failing entry, like a wholly bad read of qsplit.h.
 //
@@ -33,6 +43,8 @@
 //
 // The column walk is Myers' bit-vector form (J. ACM 46, 1999; the search variant, whose row 0 is all zero): m <= 64 is one word, bit
 // m - 1 of the horizontal deltas carries the change of D[m][j].  Bits above m - 1 hold whatever: carries only travel upwards.
+// The anchored walk is the same form with row 0 counting up: Pv = ~0 << O_p, Mv = 0, score = m - O_p at the start, and a one comes
+// in at the bottom of the horizontal plus-delta in every step.
 #pragma once
 
 #include <stdint.h>
@@ -66,9 +78,13 @@ struct Pattern {
     uint64_t peq_head[4];
     uint64_t peq_tail[4];
     uint32_t m, k;
+    uint32_t o, k_o;  // the anchored walk (set_overhang): O_p and k'_p; o = 0: none
 };
 
 ADAPTERS_FN uint32_t edits_allowed(uint32_t m, uint32_t errors_percent) { return m * errors_percent / 100u; }
+constexpr int kMaxOverhang = kMaxBases - kMinBases;  // O
+// O_p: the pattern bases that may be missing in front of the read's edge
+ADAPTERS_FN uint32_t overhang_of(uint32_t m, uint32_t overhang) { return overhang < m - (uint32_t)kMinBases ? overhang : m - (uint32_t)kMinBases; }
 
 // the column state of one (text, pattern) pair
 struct Column {
@@ -109,6 +125,37 @@ ADAPTERS_FN void column_step(Column *s, uint64_t eq, uint64_t top, int32_t j) {
         s->jbest = j;
     }
 }
+
+// The anchored walk: the first o pattern bases cost nothing (D[i][0] = max(0, i - o)), the text is taken from its first base
+// (D[0][j] = j).  o <= kMaxOverhang < 64.
+ADAPTERS_FN void column_start_anchored(Column *s, uint32_t m, uint32_t o) {
+    s->pv = ~0ull << o;
+    s->mv = 0;
+    s->score = (int32_t)(m - o);
+    s->dmin = 0x7fffffff;
+    s->jbest = 0;
+}
+
+ADAPTERS_FN void column_step_anchored(Column *s, uint64_t eq, uint64_t top, int32_t j) {
+    const uint64_t pv = s->pv, mv = s->mv;
+    const uint64_t xv = eq | mv;
+    const uint64_t xh = (((eq & pv) + pv) ^ pv) | eq;
+    uint64_t ph = mv | ~(xh | pv);
+    uint64_t mh = pv & xh;
+    s->score += (ph & top) ? 1 : 0;
+    s->score -= (mh & top) ? 1 : 0;
+    ph = (ph << 1) | 1ull;  // (row 0 counts up: D[0][j] - D[0][j - 1] = 1)
+    mh <<= 1;
+    s->pv = mh | ~(xv | ph);
+    s->mv = ph & xv;
+    if (s->score <= s->dmin) {
+        s->dmin = s->score;
+        s->jbest = j;
+    }
+}
+
+// the columns an anchored walk needs of a text of n bases
+ADAPTERS_FN int32_t anchored_columns(int32_t n, uint32_t m, uint32_t k_o) { return n < (int32_t)(m + k_o) ? n : (int32_t)(m + k_o); }
 
 ADAPTERS_FN uint64_t select_eq(const uint64_t peq[4], uint32_t code) {
     uint64_t eq = 0;
@@ -234,6 +281,16 @@ inline int64_t build(const uint8_t *bases, const uint64_t *offsets, const int64_
     return 0;
 }
 
+// --adapter_overhang: O_p and k'_p of every pattern; false for O outside 0..kMaxOverhang
+inline bool set_overhang(std::vector<Pattern> *patterns, int errors_percent, int overhang) {
+    if (overhang < 0 || overhang > kMaxOverhang) return false;
+    for (Pattern &p : *patterns) {
+        p.o = overhang_of(p.m, (uint32_t)overhang);
+        p.k_o = edits_allowed(p.m - p.o, (uint32_t)errors_percent);
+    }
+    return true;
+}
+
 // The serial walk for one end of one read: the kernel's oracle.  side 0: the head, 1: the tail.  Reads read[0, L) and nothing else.
 inline uint32_t end_key(const uint8_t *read, int64_t L, int side, int64_t W, const Pattern *patterns, uint32_t n_patterns) {
     const int64_t n = L < W ? L : W;
@@ -249,6 +306,17 @@ inline uint32_t end_key(const uint8_t *read, int64_t L, int side, int64_t W, con
             column_step(&col, select_eq(peq, code_of(c)), top, (int32_t)(j + 1));
         }
         if (n >= 1 && col.dmin <= (int32_t)pat.k) {
+            const uint32_t mine = ((uint32_t)col.jbest << 8) | p;
+            if (mine > key) key = mine;
+        }
+        if (pat.o == 0u) continue;
+        column_start_anchored(&col, pat.m, pat.o);
+        const int64_t cols = anchored_columns((int32_t)n, pat.m, pat.k_o);
+        for (int64_t j = 0; j < cols; ++j) {
+            const uint8_t c = side ? read[L - 1 - j] : read[j];
+            column_step_anchored(&col, select_eq(peq, code_of(c)), top, (int32_t)(j + 1));
+        }
+        if (n >= 1 && col.dmin <= (int32_t)pat.k_o) {
             const uint32_t mine = ((uint32_t)col.jbest << 8) | p;
             if (mine > key) key = mine;
         }

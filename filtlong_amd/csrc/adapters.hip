@@ -11,6 +11,11 @@
 //                    per base, no dynamic register indexing, no scratch.  The text comes out of LDS four bases a read (a wave's
 //                    lanes on one text read the same dword: a broadcast).  A pattern that hits writes (jbest << 8) | pattern
 //                    with one atomicMax into the end's key, zeroed before.
+//   --adapter_overhang  an object with O > 0 (flx_adapters_set_overhang) runs the second instantiation, k_adapter_cuts<true>: behind
+//                    its free walk a lane whose pattern has O_p > 0 walks the same staged text again from its first base, anchored
+//                    (adapters.h), with the same four masks, for min(n, m + k'_p) <= 89 columns, and its one atomicMax takes the
+//                    larger of the two candidates.  No LDS and no staging of its own, the same work-item layout.  An object with
+//                    O = 0 launches k_adapter_cuts<false>, which has no trace of the second walk.
 //   bounds           staging reads the bytes [offset, offset + L) of a read and no other; the keys of read r are 2 r and 2 r + 1.
 //   children         k_adapter_children turns the two keys into the child CSR's count, first and last (the rule: adapters.h);
 //                    k_adapter_emit writes the one range.  Everything behind that — the child plane, the children's scoring — is
@@ -45,6 +50,7 @@ struct CutArgs {
     uint32_t *keys;   // [n_ends], zero
 };
 
+template <bool kOverhang>
 __global__ void __launch_bounds__(kThreads) k_adapter_cuts(const CutArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_text[];  // [epb][stride]
     __shared__ int32_t s_n[kMaxEnds];                                  // bases of the text (0: nothing to do)
@@ -111,7 +117,35 @@ __global__ void __launch_bounds__(kThreads) k_adapter_cuts(const CutArgs a) {
                 }
             }
         }
-        if (col.dmin <= (int32_t)k) atomicMax(&a.keys[2ull * s_read[le] + side], ((uint32_t)col.jbest << 8) | p);
+        if constexpr (kOverhang) {
+            // the anchored walk: the same text from its first base, the first o pattern bases free
+            uint32_t cut = col.dmin <= (int32_t)k ? (uint32_t)col.jbest : 0u;  // (a hit has jbest >= 1)
+            const uint32_t o = pat->o;
+            if (o != 0u) {
+                const uint32_t k_o = pat->k_o;
+                const int32_t cols = adapters::anchored_columns(n, m, k_o);
+                adapters::column_start_anchored(&col, m, o);
+                for (int32_t j0 = 0; j0 < cols; j0 += 4) {
+                    const uint32_t four = text[j0 >> 2];
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        if (j0 + b < cols) {
+                            const uint32_t code = (four >> (8 * b)) & 0xffu;
+                            uint64_t eq = 0;
+                            eq = code == 0u ? peq0 : eq;
+                            eq = code == 1u ? peq1 : eq;
+                            eq = code == 2u ? peq2 : eq;
+                            eq = code == 3u ? peq3 : eq;
+                            adapters::column_step_anchored(&col, eq, top, j0 + b + 1);
+                        }
+                    }
+                }
+                if (col.dmin <= (int32_t)k_o && (uint32_t)col.jbest > cut) cut = (uint32_t)col.jbest;
+            }
+            if (cut) atomicMax(&a.keys[2ull * s_read[le] + side], (cut << 8) | p);
+        } else {
+            if (col.dmin <= (int32_t)k) atomicMax(&a.keys[2ull * s_read[le] + side], ((uint32_t)col.jbest << 8) | p);
+        }
     }
 }
 
@@ -147,20 +181,27 @@ __global__ void __launch_bounds__(256) k_adapter_emit(uint64_t n_reads, const ui
 // the adapters' pattern table on the context's device
 int flx_adapters_table(flx_ctx *ctx, flx_adapters *ad, const Pattern **out) {
     std::lock_guard<std::mutex> lk(ad->mu);
+    const size_t bytes = ad->patterns.size() * sizeof(Pattern);
     for (auto &d : ad->on_device)
-        if (d.first == ctx->device) {
-            *out = d.second;
+        if (d.device == ctx->device) {
+            if (d.version != ad->version) {
+                // flx_adapters_set_overhang since the upload: whatever still reads the old table finishes first
+                FLX_HIP(ctx, hipSetDevice(ctx->device));
+                FLX_HIP(ctx, hipDeviceSynchronize());
+                FLX_HIP(ctx, hipMemcpy(d.table, ad->patterns.data(), bytes, hipMemcpyHostToDevice));
+                d.version = ad->version;
+            }
+            *out = d.table;
             return FLX_OK;
         }
     Pattern *p = nullptr;
-    const size_t bytes = ad->patterns.size() * sizeof(Pattern);
     FLX_HIP(ctx, hipMalloc((void **)&p, bytes));
     const hipError_t e = hipMemcpy(p, ad->patterns.data(), bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipFree(p);
         return flx_fail(ctx, FLX_ERR_HIP, "the adapters' pattern table: %s", hipGetErrorString(e));
     }
-    ad->on_device.push_back({ctx->device, p});
+    ad->on_device.push_back({ctx->device, p, ad->version});
     *out = p;
     return FLX_OK;
 }
@@ -183,9 +224,21 @@ extern "C" int flx_adapters_create(const uint8_t *bases, const uint64_t *offsets
 
 extern "C" void flx_adapters_destroy(flx_adapters *ad) {
     if (!ad) return;
-    for (auto &d : ad->on_device) (void)hipFree(d.second);
+    for (auto &d : ad->on_device) (void)hipFree(d.table);
     delete ad;
 }
+
+extern "C" int flx_adapters_set_overhang(flx_adapters *ad, int overhang) {
+    if (!ad) return FLX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(ad->mu);
+    if (overhang == ad->overhang) return FLX_OK;
+    if (!adapters::set_overhang(&ad->patterns, ad->errors_percent, overhang)) return FLX_ERR_INVALID;
+    ad->overhang = overhang;
+    ++ad->version;  // a device that holds the table gets it again with its next call (flx_adapters_table)
+    return FLX_OK;
+}
+
+extern "C" int flx_adapters_overhang(const flx_adapters *ad) { return ad ? ad->overhang : 0; }
 
 extern "C" uint32_t flx_adapters_patterns(const flx_adapters *ad) { return ad ? (uint32_t)ad->patterns.size() : 0u; }
 
@@ -214,7 +267,10 @@ extern "C" int flx_adapter_cuts_dev(flx_ctx *ctx, flx_adapters *ad, const void *
     const uint64_t groups = (a.n_ends + a.epb - 1) / a.epb;  // below 2^32: n_ends is
     flx_time_scope timed(ctx, "flx_adapters");
     FLX_HIP(ctx, hipMemsetAsync(d_keys, 0, a.n_ends * 4, ctx->stream));
-    hipLaunchKernelGGL(k_adapter_cuts, dim3((unsigned)groups), dim3(kThreads), (size_t)a.epb * a.stride, ctx->stream, a);
+    if (ad->overhang > 0)
+        hipLaunchKernelGGL(k_adapter_cuts<true>, dim3((unsigned)groups), dim3(kThreads), (size_t)a.epb * a.stride, ctx->stream, a);
+    else
+        hipLaunchKernelGGL(k_adapter_cuts<false>, dim3((unsigned)groups), dim3(kThreads), (size_t)a.epb * a.stride, ctx->stream, a);
     FLX_HIP(ctx, hipGetLastError());
     timed.end();
     return FLX_OK;

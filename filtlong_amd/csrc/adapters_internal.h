@@ -11,8 +11,15 @@ struct flx_adapters {
     std::vector<adapters::Pattern> patterns;
     int errors_percent = 0, window = 0;
     int split_errors_percent = -1;  // flx_adapters_set_split: 0..40 the middle search is on, -1 off
+    int overhang = 0;               // flx_adapters_set_overhang: O, 0 off; o and k_o of every pattern follow it
+    uint64_t version = 0;           // of the patterns: counts the changes of `overhang`
     std::mutex mu;
-    std::vector<std::pair<int, adapters::Pattern *>> on_device;  // the pattern table, uploaded once per device that asks for it
+    struct OnDevice {
+        int device;
+        adapters::Pattern *table;
+        uint64_t version;  // of the patterns it holds
+    };
+    std::vector<OnDevice> on_device;  // the pattern table, uploaded once per device that asks for it and again after a change
 };
 
 // the adapters' pattern table on the context's device

@@ -336,6 +336,23 @@ int flx_score_batch_adapters_dev(flx_ctx *ctx, flx_adapters *adapters, const voi
  * flx_adapter_cuts; FLX_ERR_INVALID on an object with the search off.  Timed as "flx_adapter_marks". */
 int flx_adapters_set_split(flx_adapters *adapters, int split_errors_percent);
 int flx_adapters_split(const flx_adapters *adapters);
+/* Adapters that the read begins or ends INSIDE (added under version 4).  The ends rule above charges one edit for every adapter base
+ * the read lacks; with an overhang O > 0 every (text, pattern) pair gets a second, anchored walk:
+ *   allowance  per pattern of m bases O_p = min(O, m - 12) (12 pattern bases always remain) and k'_p = (m - O_p) * E / 100: the
+ *              allowance of the shortest truncated pattern, used for every truncation.  O_p = 0 (m = 12): no second walk.
+ *   walk       the same texts and the same recurrence with other borders: D[i][0] = max(0, i - O_p), the first O_p pattern bases may
+ *              be missing at no cost; D[0][j] = j, the occurrence begins at the read's edge.  d'(j) = D[m][j], 1 <= j <= n; dmin'
+ *              its minimum, jbest' the largest j with d'(j) = dmin'; a hit iff n >= 1 and dmin' <= k'_p.  (d'(j) >= j - m: no j
+ *              above m + k'_p can be a hit.)  At the tail the reversed pattern's first bases are the adapter's last: there the
+ *              overhang frees the END of the adapter.
+ *   keys       per read end, max over every hitting walk, free or anchored, of every pattern of (jbest << 8) | pattern: the key
+ *              with an overhang is never below the key without.  cut = key >> 8 and everything behind the keys are unchanged.
+ * flx_adapters_set_overhang: O from 0 to 52 (64 - 12); 0, the state after flx_adapters_create, is the ends rule alone in every byte
+ * and every launch; anything else is FLX_ERR_INVALID.  A device that already holds the object's patterns gets them again with the
+ * next call there.  flx_adapters_overhang: the value set.  flx_adapter_cuts(_dev), flx_score_batch_adapters(_dev) and a pipeline
+ * with flx_pipeline_set_adapters follow the object; flx_adapter_marks(_dev) do not depend on it. */
+int flx_adapters_set_overhang(flx_adapters *adapters, int overhang);
+int flx_adapters_overhang(const flx_adapters *adapters);
 int flx_adapter_marks(flx_ctx *ctx, flx_adapters *adapters, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets,
                       const int32_t *lengths, const uint32_t *order, uint64_t n_reads, uint32_t *marks);
 int flx_adapter_marks_dev(flx_ctx *ctx, flx_adapters *adapters, const void *d_plane, uint64_t plane_bytes, const void *d_offsets,
