@@ -42,6 +42,8 @@ ABI_SYMBOLS = [
     "flx_adapters_set_overhang", "flx_adapters_overhang",
     "flx_complexity_window", "flx_complexity_span", "flx_complexity_bad", "flx_complexity_bad_dev", "flx_pipeline_set_complexity",
     "flx_pipeline_complexity",
+    "flx_endtrim_span", "flx_endtrim_cuts", "flx_endtrim_cuts_dev", "flx_score_batch_endtrim", "flx_score_batch_endtrim_dev",
+    "flx_pipeline_set_endtrim", "flx_pipeline_endtrim",
 ]
 
 
@@ -239,6 +241,15 @@ def load():
         L.flx_complexity_bad_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.c_int, vp]
         L.flx_pipeline_set_complexity.argtypes = [vp, dbl, C.c_int]
         L.flx_pipeline_complexity.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    if hasattr(L, "flx_endtrim_cuts") or not os.environ.get("FLX_LIB_PATH"):  # (an experiment build of an older tree may lack them)
+        L.flx_endtrim_span.argtypes = []
+        L.flx_endtrim_span.restype = C.c_uint32
+        L.flx_endtrim_cuts.argtypes = [vp, vp, u64, vp, vp, vp, u64, u64, vp]
+        L.flx_endtrim_cuts_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, u64, vp]
+        L.flx_score_batch_endtrim.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.POINTER(Params), u64, C.POINTER(Scores)]
+        L.flx_score_batch_endtrim_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.POINTER(Params), u64, C.POINTER(Scores)]
+        L.flx_pipeline_set_endtrim.argtypes = [vp, dbl]
+        L.flx_pipeline_endtrim.argtypes = [vp, C.POINTER(vp)]
     L.flx_last_screen_filter.argtypes = [vp]
     L.flx_last_screen_filter.restype = C.c_char_p
     if hasattr(L, "flx_screenset_create") or not os.environ.get("FLX_LIB_PATH"):  # (an experiment build of an older tree may lack them)

@@ -119,10 +119,15 @@ class Context:
 
     # ---- seam 2: per-read scoring (host buffers) -----------------------------------------------
     def score_reads(self, plane, offsets, lengths, params, kmers=None, order=None, child_capacity=None, split_window_q=None,
-                    adapters=None, seq_plane=None):
+                    adapters=None, seq_plane=None, trim_ends_q=None):
         """Batched Read::Read.  Returns a dict of numpy arrays in input order.  split_window_q (Phred mode only): the reads are
         split at their low-quality windows (flx_score_batch_qsplit).  adapters (an Adapters, Phred mode only) with seq_plane, the
-        sequences at the offsets of the qualities: the adapters are cut off the read ends (flx_score_batch_adapters)."""
+        sequences at the offsets of the qualities: the adapters are cut off the read ends (flx_score_batch_adapters).  trim_ends_q
+        (Phred mode only, a quality on the scale of min_window_q): the low-quality ends are cut off (flx_score_batch_endtrim with
+        t = qsplit_threshold(trim_ends_q))."""
+        if trim_ends_q is not None and (kmers is not None or split_window_q is not None or adapters is not None):
+            raise ValueError("trim_ends_q is for Phred mode, and not with split_window_q or adapters")
+        endtrim_t = None if trim_ends_q is None else qsplit_threshold(trim_ends_q)
         if split_window_q is not None and kmers is not None:
             raise ValueError("split_window_q is for Phred mode")
         if adapters is not None:
@@ -161,6 +166,9 @@ class Context:
             if adapters is not None:
                 rc = self.L.flx_score_batch_adapters(self.h, adapters.h, plane.ctypes.data, seq_plane.ctypes.data, plane.nbytes,
                                                      offsets.ctypes.data, lengths.ctypes.data, ordp, n, C.byref(params), C.byref(s))
+            elif endtrim_t is not None:
+                rc = self.L.flx_score_batch_endtrim(self.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data,
+                                                    ordp, n, C.byref(params), endtrim_t, C.byref(s))
             elif split_window_q is not None:
                 rc = self.L.flx_score_batch_qsplit(self.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data,
                                                    ordp, n, C.byref(params), float(split_window_q), C.byref(s))
@@ -180,7 +188,8 @@ class Context:
 
     # ---- seam 2, streaming ----------------------------------------------------------------------
     def score_stream(self, chunks, params, kmers=None, chunk_bytes=1 << 20, chunk_reads=1 << 12, grow=False, split_window_q=None,
-                     exclude=None, exclude_percent=10.0, adapters=None, max_low_complexity=None, low_complexity_score=20):
+                     exclude=None, exclude_percent=10.0, adapters=None, max_low_complexity=None, low_complexity_score=20,
+                     trim_ends_q=None):
         """flx_pipeline_*: `chunks` is an iterable of lists of byte strings (Phred mode: qualities, k-mer mode: sequences).
         Every chunk is packed into the pipeline's pinned buffer and submitted; returns the same dict as score_reads for
         all reads in submission order.  grow: enlarge the slots (flx_pipeline_reserve) for a chunk that does not fit.
@@ -189,7 +198,8 @@ class Context:
         the result also has "hits" and "excluded".  adapters (an Adapters, Phred mode): flx_pipeline_set_adapters; every chunk is
         such a PAIR as well and the result also has "adapter_keys" (n x 2: head, tail).  max_low_complexity (a percentage):
         flx_pipeline_set_complexity with low_complexity_score; in Phred mode every chunk is such a PAIR too, and the result also has
-        "bad_windows" and "low_complexity"."""
+        "bad_windows" and "low_complexity".  trim_ends_q (Phred mode): flx_pipeline_set_endtrim before the first chunk; the result
+        also has "endtrim_cuts" (n x 2: head, tail)."""
         L = self.L
         pipe = C.c_void_p()
         self._check(L.flx_pipeline_create(self.h, kmers.h if kmers is not None else None, C.byref(params), chunk_bytes,
@@ -205,6 +215,8 @@ class Context:
                 self._check(L.flx_pipeline_set_adapters(pipe, adapters.h))
             if max_low_complexity is not None:
                 self._check(L.flx_pipeline_set_complexity(pipe, float(max_low_complexity), int(low_complexity_score)))
+            if trim_ends_q is not None:
+                self._check(L.flx_pipeline_set_endtrim(pipe, float(trim_ends_q)))
             for strings in chunks:
                 seqs = None
                 if two_planes:
@@ -262,6 +274,10 @@ class Context:
                 kp = C.c_void_p()
                 self._check(L.flx_pipeline_adapters(pipe, C.byref(kp)))
                 out["adapter_keys"] = take(kp, np.uint32, 2 * n).reshape(-1, 2)
+            if trim_ends_q is not None:
+                cp = C.c_void_p()
+                self._check(L.flx_pipeline_endtrim(pipe, C.byref(cp)))
+                out["endtrim_cuts"] = take(cp, np.uint32, 2 * n).reshape(-1, 2)
             return out
         finally:
             L.flx_pipeline_destroy(pipe)
@@ -457,6 +473,26 @@ class Context:
     def complexity_bad_dev(self, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, score, d_bad):
         self._check(self.L.flx_complexity_bad_dev(self.h, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, int(score), d_bad))
 
+    # ---- quality trimming of the read ends -----------------------------------------------------------
+    def endtrim_cuts(self, plane, offsets, lengths, t, order=None):
+        """flx_endtrim_cuts: for every read of the QUALITY plane its head cut and its tail cut against the threshold t (0 <= t < 2^32
+        on the scale of qsplit_table(); qsplit_threshold(Q) for a quality Q).  uint32 array (n, 2) in input order."""
+        n = len(lengths)
+        plane = np.ascontiguousarray(plane, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        out = np.full(2 * max(n, 1), 0xA5A5A5A5, dtype=np.uint32)
+        ordp = None
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.uint32)
+            ordp = order.ctypes.data
+        self._check(self.L.flx_endtrim_cuts(self.h, plane.ctypes.data, plane.nbytes, offsets.ctypes.data, lengths.ctypes.data, ordp, n,
+                                            int(t), out.ctypes.data))
+        return out[:2 * n].reshape(-1, 2)
+
+    def endtrim_cuts_dev(self, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, t, d_cuts):
+        self._check(self.L.flx_endtrim_cuts_dev(self.h, d_plane, plane_bytes, d_offsets, d_lengths, d_order, n, int(t), d_cuts))
+
     # ---- adapter trimming -------------------------------------------------------------------------
     def adapter_cuts(self, plane, offsets, lengths, adapters, order=None):
         """flx_adapter_cuts: for every read of the SEQUENCE plane its two keys, (jbest << 8) | pattern of the adapter occurrence that
@@ -612,6 +648,11 @@ def qsplit_threshold(q):
     if rc:
         raise FlxError(rc, "split_window_q must be greater than 0 and less than 100")
     return int(t.value)
+
+
+def endtrim_span():
+    """Quality bytes per work item of the end-trimming kernel (flx_endtrim_span; no device needed)."""
+    return int(_lib.load().flx_endtrim_span())
 
 
 def screen_threshold(percent):

@@ -49,6 +49,7 @@ struct Args {
     bool max_low_complexity_set = false; double max_low_complexity = 0;  // not a reference flag: --max_low_complexity P drops reads with at least P % of their 64-base windows simple repeats
     bool low_complexity_score_set = false; long long low_complexity_score = 20;  // --low_complexity_score T: a window is a simple repeat above T tenths on sdust's scale (-1: not an integer)
     bool adapter_overhang_set = false; long long adapter_overhang = 0;  // --adapter_overhang O: adapter bases that may lie beyond a read's edge, 0: off (-1: not an integer)
+    bool trim_ends_q_set = false; double trim_ends_q = 0;  // not a reference flag: --trim_ends_q Q cuts the low-quality ends off the reads (Phred mode)
 };
 enum ParsingResult { GOOD, BAD, HELP, VERSION };
 
@@ -129,8 +130,8 @@ static long long whole_number(const std::string &value) {
 // reference reads the width out of an untouched `struct winsize` — 0 in practice: the description comes out one word per line and,
 // the other widths being unsigned differences that wrap around, nothing else is wrapped at all.  Both cases are restated here.
 // (--gpus, --gzip, --bam, --report, --split_window_q, --exclude, --exclude_percent, --exclude_k, --trim_adapters, --adapter_errors,
-// --adapter_window, --split_adapters, --adapter_split_errors, --max_low_complexity, --low_complexity_score and --adapter_overhang, this
-// binary's flags of its own, are documented in README.md: the menu is the reference's.)
+// --adapter_window, --split_adapters, --adapter_split_errors, --max_low_complexity, --low_complexity_score, --adapter_overhang and
+// --trim_ends_q, this binary's flags of its own, are documented in README.md: the menu is the reference's.)
 static std::vector<std::string> help_wrap(const std::string &in, size_t width, size_t first = 0) {  // src/args.h:94-149
     std::vector<std::string> out;
     size_t cur = first ? first : width, linesize = 0;
@@ -310,6 +311,7 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
             else if (flag == "adapter_split_errors") { a.adapter_split_errors = whole_number(need("adapter_split_errors")); a.adapter_split_errors_set = true; }
             else if (flag == "max_low_complexity") { a.max_low_complexity = read_double("float", need("max_low_complexity")); a.max_low_complexity_set = true; }
             else if (flag == "adapter_overhang") { a.adapter_overhang = whole_number(need("adapter_overhang")); a.adapter_overhang_set = true; }
+            else if (flag == "trim_ends_q") { a.trim_ends_q = read_double("float", need("trim_ends_q")); a.trim_ends_q_set = true; }
             else if (flag == "low_complexity_score") { a.low_complexity_score = whole_number(need("low_complexity_score")); a.low_complexity_score_set = true; }
             else throw ParseError("Error: flag could not be matched: " + flag);
         }
@@ -335,7 +337,8 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     for (auto &f : files)
         if (!file_exists(f)) { std::cerr << "Error: cannot find file: " << f << "\n"; return BAD; }
     if (!a.trim && !a.split_set && !a.target_bases_set && !a.keep_percent_set && !a.min_length_set && !a.max_length_set &&
-        !a.min_mean_q_set && !a.min_window_q_set && !a.split_window_q_set && !a.exclude_set && !a.trim_adapters_set && !a.max_low_complexity_set) {
+        !a.min_mean_q_set && !a.min_window_q_set && !a.split_window_q_set && !a.exclude_set && !a.trim_adapters_set && !a.max_low_complexity_set &&
+        !a.trim_ends_q_set) {
         std::cerr << "Error: no thresholds set, you must use one of the following options:\n";
         std::cerr << "target_bases, keep_percent, min_length, max_length, min_mean_q, min_window_q, trim, split\n";
         return BAD;
@@ -394,6 +397,12 @@ static ParsingResult parse_args(int argc, char **argv, Args &a) {
     if (a.adapter_overhang_set && (a.adapter_overhang < 0 || a.adapter_overhang > 52)) {
         std::cerr << "Error: the value for --adapter_overhang must be an integer between 0 and 52\n"; return BAD; }
     if (a.adapter_overhang_set && !a.trim_adapters_set) { std::cerr << "Error: --adapter_overhang needs --trim_adapters\n"; return BAD; }
+    // --trim_ends_q: behind every check above
+    if (a.trim_ends_q_set && !(a.trim_ends_q > 0.0 && a.trim_ends_q < 100.0)) {
+        std::cerr << "Error: the value for --trim_ends_q must be greater than 0 and less than 100\n"; return BAD; }
+    if (a.trim_ends_q_set && some_reference) { std::cerr << "Error: --trim_ends_q cannot be used with an external reference\n"; return BAD; }
+    if (a.trim_ends_q_set && a.split_window_q_set) { std::cerr << "Error: --trim_ends_q cannot be used with --split_window_q\n"; return BAD; }
+    if (a.trim_ends_q_set && a.trim_adapters_set) { std::cerr << "Error: --trim_ends_q cannot be used with --trim_adapters\n"; return BAD; }
     return GOOD;
 }
 

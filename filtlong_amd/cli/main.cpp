@@ -103,9 +103,10 @@ static int exchange_totals(const Run &run, const Pass1 &p, const flx_scores &res
         std::cerr << "  excluded by reference: " << int_to_string((long long)excluded_reads) << " reads (" << int_to_string((long long)excluded_bases) << " bp)\n";
     if (run.low_complexity() && rank == 0)
         std::cerr << "  low complexity: " << int_to_string((long long)lowc_reads) << " reads (" << int_to_string((long long)lowc_bases) << " bp)\n";
-    if ((args.trim || args.split_set || args.split_window_q_set || args.trim_adapters_set) && rank == 0) {  // src/main.cpp:155-166 (--split_window_q: "after splitting")
+    if ((args.trim || args.split_set || args.split_window_q_set || args.trim_adapters_set || args.trim_ends_q_set) && rank == 0) {  // src/main.cpp:155-166 (--split_window_q: "after splitting")
         if (args.split_adapters) std::cerr << "  split at adapters: " << int_to_string((long long)split_reads) << " reads\n";
         if (args.trim_adapters_set) std::cerr << "  after adapter trimming: ";
+        else if (args.trim_ends_q_set) std::cerr << "  after quality trimming: ";
         else if (args.trim && args.split_set) std::cerr << "  after trimming and splitting: ";
         else if (args.trim) std::cerr << "  after trimming: ";
         else std::cerr << "  after splitting: ";

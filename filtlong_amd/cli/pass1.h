@@ -50,7 +50,7 @@ static int open_reads_input(Run &run, ReadsInput &in) {
             if (file.open(args.input_reads) && bam_detect(file.p, file.n)) in.streamed = false;
         }
         in.data.bam = &kBamHooks;
-        in.data.keep_bam = args.bam && !args.trim && !args.split_set && !args.split_window_q_set && !args.trim_adapters_set;  // (--bam: the reads go out whole, as their original records)
+        in.data.keep_bam = args.bam && !args.trim && !args.split_set && !args.split_window_q_set && !args.trim_adapters_set && !args.trim_ends_q_set;  // (--bam: the reads go out whole, as their original records)
     }
     if (in.streamed ? !in.blocks.open(args.input_reads, true) : !in.data.open(args.input_reads)) {
         if (!in.streamed && !in.data.bam_error.empty()) std::cerr << "Error: could not read BAM input " << args.input_reads << ": " << in.data.bam_error << "\n";
@@ -118,6 +118,8 @@ struct Scorer {
         // --trim_adapters: the pipeline cuts the adapters off the read ends and returns at most one child per read (with --split_adapters
         // the object also splits at the adapters inside a read: any number of children); the same second plane
         if (run.adapters && flx_pipeline_set_adapters(pipe, run.adapters) != FLX_OK) return false;
+        // --trim_ends_q: the pipeline cuts the low-quality ends off the reads and returns at most one child per read; the qualities suffice
+        if (run.args.trim_ends_q_set && flx_pipeline_set_endtrim(pipe, run.args.trim_ends_q) != FLX_OK) return false;
         // --max_low_complexity: the pipeline also counts the bad windows of every read, behind the screen; the same second plane
         return !run.low_complexity() ||
                flx_pipeline_set_complexity(pipe, run.args.max_low_complexity, (int)run.args.low_complexity_score) == FLX_OK;
@@ -207,6 +209,7 @@ struct Scorer {
         if (flx_pipeline_finish(pipe, &res, &n_scored) != FLX_OK || n_scored != n) return report ? run.fail("scoring") : 1;
         if (run.excluding() && flx_pipeline_screen(pipe, &run.screen_hits, &run.screen_excluded) != FLX_OK) return report ? run.fail("scoring") : 1;
         if (run.adapters && flx_pipeline_adapters(pipe, &run.adapter_keys) != FLX_OK) return report ? run.fail("scoring") : 1;
+        if (run.args.trim_ends_q_set && flx_pipeline_endtrim(pipe, &run.endtrim_cuts) != FLX_OK) return report ? run.fail("scoring") : 1;
         if (run.low_complexity() && flx_pipeline_complexity(pipe, &run.complexity_bad, &run.complexity_flagged) != FLX_OK) return report ? run.fail("scoring") : 1;
         return kGoOn;
     }

@@ -61,6 +61,7 @@ struct Run {
     flx_adapters *adapters = nullptr;          // --trim_adapters: the patterns (reference.h: build_adapters) ...
     std::vector<std::string> adapter_names;    // ... the names of their sequences (pattern p belongs to sequence p / 2) ...
     const uint32_t *adapter_keys = nullptr;    // ... and, once the scores are in, every read's head and tail key (owned by the pipeline)
+    const uint32_t *endtrim_cuts = nullptr;    // --trim_ends_q: once the scores are in, every read's head and tail cut (owned by the pipeline)
     flx_params prm;
 
     explicit Run(const Args &a) : args(a) {

@@ -38,6 +38,8 @@ static void print_read_blocks(std::ostream &os, const Run &run, const Pass1 &p, 
             bad.push_back({0, lengths[i]});
         } else if (run.adapter_keys && res.first[i] == -1 && lengths[i] > 0) {  // --trim_adapters: the two cuts leave nothing
             bad.push_back({0, lengths[i]});
+        } else if (run.endtrim_cuts && res.first[i] == -1 && lengths[i] > 0) {  // --trim_ends_q: the two cuts leave nothing
+            bad.push_back({0, lengths[i]});
         }
         if (!bad.empty()) {
             os << "        bad ranges = ";
@@ -68,6 +70,8 @@ static void print_read_blocks(std::ostream &os, const Run &run, const Pass1 &p, 
                 os << "          middle adapters = " << ranges << " ranges (" << bp << " bp)\n";
             }
         }
+        if (run.endtrim_cuts)  // --trim_ends_q: the bases cut off either end, behind the lines of the parent's block
+            os << "          quality trim = start " << run.endtrim_cuts[2 * i] << ", end " << run.endtrim_cuts[2 * i + 1] << "\n";
         if (run.screen_hits)  // --exclude: behind the lines of the parent's block
             os << "          excluded = " << (run.screen_excluded[i] ? "yes" : "no") << " (" << run.screen_hits[i] << " of "
                << (lengths[i] >= run.exclude_k ? lengths[i] - run.exclude_k + 1 : 0) << " " << run.exclude_k << "-mers)\n";

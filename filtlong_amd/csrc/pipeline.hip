@@ -19,6 +19,9 @@
 // adapters.hip: flx_score_batch_adapters_dev that also leaves the keys [2 n] in d_keys (NULL: in a workspace of its own)
 int flx_adapters_score_dev(flx_ctx *ctx, flx_adapters *ad, const void *d_plane, const void *d_seq_plane, uint64_t plane_bytes, const void *d_offsets,
                            const void *d_lengths, const void *d_order, uint64_t n_reads, const flx_params *params, flx_scores *out, uint32_t *d_keys);
+// endtrim.hip: flx_score_batch_endtrim_dev that also leaves the cuts [2 n] in d_cuts (NULL: in a workspace of its own)
+int flx_endtrim_score_dev(flx_ctx *ctx, const void *d_plane, uint64_t plane_bytes, const void *d_offsets, const void *d_lengths, const void *d_order,
+                          uint64_t n_reads, const flx_params *params, uint64_t t, flx_scores *out, uint32_t *d_cuts);
 
 namespace {
 
@@ -38,6 +41,7 @@ struct Slot {
     uint32_t *d_hits = nullptr;  // with a screen only
     uint8_t *d_excl = nullptr;
     uint32_t *d_keys = nullptr;  // with adapters only: [2 n]
+    uint32_t *d_cuts = nullptr;  // with the quality trimming of the ends only: [2 n]
     uint32_t *d_bad = nullptr;   // with the low-complexity filter only
     uint8_t *d_lowc = nullptr;
     hipEvent_t copied = nullptr;
@@ -59,6 +63,8 @@ struct flx_pipeline {
     uint64_t complexity_t = 0;
     int complexity_score = 0;
     flx_adapters *adapters = nullptr;         // flx_pipeline_set_adapters: Phred mode, adapters cut off the read ends
+    bool endtrim = false;    // flx_pipeline_set_endtrim: Phred mode, the low-quality ends of the reads cut off
+    uint64_t endtrim_t = 0;
     int planes = 1;          // 2: a Phred-mode pipeline with a screen or adapters — qualities, then sequences, plane_bytes each
     bool submitted = false;  // a chunk has been submitted
     uint64_t cap_bytes = 0, cap_reads = 0;
@@ -90,6 +96,7 @@ struct flx_pipeline {
     std::vector<uint32_t> bad_windows;    // with the low-complexity filter: bad windows of every read, and who was flagged
     std::vector<uint8_t> low_complexity;
     std::vector<uint32_t> adapter_keys;   // with adapters: head and tail key of every read
+    std::vector<uint32_t> endtrim_cuts;   // with the quality trimming of the ends: head and tail cut of every read
     double h2d_s = 0, score_s = 0;
 };
 
@@ -117,6 +124,7 @@ int alloc_slot(flx_pipeline *p, Slot &s) {
         FLX_HIP(ctx, hipMalloc((void **)&s.d_excl, nr));
     }
     if (p->adapters) FLX_HIP(ctx, hipMalloc((void **)&s.d_keys, nr * 8 + 8));
+    if (p->endtrim) FLX_HIP(ctx, hipMalloc((void **)&s.d_cuts, nr * 8 + 8));
     if (p->complexity) {
         FLX_HIP(ctx, hipMalloc((void **)&s.d_bad, nr * 4));
         FLX_HIP(ctx, hipMalloc((void **)&s.d_lowc, nr));
@@ -129,7 +137,7 @@ void free_slot(Slot &s) {
     if (s.h_plane) (void)hipHostFree(s.h_plane);
     if (s.h_off) (void)hipHostFree(s.h_off);
     for (void *d : {(void *)s.d_plane, (void *)s.d_off, (void *)s.d_mean, (void *)s.d_win, (void *)s.d_pass, (void *)s.d_first,
-                    (void *)s.d_last, (void *)s.d_coff, (void *)s.d_hits, (void *)s.d_excl, (void *)s.d_keys, (void *)s.d_bad, (void *)s.d_lowc})
+                    (void *)s.d_last, (void *)s.d_coff, (void *)s.d_hits, (void *)s.d_excl, (void *)s.d_keys, (void *)s.d_cuts, (void *)s.d_bad, (void *)s.d_lowc})
         if (d) (void)hipFree(d);
     if (s.copied) (void)hipEventDestroy(s.copied);
     s = Slot();
@@ -155,7 +163,7 @@ int score_slot(flx_pipeline *p, Slot &s) {
     const uint64_t n = s.n;
     FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, s.copied, 0));
     const bool kmer_mode = p->set && flx_kmerset_size(p->set) > 0;
-    const bool want_children = (kmer_mode && (p->params.trim || p->params.split_set)) || p->qsplit || p->adapters;
+    const bool want_children = (kmer_mode && (p->params.trim || p->params.split_set)) || p->qsplit || p->adapters || p->endtrim;
     const uint8_t *d_seq = s.d_plane + (uint64_t)(p->planes - 1) * s.plane_bytes;  // the sequences are the chunk's last plane
     flx_scores dev;
     for (;;) {
@@ -169,6 +177,7 @@ int score_slot(flx_pipeline *p, Slot &s) {
             dev.child_passed = p->d_cpass; dev.child_capacity = p->child_cap;
         }
         const int rc = p->adapters ? flx_adapters_score_dev(ctx, p->adapters, s.d_plane, d_seq, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, &p->params, &dev, s.d_keys)
+                       : p->endtrim ? flx_endtrim_score_dev(ctx, s.d_plane, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, &p->params, p->endtrim_t, &dev, s.d_cuts)
                        : p->qsplit ? flx_score_batch_qsplit_dev(ctx, s.d_plane, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, &p->params, p->qsplit_q, &dev)
                                  : flx_score_batch_dev(ctx, p->set, s.d_plane, s.plane_bytes, s.d_off, s.d_len, s.d_ord, n, &p->params, &dev);
         if (rc == FLX_ERR_CAPACITY && dev.n_children > p->child_cap) {
@@ -216,6 +225,10 @@ int score_slot(flx_pipeline *p, Slot &s) {
     if (p->adapters) {
         p->adapter_keys.resize(2 * (at + n));
         if (n) FLX_HIP(ctx, hipMemcpyAsync(&p->adapter_keys[2 * at], s.d_keys, n * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (p->endtrim) {
+        p->endtrim_cuts.resize(2 * (at + n));
+        if (n) FLX_HIP(ctx, hipMemcpyAsync(&p->endtrim_cuts[2 * at], s.d_cuts, n * 8, hipMemcpyDeviceToHost, st));
     }
     const uint64_t nc = want_children ? dev.n_children : 0;
     const uint64_t cbase = p->child_offsets.back();
@@ -327,6 +340,7 @@ extern "C" int flx_pipeline_set_qsplit(flx_pipeline *p, double q) {
     if (p->set && flx_kmerset_size(p->set) > 0) return flx_fail(ctx, FLX_ERR_STATE, "split_window_q is for Phred mode: the pipeline has a k-mer set");
     if (p->submitted) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_qsplit after flx_pipeline_submit");
     if (p->adapters) return flx_fail(ctx, FLX_ERR_STATE, "split_window_q and adapters do not compose: the pipeline has adapters");
+    if (p->endtrim) return flx_fail(ctx, FLX_ERR_STATE, "split_window_q and trim_ends_q do not compose: the pipeline trims the read ends by quality");
     uint64_t t = 0;
     if (flx_qsplit_threshold(q, &t) != FLX_OK) return flx_fail(ctx, FLX_ERR_INVALID, "split_window_q must be greater than 0 and less than 100");
     if (p->params.trim || p->params.split_set) return flx_fail(ctx, FLX_ERR_INVALID, "trim/split need a k-mer set: not with split_window_q");
@@ -363,6 +377,7 @@ extern "C" int flx_pipeline_set_adapters(flx_pipeline *p, flx_adapters *adapters
     if (p->submitted || p->handed_out) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_adapters after flx_pipeline_next_buffer / flx_pipeline_submit");
     if (p->set && flx_kmerset_size(p->set) > 0) return flx_fail(ctx, FLX_ERR_STATE, "adapters are for Phred mode: the pipeline has a k-mer set");
     if (p->qsplit) return flx_fail(ctx, FLX_ERR_STATE, "adapters and split_window_q do not compose: the pipeline splits at low-quality windows");
+    if (p->endtrim) return flx_fail(ctx, FLX_ERR_STATE, "adapters and trim_ends_q do not compose: the pipeline trims the read ends by quality");
     if (!adapters) return flx_fail(ctx, FLX_ERR_INVALID, "flx_pipeline_set_adapters: adapters must not be NULL");
     if (p->params.trim || p->params.split_set) return flx_fail(ctx, FLX_ERR_INVALID, "trim/split need a k-mer set: not with adapters");
     FLX_HIP(ctx, hipSetDevice(ctx->device));
@@ -393,6 +408,31 @@ extern "C" int flx_pipeline_complexity(flx_pipeline *p, const uint32_t **bad, co
     if (!p->queue.empty()) return flx_fail(p->ctx, FLX_ERR_STATE, "flx_pipeline_complexity before flx_pipeline_finish");
     if (bad) *bad = p->bad_windows.data();
     if (flagged) *flagged = p->low_complexity.data();
+    return FLX_OK;
+}
+
+extern "C" int flx_pipeline_set_endtrim(flx_pipeline *p, double q) {
+    if (!p) return FLX_ERR_INVALID;
+    flx_ctx *ctx = p->ctx;
+    if (p->submitted || p->handed_out) return flx_fail(ctx, FLX_ERR_STATE, "flx_pipeline_set_endtrim after flx_pipeline_next_buffer / flx_pipeline_submit");
+    if (p->set && flx_kmerset_size(p->set) > 0) return flx_fail(ctx, FLX_ERR_STATE, "trim_ends_q is for Phred mode: the pipeline has a k-mer set");
+    if (p->qsplit) return flx_fail(ctx, FLX_ERR_STATE, "trim_ends_q and split_window_q do not compose: the pipeline splits at low-quality windows");
+    if (p->adapters) return flx_fail(ctx, FLX_ERR_STATE, "trim_ends_q and adapters do not compose: the pipeline has adapters");
+    uint64_t t = 0;
+    if (flx_qsplit_threshold(q, &t) != FLX_OK) return flx_fail(ctx, FLX_ERR_INVALID, "trim_ends_q must be greater than 0 and less than 100");
+    if (p->params.trim || p->params.split_set) return flx_fail(ctx, FLX_ERR_INVALID, "trim/split need a k-mer set: not with trim_ends_q");
+    FLX_HIP(ctx, hipSetDevice(ctx->device));
+    p->endtrim = true;
+    p->endtrim_t = t;
+    return realloc_slots(p);  // (the cuts of every slot)
+}
+
+extern "C" int flx_pipeline_endtrim(flx_pipeline *p, const uint32_t **cuts) {
+    if (!p) return FLX_ERR_INVALID;
+    if (!p->endtrim) return flx_fail(p->ctx, FLX_ERR_STATE, "flx_pipeline_endtrim on a pipeline without trim_ends_q");
+    std::unique_lock<std::mutex> lk(p->mu);
+    if (!p->queue.empty()) return flx_fail(p->ctx, FLX_ERR_STATE, "flx_pipeline_endtrim before flx_pipeline_finish");
+    if (cuts) *cuts = p->endtrim_cuts.data();
     return FLX_OK;
 }
 

@@ -59,11 +59,12 @@ extern "C" int flx_score_batch_dev(flx_ctx *ctx, const flx_kmerset *set, const v
 
 // the host-array form of a scoring call: everything staged through device buffers of the call's own.  split_window_q (not NULL:
 // flx_score_batch_qsplit) sends the batch through flx_score_batch_qsplit_dev instead of flx_score_batch_dev; adapters (not NULL:
-// flx_score_batch_adapters, with the sequences in seq_plane) through flx_score_batch_adapters_dev.
+// flx_score_batch_adapters, with the sequences in seq_plane) through flx_score_batch_adapters_dev; endtrim_t (not NULL:
+// flx_score_batch_endtrim) through flx_score_batch_endtrim_dev.
 static int score_batch_host(flx_ctx *ctx, const flx_kmerset *set, const uint8_t *plane, uint64_t plane_bytes,
                             const uint64_t *offsets, const int32_t *lengths, const uint32_t *order,
                             uint64_t n_reads, const flx_params *params, const double *split_window_q, flx_scores *out,
-                            flx_adapters *adapters = nullptr, const uint8_t *seq_plane = nullptr) {
+                            flx_adapters *adapters = nullptr, const uint8_t *seq_plane = nullptr, const uint64_t *endtrim_t = nullptr) {
     FLX_CHECK(validate_common(ctx, n_reads, plane_bytes, params, out));
     if (n_reads == 0) {
         out->n_children = 0;
@@ -71,13 +72,14 @@ static int score_batch_host(flx_ctx *ctx, const flx_kmerset *set, const uint8_t 
         return FLX_OK;
     }
     if (!plane || !offsets || !lengths) return flx_fail(ctx, FLX_ERR_INVALID, "plane/offsets/lengths must not be NULL");
-    // (with adapters `order` must be a permutation: every key is written by exactly the patterns of its own read end)
-    FLX_CHECK(flx_check_reads(ctx, plane_bytes, offsets, lengths, adapters ? order : nullptr, n_reads));
+    // (with adapters `order` must be a permutation: every key is written by exactly the patterns of its own read end; so are the cuts
+    // of the read ends)
+    FLX_CHECK(flx_check_reads(ctx, plane_bytes, offsets, lengths, adapters || endtrim_t ? order : nullptr, n_reads));
     PhaseTimer pt;
     pt.mark("validate");
     FLX_HIP(ctx, hipSetDevice(ctx->device));
     const bool kmer_mode = set && flx_kmerset_size(set) > 0;
-    const bool want_children = (kmer_mode && (params->trim || params->split_set)) || split_window_q || adapters;
+    const bool want_children = (kmer_mode && (params->trim || params->split_set)) || split_window_q || adapters || endtrim_t;
     if (want_children && !out->child_offsets)
         return flx_fail(ctx, FLX_ERR_INVALID, "trim/split requested but child outputs are NULL");
 
@@ -155,6 +157,8 @@ static int score_batch_host(flx_ctx *ctx, const flx_kmerset *set, const uint8_t 
     int rc;
     if (adapters)
         rc = flx_score_batch_adapters_dev(ctx, adapters, d_plane.p, d_seq.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr, n_reads, params, &dev);
+    else if (endtrim_t)
+        rc = flx_score_batch_endtrim_dev(ctx, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr, n_reads, params, *endtrim_t, &dev);
     else if (split_window_q)
         rc = flx_score_batch_qsplit_dev(ctx, d_plane.p, plane_bytes, d_off.p, d_len.p, order ? d_ord.p : nullptr, n_reads, params, *split_window_q, &dev);
     else
@@ -211,4 +215,12 @@ extern "C" int flx_score_batch_adapters(flx_ctx *ctx, flx_adapters *adapters, co
     if (n_reads && !seq_plane) return flx_fail(ctx, FLX_ERR_INVALID, "the sequence plane must not be NULL");
     if (params && (params->trim || params->split_set)) return flx_fail(ctx, FLX_ERR_INVALID, "trim/split need a k-mer set: not with adapters");
     return score_batch_host(ctx, nullptr, plane, plane_bytes, offsets, lengths, order, n_reads, params, nullptr, out, adapters, seq_plane);
+}
+
+extern "C" int flx_score_batch_endtrim(flx_ctx *ctx, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets, const int32_t *lengths,
+                                       const uint32_t *order, uint64_t n_reads, const flx_params *params, uint64_t t, flx_scores *out) {
+    if (!ctx) return FLX_ERR_INVALID;
+    if (t > 0xffffffffull) return flx_fail(ctx, FLX_ERR_INVALID, "flx_score_batch_endtrim: t must be below 2^32");
+    if (params && (params->trim || params->split_set)) return flx_fail(ctx, FLX_ERR_INVALID, "trim/split need a k-mer set: not with trim_ends_q");
+    return score_batch_host(ctx, nullptr, plane, plane_bytes, offsets, lengths, order, n_reads, params, nullptr, out, nullptr, nullptr, &t);
 }

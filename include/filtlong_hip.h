@@ -359,6 +359,37 @@ int flx_adapter_marks_dev(flx_ctx *ctx, flx_adapters *adapters, const void *d_pl
                           const void *d_lengths, const void *d_order, uint64_t n_reads, uint32_t *d_marks);
 
 /* ------------------------------------------------------------------------------------------
+ * quality trimming of the read ends (added under version 4; the reference has no counterpart: its users run seqtk trimfq, cutadapt
+ * -q or chopper --trim-approach over the file first).  Phred mode; the plane holds QUALITY strings.  Defined on integers, on the
+ * scale and the table of --split_window_q:
+ *   weight     w(b) = (int64)E[b] - (int64)t for quality byte b, E = flx_qsplit_table, 0 <= t < 2^32 (for a quality Q on the 0-100
+ *              scale t = flx_qsplit_threshold(Q)): positive for a base worse than the threshold, zero for one exactly on it
+ *   head cut   h = the SMALLEST j, 0 <= j <= L, at which P(j) = sum of w(q[i]) for i < j takes its maximum (P(0) = 0: no positive
+ *              prefix sum, no cut; ties keep more of the read)
+ *   tail cut   c = the smallest c at which S(c) = sum of w(q[L - 1 - i]) for i < c takes its maximum
+ * Both cuts are taken over the WHOLE read and independently of each other; |w| < 2^32 and L < 2^31 keep every sum inside int64.
+ *   children   the rule of the adapter ends with s = h and e = L - c: both cuts 0: the read goes on as itself (no child, first 0,
+ *              last L); s < e: one child [s, e); s >= e: no child, first = last = -1, passed = 0.  A child's scores are the bits
+ *              flx_score_batch gives its quality substring, with its own hard cut-offs.
+ * flx_endtrim_cuts(_dev): cuts[2 i] = h and cuts[2 i + 1] = c of read i in input order (`order`, NULL or a permutation, only says
+ * in which order the reads are processed); a length <= 0 gives 0, 0; every entry is written, none accumulated.  FLX_ERR_INVALID
+ * for t >= 2^32.  The work item is a span of flx_endtrim_span() quality bytes of one read (host only: tests place lengths on its
+ * edges), the spans of a read are combined in order by a second small kernel.  Timed as "flx_endtrim".
+ * flx_score_batch_endtrim(_dev): flx_score_batch_adapters(_dev) with the cuts in the place of the adapters' — the same argument
+ * checks, FLX_ERR_CAPACITY with the number of children in out->n_children, params->trim and params->split_set must be 0 — and no
+ * sequence plane.
+ * ---------------------------------------------------------------------------------------- */
+uint32_t flx_endtrim_span(void);
+int flx_endtrim_cuts(flx_ctx *ctx, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets, const int32_t *lengths,
+                     const uint32_t *order, uint64_t n_reads, uint64_t t, uint32_t *cuts);
+int flx_endtrim_cuts_dev(flx_ctx *ctx, const void *d_plane, uint64_t plane_bytes, const void *d_offsets, const void *d_lengths,
+                         const void *d_order, uint64_t n_reads, uint64_t t, uint32_t *d_cuts);
+int flx_score_batch_endtrim(flx_ctx *ctx, const uint8_t *plane, uint64_t plane_bytes, const uint64_t *offsets, const int32_t *lengths,
+                            const uint32_t *order, uint64_t n_reads, const flx_params *params, uint64_t t, flx_scores *out);
+int flx_score_batch_endtrim_dev(flx_ctx *ctx, const void *d_plane, uint64_t plane_bytes, const void *d_offsets, const void *d_lengths,
+                                const void *d_order, uint64_t n_reads, const flx_params *params, uint64_t t, flx_scores *out);
+
+/* ------------------------------------------------------------------------------------------
  * between seam 2 and seam 3 — the reads2 gather     (replaces src/main.cpp:138-147)
  *
  * reads2 = file order with every trimmed / split parent replaced IN PLACE by its children.  Gathers what the global
@@ -493,6 +524,15 @@ int flx_pipeline_adapters(flx_pipeline *p, const uint32_t **keys);
  * pipeline, after flx_pipeline_finish. */
 int flx_pipeline_set_complexity(flx_pipeline *p, double percent, int score_t);
 int flx_pipeline_complexity(flx_pipeline *p, const uint32_t **bad, const uint8_t **flagged);
+/* --trim_ends_q for a Phred-mode pipeline (added under version 4): every chunk then goes through flx_score_batch_endtrim_dev with
+ * t = flx_qsplit_threshold(q); the chunk stays ONE plane of qualities unless a screen or the low-complexity filter adds the sequences.
+ * FLX_ERR_INVALID unless 0 < q < 100; FLX_ERR_STATE after the first flx_pipeline_next_buffer / flx_pipeline_submit, on a pipeline
+ * with a k-mer set, and together with flx_pipeline_set_qsplit or flx_pipeline_set_adapters (in either order: the producers of
+ * children do not compose).
+ * flx_pipeline_endtrim: the cuts (head, tail) of all reads in submission order, a host array of 2 n entries owned by the pipeline,
+ * after flx_pipeline_finish. */
+int flx_pipeline_set_endtrim(flx_pipeline *p, double q);
+int flx_pipeline_endtrim(flx_pipeline *p, const uint32_t **cuts);
 int flx_pipeline_next_buffer(flx_pipeline *p, uint8_t **plane, uint64_t *capacity_bytes, uint64_t *capacity_reads);
 /* Grow both slots to at least this capacity (never shrinks; waits for the chunks in flight first).  For callers that learn
  * the longest read only while streaming.  Not between next_buffer and submit. */
